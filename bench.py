@@ -25,6 +25,18 @@ kernels alone allow (no exchange latency) — the evidence one GPU can give for 
 Prints ONE JSON line (rank 0).  `value` = element-integrations/s of the whole job over the timed
 region (3·cells per step / step time, reaction included in the step time); DoF-updates/s and the
 per-phase rates are extra keys.
+
+A plain run does what that line needs and nothing else: set-up, warm-up, the --steps timed steps, the outputs of
+--dump-outputs, the line.  Everything that measures or checks beyond it runs only under --full (its --no-* switches
+still apply there): the halo-sum check of an N-rank run before the clock, the instrumented pass behind the timed
+region that fills the phases an N-rank run does not record, the HIP-graph step, the PCG2019 reaction rate, the
+distributed CG iteration, the slab sweep, the SpMV plan statistics and the CPU baseline with its parity check.
+
+--dump-outputs DIR (rank 0) writes what the last timed step left for a caller, as float64 .npy files: M_nzval and
+K_nzval (the value arrays, pattern order), b and u (the ionic states, state-major).  An array longer than
+DUMP_SAMPLE entries is sampled at fixed, seeded positions, so that two builds can be compared entry for entry.  The
+ionic states are reset to the initial state after the clock-settling pre-roll, whose length depends on timing: with
+the same arguments every run times the same steps from the same inputs.
 """
 import argparse
 import gc
@@ -72,6 +84,8 @@ BYTES_PER_DOF_UPDATE = 16.0    # in place; 24 when du is materialised
 # v_fma_f64 / v_fmac_f64 = 2), keyed by (matrices, tensor form) as tb_last_kernel_name() reports the instance that ran
 FLOP_PER_INSTANCE = {("K+M", "ISO"): 375 + 354 + 2 * 483, ("K+M", "DIAG"): 430 + 354 + 2 * 465, ("K+M", "GEN"): 430 + 354 + 2 * 609,
                      ("K", "ISO"): 310 + 344 + 2 * 436, ("K", "DIAG"): 365 + 344 + 2 * 418, ("K", "GEN"): 365 + 344 + 2 * 562, ("M", "-"): 97 + 79 + 2 * 153}
+DUMP_SAMPLE = 1 << 20          # --dump-outputs: entries kept of a longer array (8 MiB in float64; four arrays stay below 64 MB)
+DUMP_SEED = 20261016           # --dump-outputs: seed of the sampled positions
 
 
 def parse():
@@ -125,6 +139,12 @@ def parse():
     ap.add_argument("--ionic", default="tt06", choices=["pcg2019", "tt06", "fhn", "ord"],
                     help="ionic model of the reaction step (tt06 = the 19-state model BASELINE's 10M-hex configuration names; "
                          "pcg2019 = the reference's own 7-state model)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline line: halo-sum check, instrumented phase pass (N > 1), HIP-graph step, "
+                         "PCG2019 reaction rate, distributed CG, slab sweep, SpMV plan statistics, CPU baseline (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (M and K values, b, ionic states u) to DIR/<name>.npy in float64; arrays longer than "
+                         "%d entries as a fixed, seeded sample (rank 0)" % DUMP_SAMPLE)
     return ap.parse_args()
 
 
@@ -516,6 +536,7 @@ def main():
                 u0[:, model.phi_index] += (30.0 if self.ns > 2 else 0.5) * (1.0 + np.sin(3.0 * xd_[:, 0] + 2.0 * xd_[:, 1] + xd_[:, 2]))
             self.u0 = np.ascontiguousarray(u0.T).ravel()
             self.u = torch.from_numpy(self.u0).cuda()
+            self.u0_dev = self.u.clone()           # the initial state in HBM: time_steps resets u with a device copy (see there)
             self.f = tb.PointwiseODEFunction(npts, model)
             self.cache = tb.setup_solver_cache(self.f, tb.ForwardEulerCellSolver(dev), u=self.u, keep_du=args.keep_du)
             self.evpool = []
@@ -687,6 +708,9 @@ def main():
             dev.defer_status(True)
             self.preroll(lambda i: self.step(i))                     # untimed: clocks (see --preroll-ms)
             dev.defer_status(False)
+            # the pre-roll's step count depends on timing: warm-up and timed steps start from the initial state.  A device copy keeps the gap between
+            # the pre-roll and the warm-up steps short; re-uploading u0 from the host lengthened it by the upload and cost the timed steps 2.5 % (216^3)
+            self.u.copy_(self.u0_dev)
             for i in range(warmup):
                 self.step(i)                                         # the W warm-up steps, status read per call
             if args.trace_markers:
@@ -824,11 +848,25 @@ def main():
                     "note": "one Jacobi-CG iteration on A = M - dt K under the partition (barrier-bracketed, max over ranks, host-timed over %d iterations, device "
                             "scalars, no host read): interface rows packed first, exchange overlapped with the local SpMV + p'Ap, two all-reduces" % nit}
 
+    def dump_outputs(prob, out_dir):
+        """--dump-outputs: the arrays the last timed step left for its caller, gathered on the device (tb_gather_indexed) at DUMP_SAMPLE seeded
+        positions where an array is longer, written as float64 .npy"""
+        os.makedirs(out_dir, exist_ok=True)
+        arrays = (("M_nzval", prob.M.A.data_ptr(), prob.M.A.n), ("K_nzval", prob.K.A.data_ptr(), prob.K.A.n),
+                  ("b", prob.b.data_ptr(), prob.b.numel()), ("u", prob.u.data_ptr(), prob.u.numel()))
+        for k_, (name_, ptr_, len_) in enumerate(arrays):
+            assert len_ < 2 ** 31, (name_, len_)                     # Int32 positions
+            idx_ = np.arange(len_) if len_ <= DUMP_SAMPLE else np.unique(np.random.default_rng([DUMP_SEED, k_]).integers(0, len_, DUMP_SAMPLE))
+            idx_d = torch.from_numpy(idx_.astype(np.int32)).cuda()
+            val_d = torch.empty(len(idx_), dtype=torch.float64, device="cuda")
+            tb._lib.check(tb.lib().tb_gather_indexed(dev.h, len(idx_), ptr_, idx_d.data_ptr(), val_d.data_ptr()))
+            np.save(os.path.join(out_dir, name_ + ".npy"), val_d.cpu().numpy())
+
     t_setup0 = time.perf_counter()
     pr = Problem(part.local_nel(), part.left, part.right, rank, world, part.interface_nodes(), gd, xd)
     g, dh, sp, npts, ns = pr.g, pr.dh, pr.sp, pr.npts, pr.ns
     t_setup1 = time.perf_counter()
-    if world > 1:
+    if world > 1 and args.full:
         # the exchange carries what it should before anything is timed through it: every rank sends rank + 1 on its shared dofs and must hold
         # rank + 1 + Σ (peer + 1) over the parts it shares each dof with — exactly (small integers), on whichever path was chosen above
         v_ = torch.full((npts,), float(rank + 1), dtype=torch.float64, device="cuda")
@@ -844,15 +882,20 @@ def main():
     torch.cuda.synchronize()
     t_setup2 = time.perf_counter()
     elapsed = pr.time_steps(args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(pr, args.dump_outputs)          # before anything else touches M, K, b or u
     phase = pr.phase
     phase_note = None
-    if pr.pe_mode == "matrix" and args.phase_events == "auto":
+    if pr.pe_mode == "matrix" and args.phase_events == "auto" and args.full:
         inst_ = pr.instrumented_phases(args.steps)
         for k_ in phase:
             if phase[k_] != phase[k_]:                    # not recorded in the timed steps
                 phase[k_] = inst_[k_]
         phase_note = ("the timed steps record the two events around the matrix pass only; source / halo / reaction are from a second pass of %d steps with all six "
                       "events, behind the timed region (its matrix phase: %.4f ms)" % (args.steps, inst_["diffusion"] / args.steps))
+    elif pr.pe_mode == "matrix" and args.phase_events == "auto":
+        phase_note = ("the timed steps record the two events around the matrix pass only; source / halo / reaction (and the rates and roofline figures "
+                      "derived from them) are null: the instrumented pass that measures them runs under --full")
 
     def graph_step_ms(prob):
         """(ms per step, nodes, error) of the step as one HIP-graph launch; never fatal"""
@@ -868,12 +911,12 @@ def main():
                 pass
             return None, None, str(ex)[:200]
 
-    g_ms, g_nodes, g_err = graph_step_ms(pr)
+    g_ms, g_nodes, g_err = graph_step_ms(pr) if args.full else (None, None, None)
     chk = pr.checksums() if args.checksums else None
 
     # outside the timed region: the reference's own 7-state ionic model (PCG2019) on the same points, for the record
     ref_rx = None
-    if args.ionic != "pcg2019":
+    if args.full and args.ionic != "pcg2019":
         mref = tb.PCG2019()
         fref = tb.PointwiseODEFunction(npts, mref)
         uref = torch.from_numpy(np.ascontiguousarray(np.tile(mref.default_initial_state(), (npts, 1)).T).ravel()).cuda()
@@ -891,11 +934,11 @@ def main():
         del cref, uref
 
     # the second rate of the line: CG iterations of the heat solve on the same partition (its own timed region, barrier-bracketed, max over ranks)
-    dist_cg = None if args.no_dist_cg else pr.time_cg()
+    dist_cg = None if (args.no_dist_cg or not args.full) else pr.time_cg()
 
     # N = 1: the slabs a strong-scaling run on N GPUs hands each rank, timed one after the other on this GPU (same kernels, same plans, no exchange)
     slab_sweep = None
-    if world == 1 and not args.no_slab_sweep and n % 8 == 0 and args.layers == 0 and args.mesh == "box":
+    if world == 1 and args.full and not args.no_slab_sweep and n % 8 == 0 and args.layers == 0 and args.mesh == "box":
         slab_sweep = {"layers": {}, "note": "step = M + K + b + %s reaction, cg = one Jacobi-CG iteration on A = M - dt K, each on an %dx%dxL slab of the mesh (the share of one of "
                                            "N = %d/L GPUs under --scaling strong); predicted_speedup = t(%d layers) / t(L layers): what the kernels alone allow, without the halo "
                                            "exchange and the two all-reduces of an iteration; *_graph: the same work as one HIP-graph launch per step / iteration (tb_graph_*); "
@@ -971,13 +1014,26 @@ def main():
             cells_total, dofs_total = full_grid.n_cells, full_grid.n_nodes
         ms = elapsed / K_ * 1e3
         k_ms = phase["diffusion"] / K_            # fused: the one M + K launch
+        # a phase the timed steps did not record: null where the instrumented pass behind the region would have filled it (--phase-events auto on
+        # N ranks without --full), so that the default multi-GPU line stays strict JSON; NaN under an explicit --phase-events matrix | none, as before
+        missing = None if args.phase_events == "auto" else float("nan")
+
+        def per_step(k):
+            return phase[k] / K_ if phase[k] == phase[k] else missing
+
+        def rate(num, k):                          # num per ms of phase k, in 1/s
+            v = per_step(k)
+            return missing if v is None or v != v else num / (v * 1e-3)
         # algorithmic bytes of the dominant launch, each datum once: connectivity 32 B + coordinates 24 B per cell, 27 nz × 8 B per
         # cell and matrix written once — 272 B/cell for one matrix, 488 B/cell for the fused pair (2 × 272 = 544 B/cell if each of the two
         # element-integrations were charged its own mesh read: reported as frac_per_integration)
         bytes_per_cell = (BYTES_PER_CELL_MATRIX + 216.0) if fused else BYTES_PER_CELL_MATRIX
         achieved = bytes_per_cell * g.n_cells / (k_ms * 1e-3) / 1e9
         kname = getattr(pr, "matrix_kernel", "") or ("k_matrix_direct<Hex8<2>,DIFFUSION>" if args.strategy != "patch" else "unknown")   # tb_last_kernel_name() after the step's matrix call
-        mk_ms = k_ms + phase["mass"] / K_
+        mass_ms = per_step("mass")
+        if mass_ms is None and fused:
+            mass_ms = 0.0                         # the fused pass leaves the mass phase without a launch
+        mk_ms = None if mass_ms is None else k_ms + mass_ms
         # FP64 side of the same launch (SURVEY §8d asks for both fractions).  Flops per cell instance counted on the ISA of the shipped kernel
         # (scripts/isa_hist.py on k_patch_hex8_record<K+M,DIAG>, the same element routine as the staged kernel: 430 v_mul_f64 + 354 v_add_f64 + 465 v_fma_f64 → 1 714 flop); a patch re-integrates
         # the halo cells of its rows, so the kernel executes `instances_per_cell` × that; "useful" charges every cell once.
@@ -1000,6 +1056,7 @@ def main():
                                       (" + neighbour halo sum of b" + ("" if args.no_overlap_exchange else " (b is launched first and its exchange posted behind it; the received partials are added behind the reaction step)")) if world > 1 else "", args.ionic.upper()),
                        "mesh": args.mesh, "renumber": args.renumber,
                        "preroll_ms": args.preroll_ms,   # untimed steps in front of the W warm-up steps: the GPU's clocks (see --preroll-ms)
+                       "full": args.full,               # whether the measurements and checks beyond the headline ran (--full)
                        "cells_total": cells_total, "cells_per_gpu": g.n_cells, "dofs_per_gpu": npts, "nnz_per_gpu": sp.nnz, "ionic_model": args.ionic, "ionic_states": ns,
                        "partition": "z-slabs" if gpart is None else "recursive coordinate bisection of the cell centroids (%d parts, this rank: %d neighbour parts, %d shared dofs)"
                                     % (world, len(gpart.neighbours), sum(len(i_) for _, i_ in gpart.neighbours)),
@@ -1013,31 +1070,32 @@ def main():
                         "locality_renumbering": pr.renumber_s, "steps_worth": (t_setup2 - t_setup0) / (elapsed / K_)},
             "pin": FERRITE_PIN,
             **({"checksums": chk} if chk is not None else {}),
-            "phase_ms": ({"mass+diffusion": k_ms} if fused else {"mass": phase["mass"] / K_, "diffusion": k_ms}) | {k: phase[k] / K_ for k in ("source", "halo", "reaction")},
+            "phase_ms": ({"mass+diffusion": k_ms} if fused else {"mass": per_step("mass"), "diffusion": k_ms}) | {k: per_step(k) for k in ("source", "halo", "reaction")},
             **({"phase_ms_note": phase_note} if phase_note else {}),
-            "phase_rates": {"matrix_integrations_per_s": 2 * g.n_cells / (mk_ms * 1e-3),
-                            "source_cells_per_s": g.n_cells / (phase["source"] / K_ * 1e-3),
-                            "reaction_dof_updates_per_s": ns * npts / (phase["reaction"] / K_ * 1e-3)},
+            "phase_rates": {"matrix_integrations_per_s": None if mk_ms is None else 2 * g.n_cells / (mk_ms * 1e-3),
+                            "source_cells_per_s": rate(g.n_cells, "source"),
+                            "reaction_dof_updates_per_s": rate(ns * npts, "reaction")},
             # "bound" names the roofline `achieved` / `peak` are priced against (algorithmic bytes over the HBM peak, the contract's definition); the FP64
             # vector roof sits beside it in `fp64` (SURVEY §8d asks for both), `nearest_roof` says which of the two fractions is the larger, and
             # `limiter` what the counters and phase stamps say holds the kernel below both (profiles/)
             "roofline": {"kernel": kname, "bound": "hbm",
                          "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "traffic": None, "algorithmic_bytes_per_cell": bytes_per_cell, "launch_ms": k_ms,
-                         "frac_per_integration": BYTES_PER_CELL_MATRIX * 2 * g.n_cells / (mk_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                         "frac_per_integration": None if mk_ms is None else BYTES_PER_CELL_MATRIX * 2 * g.n_cells / (mk_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                          "fp64": {"bound": "fp64-valu", "achieved": tf_useful, "achieved_incl_halo": tf_useful * inst_per_cell, "peak": FP64_VECTOR_TFLOPS, "unit": "TFLOP/s",
                                   "frac": tf_useful / FP64_VECTOR_TFLOPS, "frac_incl_halo": tf_useful * inst_per_cell / FP64_VECTOR_TFLOPS,
                                   "flop_per_cell_instance": flop_inst, "flop_count_of_instance": list(flop_key) if flop_key in FLOP_PER_INSTANCE else None, "instances_per_cell": inst_per_cell,
                                   "note": "flops counted on the kernel's ISA (v_mul/v_add = 1, v_fma = 2); useful = one instance per cell, incl_halo = what the kernel executes"},
-                         "reaction": {"bound": "hbm", "achieved": (BYTES_PER_DOF_UPDATE + (8 if args.keep_du else 0)) * ns * npts / (phase["reaction"] / K_ * 1e-3) / 1e9,
+                         "reaction": {"bound": "hbm", "achieved": rate((BYTES_PER_DOF_UPDATE + (8 if args.keep_du else 0)) * ns * npts / 1e9, "reaction"),
                                       "peak": HBM_PEAK_GBS, "unit": "GB/s"},
-                         "source": {"bound": "hbm", "achieved": BYTES_PER_CELL_VECTOR * g.n_cells / (phase["source"] / K_ * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s"}},
+                         "source": {"bound": "hbm", "achieved": rate(BYTES_PER_CELL_VECTOR * g.n_cells / 1e9, "source"), "peak": HBM_PEAK_GBS, "unit": "GB/s"}},
         }
         rf = out["roofline"]
         rf["fp64_frac"], rf["fp64_frac_incl_halo"] = rf["fp64"]["frac"], rf["fp64"]["frac_incl_halo"]
         rf["nearest_roof"] = "fp64-valu" if rf["fp64_frac_incl_halo"] > rf["frac"] else "hbm"
         for k in ("reaction", "source"):
-            out["roofline"][k]["frac"] = out["roofline"][k]["achieved"] / HBM_PEAK_GBS
+            a_ = out["roofline"][k]["achieved"]
+            out["roofline"][k]["frac"] = None if a_ is None else a_ / HBM_PEAK_GBS
         if ref_rx is not None:
             out["reference_model_reaction"] = ref_rx
         if dist_cg is not None:
@@ -1072,15 +1130,16 @@ def main():
         # the plans this numbering got: patch statistics (halo re-integration) and whether the SpMV index compression applies
         if args.strategy == "patch":
             out["patch_stats"] = pr.K.pattern.patch_stats()
-        try:
-            import ctypes as _C
-            o2 = (_C.c_int64 * 2)()
-            tb._lib.check(tb.lib().tb_pattern_spmv_plan(pr.K.pattern.h, o2))
-            out["spmv_plan"] = {"row_signatures": int(o2[0]), "signature_entries": int(o2[1]), "nnz": int(sp.nnz),
-                                "form": "index-compressed (rows share column-offset signatures)" if o2[0] > 0 else "CSR fallback (the numbering shares no signatures)"}
-        except Exception as ex:
-            out["spmv_plan"] = {"error": str(ex)[:200]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:                              # (builds the SpMV plans: host work a plain run does not need)
+            try:
+                import ctypes as _C
+                o2 = (_C.c_int64 * 2)()
+                tb._lib.check(tb.lib().tb_pattern_spmv_plan(pr.K.pattern.h, o2))
+                out["spmv_plan"] = {"row_signatures": int(o2[0]), "signature_entries": int(o2[1]), "nnz": int(sp.nnz),
+                                    "form": "index-compressed (rows share column-offset signatures)" if o2[0] > 0 else "CSR fallback (the numbering shares no signatures)"}
+            except Exception as ex:
+                out["spmv_plan"] = {"error": str(ex)[:200]}
+        if world == 1 and args.full and not args.no_cpu_baseline:
             tag = "%dx%dx%d" % (n, n, nz_total) if args.mesh == "box" else "%s(%d cells)" % (args.mesh, g.n_cells)
             big = None if args.no_cpu_big else (g.xyz, g.conn, dh.cell_dofs, dh.ndofs, sp.rowptr, sp.colidx, tag)
 

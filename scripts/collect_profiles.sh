@@ -10,14 +10,14 @@ mkdir -p "$out"
 for mb in mfma_f64 mfma_f64_4x4 lds_atomic wg_launch mall_reuse sell_spmv partial_rows tail_atomics; do
   [ -f scripts/microbench/$mb.hip ] && hipcc --offload-arch=gfx950 -O3 -munsafe-fp-atomics scripts/microbench/$mb.hip -o scripts/microbench/$mb.bin 2>/dev/null
 done
-python3 bench.py > "$out/bench_216.json" 2> "$out/bench_216.err"
-rocprofv3 --kernel-trace --stats -d "$out/kt" -o kt -- python3 bench.py --no-cpu-baseline --no-slab-sweep > "$out/bench_under_rocprof.json" 2>/dev/null
+python3 bench.py --full > "$out/bench_216.json" 2> "$out/bench_216.err"
+rocprofv3 --kernel-trace --stats -d "$out/kt" -o kt -- python3 bench.py --full --no-cpu-baseline --no-slab-sweep > "$out/bench_under_rocprof.json" 2>/dev/null
 python3 scripts/rocpd_summary.py "$out/kt/kt_results.db" --json "$out/kernel_stats.json" > "$out/kernel_stats.txt"
 i=0
 for grp in "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_BUBBLE_sum" "WRITE_SIZE" "FETCH_SIZE" \
            "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT"; do
   i=$((i+1))
-  rocprofv3 --pmc $grp -d "$out/pmc$i" -o pmc -- python3 bench.py --no-cpu-baseline --no-slab-sweep --steps 5 > /dev/null 2>&1
+  rocprofv3 --pmc $grp -d "$out/pmc$i" -o pmc -- python3 bench.py --full --no-cpu-baseline --no-slab-sweep --steps 5 > /dev/null 2>&1
   python3 scripts/rocpd_summary.py "$out/pmc$i/pmc_results.db" --json "$out/pmc$i.json" > /dev/null
 done
 python3 scripts/make_traffic_json.py "$out" "$tag" > "$out/traffic.json"
@@ -40,7 +40,7 @@ if [ "$2" != "bench-only" ]; then
   # coupled electromechanics on the ideal LV (config 5 as two kernel rates)
   python3 scripts/bench_electromechanics.py > "$out/electromechanics_lv.json" 2>/dev/null
   # the 27-layer slab of the strong-scaling split, kernel trace
-  rocprofv3 --kernel-trace --stats -d "$out/kt27" -o kt27 -- python3 bench.py --no-cpu-baseline --layers 27 --steps 50 > /dev/null 2>&1
+  rocprofv3 --kernel-trace --stats -d "$out/kt27" -o kt27 -- python3 bench.py --full --no-cpu-baseline --layers 27 --steps 50 > /dev/null 2>&1
   python3 scripts/rocpd_summary.py "$out/kt27/kt27_results.db" --json "$out/slab27_kernel_stats.json" > "$out/slab27_kernel_stats.txt"
   # the CG product: CSR kernel against the sliced mirror, and the synthetic all-uniform-slices bound
   python3 scripts/bench_spmv.py > "$out/spmv_216.json" 2>/dev/null
@@ -51,8 +51,8 @@ if [ "$2" != "bench-only" ]; then
   rm -rf "$out/ktc"
   # round 5: unstructured presentations of the bench workload (random renumbering of the box; idealised ventricle), device-AD energies through the
   # split linearisation, RCCL cost at world size 1, HBM traffic and SQ counters of the split mechanics kernels
-  python3 bench.py --mesh shuffled > "$out/bench_shuffled.json" 2> "$out/bench_shuffled.err"
-  TB_PLAN_VERBOSE=1 python3 bench.py --mesh lv > "$out/bench_lv.json" 2> "$out/bench_lv.err"
+  python3 bench.py --full --mesh shuffled > "$out/bench_shuffled.json" 2> "$out/bench_shuffled.err"
+  TB_PLAN_VERBOSE=1 python3 bench.py --full --mesh lv > "$out/bench_lv.json" 2> "$out/bench_lv.err"
   for en in guccione humphrey linyin ho; do python3 scripts/bench_mechanics.py --n 40 --energy $en --cpu-n 2 2>/dev/null | tail -1; done > "$out/mechanics_energies_40.json"
   python3 scripts/rccl_latency.py 47089 2>/dev/null | grep "^{" > "$out/rccl_latency_world1.json"
   for grp in "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_BUBBLE_sum" "WRITE_SIZE"; do

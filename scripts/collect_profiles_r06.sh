@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 out=gpurun_out/$tag
 mkdir -p "$out"
 bash scripts/host_probe.sh > "$out/host_probe.txt" 2>&1
-python3 bench.py > "$out/bench_216.json" 2> "$out/bench_216.err"
+python3 bench.py --full > "$out/bench_216.json" 2> "$out/bench_216.err"
 rocprofv3 --kernel-trace --stats -d "$out/kt" -o kt -- python3 bench.py --no-cpu-baseline --no-slab-sweep --no-graph --no-dist-cg --trace-markers > "$out/bench_under_rocprof.json" 2>/dev/null
 python3 scripts/rocpd_summary.py "$out/kt/kt_results.db" --between scan --json "$out/kernel_stats.json" > "$out/kernel_stats.txt"
 python3 - "$out" <<'PY'
@@ -38,13 +38,13 @@ if [ "$2" != "bench-only" ]; then
   for st in atomic color; do python3 scripts/bench_mechanics.py --n 80 --strategy $st --cpu-n 2 2>/dev/null | tail -1; done > "$out/mechanics_80_q2_scattering_strategies.json"
   python3 scripts/bench_tets.py --n 100 > "$out/tets_100.json" 2>/dev/null
   python3 scripts/bench_q2_scalar.py --n 64 > "$out/q2_scalar_64.json" 2>/dev/null
-  python3 bench.py --mesh shuffled --no-slab-sweep > "$out/bench_shuffled.json" 2> "$out/bench_shuffled.err"
-  python3 bench.py --mesh shuffled --renumber dofs --no-slab-sweep > "$out/bench_shuffled_renumbered_dofs.json" 2> "$out/bench_shuffled_renumbered_dofs.err"
-  python3 bench.py --mesh lv --no-slab-sweep > "$out/bench_lv.json" 2> "$out/bench_lv.err"
+  python3 bench.py --full --mesh shuffled --no-slab-sweep > "$out/bench_shuffled.json" 2> "$out/bench_shuffled.err"
+  python3 bench.py --full --mesh shuffled --renumber dofs --no-slab-sweep > "$out/bench_shuffled_renumbered_dofs.json" 2> "$out/bench_shuffled_renumbered_dofs.err"
+  python3 bench.py --full --mesh lv --no-slab-sweep > "$out/bench_lv.json" 2> "$out/bench_lv.err"
   rocprofv3 --kernel-trace --stats -d "$out/kt27" -o kt27 -- python3 bench.py --no-cpu-baseline --layers 27 --steps 50 --no-graph --no-dist-cg --trace-markers > "$out/bench_slab27_under_rocprof.json" 2>/dev/null
   python3 scripts/rocpd_summary.py "$out/kt27/kt27_results.db" --between scan --json "$out/slab27_kernel_stats.json" > "$out/slab27_kernel_stats.txt"
   python3 scripts/rccl_latency.py 47089 2>/dev/null | grep "^{" > "$out/rccl_latency_world1.json"
-  TB_BENCH_SHARE_DEVICE=1 python3 bench.py --gpus 2 --mesh lv --no-cpu-baseline --no-slab-sweep --no-graph --checksums > "$out/bench_lv_two_ranks_one_device.json" 2> "$out/bench_lv_two_ranks_one_device.err"
+  TB_BENCH_SHARE_DEVICE=1 python3 bench.py --full --gpus 2 --mesh lv --no-cpu-baseline --no-slab-sweep --no-graph --checksums > "$out/bench_lv_two_ranks_one_device.json" 2> "$out/bench_lv_two_ranks_one_device.err"
 fi
 rm -rf "$out"/kt27 "$out"/kt "$out"/pmc1 "$out"/pmc2 "$out"/pmc3 "$out"/pmc4
 tail -c 900 "$out/bench_216.json"; head -6 "$out/kernel_stats.txt"; head -30 "$out/traffic.json"

@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 for rep in 1 2; do
   for envs in "$@"; do
     echo "== $envs"
-    env $envs timeout 600 python3 bench.py --no-cpu-baseline --no-slab-sweep --steps 20 2>/dev/null | python3 -c "
+    env $envs timeout 600 python3 bench.py --full --no-cpu-baseline --no-slab-sweep --steps 20 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('  ms/step %.3f' % d['ms_per_step'], d['phase_ms'], 'cg', round(d['distributed_cg']['iteration_ms'],4), round(d['distributed_cg']['local_spmv_ms'],4))"
   done
 done

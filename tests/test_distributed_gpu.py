@@ -209,7 +209,7 @@ def test_bench_two_ranks_end_to_end_on_one_device():
     import json
     import subprocess
     env = dict(os.environ, TB_BENCH_SHARE_DEVICE="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--n", "24", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--n", "24", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -227,12 +227,39 @@ def test_bench_two_ranks_end_to_end_on_one_device():
     assert abs(d["value"] - 3 * 24 ** 3 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
 
 
+def test_bench_plain_two_rank_line_is_strict_json():
+    """The default multi-GPU line (no --full, as a scaling run invokes it), two ranks on cuda:0 over gloo: the timed steps record the two events around
+    the matrix pass only, so source / halo / reaction and the rates and roofline figures derived from them are null — never NaN: the line is strict
+    JSON and the last thing on stdout; the matrix phase and the headline keys are numbers."""
+    import json
+    import subprocess
+    env = dict(os.environ, TB_BENCH_SHARE_DEVICE="1")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--n", "24", "--steps", "2", "--warmup", "1"],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    assert "NaN" not in lines[0] and "Infinity" not in lines[0]
+    assert [ln for ln in r.stdout.splitlines() if ln.strip()][-1] == lines[0]
+
+    def no_constant(c):
+        raise AssertionError("non-strict JSON constant %s" % c)
+    d = json.loads(lines[0], parse_constant=no_constant)
+    assert d["n_gpus"] == 2 and d["steps"] == 2 and d["config"]["full"] is False and d["ms_per_step"] > 0
+    assert abs(d["value"] - 3 * 24 ** 3 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert d["phase_ms"]["mass+diffusion"] > 0 and all(d["phase_ms"][k] is None for k in ("source", "halo", "reaction"))
+    assert d["phase_rates"]["matrix_integrations_per_s"] > 0
+    assert d["phase_rates"]["source_cells_per_s"] is None and d["phase_rates"]["reaction_dof_updates_per_s"] is None
+    assert d["roofline"]["frac"] > 0 and d["roofline"]["reaction"]["frac"] is None and d["roofline"]["source"]["achieved"] is None
+    assert "distributed_cg" not in d and "phase_ms_note" in d
+
+
 def test_bench_two_ranks_weak_mode_still_available():
     import json
     import subprocess
     env = dict(os.environ, TB_BENCH_SHARE_DEVICE="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scaling", "weak", "--n", "16", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
-                        "--no-dist-cg"], env=env, capture_output=True, text=True, timeout=600)
+                        "--no-dist-cg", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert d["scaling"] == "weak" and d["config"]["cells_per_gpu"] == 16 ** 3 and d["config"]["cells_total"] == 2 * 16 ** 3
@@ -254,7 +281,7 @@ def test_bench_unstructured_meshes_under_the_bisection_partition_match_one_rank(
     coordinate bisection (tb.distributed.partition_cells_rcb / GeneralPartition: every part exchanges with every part it shares nodes with).  Two
     ranks on cuda:0 over gloo (TB_BENCH_SHARE_DEVICE) must leave behind what one rank leaves: --checksums prints partition-independent sums of
     M, K, b and the ionic states after two steps from the same initial state — equal to 1e-10 relative."""
-    common = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-graph", "--no-slab-sweep", "--checksums", "--preroll-ms", "0"] + mesh_args
+    common = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-graph", "--no-slab-sweep", "--checksums", "--preroll-ms", "0", "--full"] + mesh_args
     one = _bench_line(["--gpus", "1"] + common)
     two = _bench_line(["--gpus", "2"] + common, env={"TB_BENCH_SHARE_DEVICE": "1"})
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2 and two["config"]["backend"].startswith("gloo")
@@ -270,7 +297,7 @@ def test_bench_three_slabs_merged_pack_and_unpack_equal_one_call_per_neighbour()
     both send buffers with ONE tb_gather_indexed and adds both receive buffers with ONE tb_scatter_add_indexed (slices of one allocation each).  The run
     leaves the sums of the run that makes one call per neighbour (1e-13) (TB_HALO_SEPARATE_CALLS): the same two numbers are added on every shared dof.
     (The comparison with one rank is the next test.)"""
-    common = ["--gpus", "3", "--n", "24", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-graph", "--no-slab-sweep", "--no-dist-cg", "--checksums", "--preroll-ms", "0"]
+    common = ["--gpus", "3", "--n", "24", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-graph", "--no-slab-sweep", "--no-dist-cg", "--checksums", "--preroll-ms", "0", "--full"]
     merged = _bench_line(common, env={"TB_BENCH_SHARE_DEVICE": "1"})
     separate = _bench_line(common, env={"TB_BENCH_SHARE_DEVICE": "1", "TB_HALO_SEPARATE_CALLS": "1"})
     assert merged["n_gpus"] == 3 and merged["config"]["layers_per_gpu"] == 8 and merged["phase_ms"]["halo"] > 0.0
@@ -282,7 +309,7 @@ def test_bench_three_slabs_of_the_box_leave_the_one_rank_sums():
     """BASELINE configs[2] at N > 1 is the SAME box in N z-slabs: every rank displaces its nodes by the whole box's perturbation (global layer index), so
     the union of the slabs is the one-rank mesh, the initial state is a function of position, and ψᵀMψ, ψᵀKψ, Σ w b², Σ w bψ (b summed over the
     interfaces by the step's own exchange), Σ w u², Σ w φψ after two steps equal the one-rank run's to 1e-10 (P-GPU result == 1-GPU result)."""
-    common = ["--n", "24", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-graph", "--no-slab-sweep", "--no-dist-cg", "--checksums", "--preroll-ms", "0"]
+    common = ["--n", "24", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-graph", "--no-slab-sweep", "--no-dist-cg", "--checksums", "--preroll-ms", "0", "--full"]
     one = _bench_line(["--gpus", "1"] + common)
     three = _bench_line(["--gpus", "3"] + common, env={"TB_BENCH_SHARE_DEVICE": "1"})
     assert three["n_gpus"] == 3 and three["config"]["layers_per_gpu"] == 8 and three["phase_ms"]["halo"] > 0.0
@@ -322,3 +349,68 @@ def test_bench_phase_event_modes_on_one_rank(mode):
     assert d["value"] > 0 and d["host_enqueue_ms_per_step"] > 0
     assert (ph["mass+diffusion"] > 0) == (mode != "none")
     assert (ph["reaction"] > 0) == (mode == "all") and (ph["source"] > 0) == (mode == "all")
+
+
+def test_bench_plain_run_is_lean_and_dumps_what_its_last_timed_step_computed(tmp_path):
+    """A plain run (no --full) prints the headline line without the extra measurements, and --dump-outputs writes the arrays of its last timed step:
+    the whole arrays at this size, float64.  Two runs with the same steps leave the same arrays (the ionic states bit for bit; M, K and b to the
+    last bits that LDS and global atomics order run by run), also when one of them runs no pre-roll at all: the states are reset after the
+    pre-roll, whose step count depends on timing.  One more timed step moves the ionic states and leaves M and K."""
+    common = ["--gpus", "1", "--n", "24", "--warmup", "1"]
+    runs = {}
+    for tag, extra in (("a", ["--steps", "2"]), ("b", ["--steps", "2", "--preroll-ms", "0"]), ("c", ["--steps", "3"])):
+        runs[tag] = _bench_line(common + extra + ["--dump-outputs", str(tmp_path / tag)])
+    d = runs["a"]
+    assert d["steps"] == 2 and runs["c"]["steps"] == 3 and d["ms_per_step"] > 0 and d["config"]["full"] is False
+    assert d["unit"] == "element-integrations/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert abs(d["value"] - 3 * 24 ** 3 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    for k in ("cpu_baseline", "distributed_cg", "cg_iterations_per_s", "slab_sweep", "graph_step", "reference_model_reaction", "spmv_plan"):
+        assert k not in d, k
+    sizes = {"M_nzval": d["config"]["nnz_per_gpu"], "K_nzval": d["config"]["nnz_per_gpu"], "b": d["config"]["dofs_per_gpu"],
+             "u": d["config"]["ionic_states"] * d["config"]["dofs_per_gpu"]}
+    out = {tag: {k: np.load(str(tmp_path / tag / (k + ".npy"))) for k in sizes} for tag in runs}
+    for k, n in sizes.items():
+        a = out["a"][k]
+        assert a.dtype == np.float64 and a.shape == (n,) and np.isfinite(a).all() and np.abs(a).max() > 0, k
+        assert np.abs(out["b"][k] - a).max() <= 1e-12 * np.abs(a).max(), k
+    np.testing.assert_array_equal(out["b"]["u"], out["a"]["u"])
+    assert not np.array_equal(out["c"]["u"], out["a"]["u"])
+    for k in ("M_nzval", "K_nzval"):
+        assert np.abs(out["c"][k] - out["a"][k]).max() <= 1e-12 * np.abs(out["a"][k]).max(), k
+
+
+def _dump_constants():
+    """(DUMP_SAMPLE, DUMP_SEED) of bench.py, imported in a child process (importing bench.py sets OpenMP binding variables for its own process)"""
+    import subprocess
+    r = subprocess.run([sys.executable, "-c", "import bench; print(bench.DUMP_SAMPLE, bench.DUMP_SEED)"], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return tuple(int(v) for v in r.stdout.split())
+
+
+def test_bench_dump_samples_long_arrays_at_seeded_positions(tb, device, tmp_path):
+    """--dump-outputs on a mesh whose M, K and u are longer than DUMP_SAMPLE: the dumped entries are those at the seeded positions (np.unique of
+    DUMP_SAMPLE draws, Int32 gather on the device) — checked against M and K assembled here on the bench's own mesh, and the whole b against the
+    source vector at the time of the last timed step (t = 0.01 (W + K - 1))."""
+    n, warmup, steps = 48, 1, 2
+    d = _bench_line(["--gpus", "1", "--n", str(n), "--steps", str(steps), "--warmup", str(warmup), "--preroll-ms", "0", "--dump-outputs", str(tmp_path)])
+    sample, seed = _dump_constants()
+    nnz, ndofs, ns = d["config"]["nnz_per_gpu"], d["config"]["dofs_per_gpu"], d["config"]["ionic_states"]
+    assert nnz > sample and ns * ndofs > sample and ndofs <= sample
+    g = tb.generate_mesh(tb.Hexahedron, (n, n, n), (0.0, 0.0, 0.0), (1.0, 1.0, 1.0), perturb=0.2)
+    dh = tb.DofHandler(g)
+    sp = tb.allocate_matrix(dh)
+    assert sp.nnz == nnz and dh.ndofs == ndofs
+    st = tb.PatchAssemblyStrategy(device)
+    D = tb.ConductivityToDiffusivityCoefficient(tb.ConstantCoefficient(np.diag([4.5e-5, 2.0e-5, 2.0e-5])), tb.ConstantCoefficient(1.0), tb.ConstantCoefficient(1.0))
+    M = tb.setup_operator(st, tb.BilinearMassIntegrator(tb.ConstantCoefficient(1.0)), dh, sp)
+    K = tb.setup_operator(st, tb.BilinearDiffusionIntegrator(D), dh, sp)
+    tb.update_operators(M, K, 0.0)
+    src = tb.update_operator(tb.setup_operator(tb.AtomicAssemblyStrategy(device), tb.LinearIntegrator(tb.AnalyticalCoefficient("cos_exp")), dh),
+                             0.01 * (warmup + steps - 1))
+    for k, (name, full) in enumerate((("M_nzval", M.A.to_host()), ("K_nzval", K.A.to_host()), ("b", src.b.to_host()), ("u", None))):
+        got = np.load(str(tmp_path / (name + ".npy")))
+        length = {"M_nzval": nnz, "K_nzval": nnz, "b": ndofs, "u": ns * ndofs}[name]
+        idx = np.arange(length) if length <= sample else np.unique(np.random.default_rng([seed, k]).integers(0, length, sample))
+        assert got.dtype == np.float64 and got.shape == idx.shape, name
+        if full is not None:
+            assert np.abs(got - full[idx]).max() <= 1e-12 * np.abs(full).max(), name

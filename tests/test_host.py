@@ -254,3 +254,15 @@ def test_locality_permutation_on_tetrahedra_and_bad_arguments(tb):
     rc = tb.lib().tb_host_locality_permutation(99, gt.n_nodes, gt.xyz.ctypes.data_as(L.c_dp), gt.n_cells, gt.conn.ctypes.data_as(L.c_i32p), 0, None, 0, 0,
                                                cp.ctypes.data_as(L.c_i32p), None, None)
     assert rc == L.TB_ERR_BAD_ARG and b"geom_kind" in tb.lib().tb_last_error_string()
+
+
+def test_bench_options_for_the_full_run_and_the_output_dump():
+    """bench.py --help (parsed before anything touches the GPU) lists --full and --dump-outputs; the dump of a 216^3 run stays below 64 MB"""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = subprocess.run([sys.executable, "-c", "import bench; print(bench.DUMP_SAMPLE)"], cwd=root, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]                # (a child process: importing bench.py sets OpenMP binding variables for its own process)
+    assert 4 * 8 * int(r.stdout) < 64e6                      # four float64 arrays of at most DUMP_SAMPLE entries each

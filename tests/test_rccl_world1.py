@@ -59,7 +59,7 @@ def test_rccl_behind_the_c_abi_world_size_one():
 def test_bench_under_launcher_initialises_rccl_at_world_size_one(exchange, backend):
     """bench.py under the launcher at world size 1: process group, barrier, max-reduced timings; with --exchange abi the communicator of the C ABI is created
     from the id that torch.distributed broadcasts, and the CG reductions / halo exchange go through tb_comm_*."""
-    r = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--n", "24", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-slab-sweep", "--exchange", exchange])
+    r = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--n", "24", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-slab-sweep", "--full", "--exchange", exchange])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-3000:], r.stderr[-3000:])
     d = json.loads(lines[0])
@@ -71,12 +71,12 @@ def test_bench_under_launcher_initialises_rccl_at_world_size_one(exchange, backe
 def test_bench_exchange_auto_falls_back_to_torch_distributed_when_no_rank_can_create_the_communicator():
     """--exchange auto: a rank that cannot create the C ABI's communicator votes 0, the minimum over the ranks decides, torch.distributed carries the data"""
     env = dict(os.environ, TB_BENCH_NO_ABI_COMM="1")
-    r = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--n", "24", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-slab-sweep"], env=env)
+    r = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--n", "24", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-slab-sweep", "--full"], env=env)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-3000:], r.stderr[-3000:])
     d = json.loads(lines[0])
     assert d["config"]["backend"] == "nccl (RCCL)" and "torch.distributed carries the exchange" in r.stderr
-    r = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--n", "24", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-slab-sweep", "--exchange", "abi"], env=env)
+    r = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--n", "24", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-slab-sweep", "--full", "--exchange", "abi"], env=env)
     assert r.returncode != 0 and "could not be created on every rank" in r.stderr
 
 
@@ -94,7 +94,7 @@ def test_three_ranks_through_the_c_abi_communicator_over_the_test_double(tmp_pat
     b = subprocess.run([hipcc, "-O1", "-shared", "-fPIC", "-I/opt/rocm/include", "-o", so, os.path.join(ROOT, "tests", "mock_rccl", "mock_rccl.cpp"), "-lrt"],
                        capture_output=True, text=True, timeout=600)
     assert b.returncode == 0, b.stderr[-2000:]
-    common = mesh_args + ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-graph", "--no-slab-sweep", "--checksums", "--preroll-ms", "0"]
+    common = mesh_args + ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-graph", "--no-slab-sweep", "--checksums", "--preroll-ms", "0", "--full"]
 
     def line(extra, env):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra + common, env=dict(os.environ, **env), capture_output=True, text=True, timeout=900)
