@@ -163,9 +163,10 @@ const char *tb_version(void);
  * binding written against revision n may call anything revision n declares, so a library of revision < n must be refused up front rather than at
  * the first missing symbol).  4: tb_cgd_update writes three doubles (d_out3; revisions ≤ 3 wrote two).  5: tb_graph_*, tb_comm_exchange_begin / _end,
  * tb_cgd_iteration, tb_last_kernel_name.  6: tb_host_locality_permutation; calls that wait for the device refuse inside an open capture
- * (TB_ERR_BAD_ARG) instead of invalidating it.  A host binding compares tb_abi_revision() with the
+ * (TB_ERR_BAD_ARG) instead of invalidating it.  7: tb_cg1_update / tb_cg1_fold / tb_cg1_iteration (single-reduction CG, seven-double scalar block).
+ * A host binding compares tb_abi_revision() with the
  * TB_ABI_REVISION it was written against and refuses to run on a mismatch (julia/ThunderboltHIPBackend.jl does, in __init__) */
-#define TB_ABI_REVISION 6
+#define TB_ABI_REVISION 7
 int tb_abi_revision(void);
 
 /* ------------------------------------------------------------------ device (AbstractGPUDevice, src/devices.jl:3-4;
@@ -478,6 +479,28 @@ int tb_cgd_rotate(tb_device *dev, double *d_S);
  * → tb_cgd_direction → tb_cgd_rotate on the six-double scalar block d_S, issued from ONE call (round 5: the per-call cost of an interpreted host is a
  * third of a thin slab's iteration).  Same kernels and results as the four calls. */
 int tb_cgd_iteration(tb_pattern *pat, const double *d_nzval, const double *d_dinv, double *d_x, double *d_r, double *d_p, double *d_Ap, double *d_S);
+/* Single-reduction form of the same Jacobi-CG (Chronopoulos–Gear): ONE all-reduce per iteration instead of two.  The vectors are x, r, u = D⁻¹r,
+ * w = A·u (assembled), p and s = A·p, kept by the recurrence s = w + β s instead of a second product.  Scalar block S (SEVEN doubles):
+ *   S[0] γ = Σ wt·r·u   S[1] δ = uᵀA u   S[2] ρ = Σ wt·r·r   — the contiguous block the caller all-reduces (3 doubles)
+ *   S[3] breakdown flag (sticky, as in tb_cgd_update; the host reads S[2], S[3])   S[4] γ of the previous iteration (0: first iteration)
+ *   S[5] α of the previous iteration   S[6] δ accumulator (the target of tb_spmv_csr_dot; zero between iterations)
+ * Set-up (the caller; tb_cgd_dot and tb_spmv_csr_dot): r = b − A x, u = D⁻¹ r, w = A u, S = {γ₀, δ₀, ρ₀, 0, 0, 0, 0}, all-reduce S[0:3].  Iteration:
+ *   tb_cg1_update    β = γ/γ_prev (0 at the first), α = γ / (δ − β γ/α_prev);  p = u + β p;  s = w + β s;  x += α p;  r −= α s;  u = D⁻¹ r;
+ *                    partials of Σ wt·r·u and Σ wt·r·r left in the device's reduction slots (d_wt NULL: weights 1).  δ − β γ/α_prev is pᵀAp: when it
+ *                    is ≤ 0 with γ ≠ 0, S[3] is set to it (α = 0) exactly as tb_cgd_update sets its flag
+ *   product          w = A u assembled over the interface; its local uᵀA_p u into S[6] (tb_spmv_csr_dot; u is consistent, no halo needed)
+ *   tb_cg1_fold      α_prev ← α, γ_prev ← γ; S[0:3] ← {Σ wt·r·u, the δ partial, Σ wt·r·r} of this rank; S[6] and the slots back to zero
+ *   all-reduce       S[0:3] over the ranks (the caller)
+ * Between tb_cg1_update and tb_cg1_fold the slots of the update are held: the product may use tb_spmv_csr*, tb_cgd_dot and the halo entries, not
+ * tb_cgd_update / tb_cgd_iteration.  n == 0 is legal.  All three are enqueue-only (capturable). */
+int tb_cg1_update(tb_device *dev, int64_t n, const double *d_wt, const double *d_dinv, const double *d_w, double *d_p, double *d_s, double *d_x, double *d_r,
+                  double *d_u, double *d_S);
+int tb_cg1_fold(tb_device *dev, double *d_S);
+/* One whole single-reduction iteration of a sub-domain without shared dofs: tb_cg1_update (weights = 1) → w = A·u with uᵀAu → tb_cg1_fold from ONE
+ * call, three launches (tb_cgd_iteration: four).  The same kernels as the three separate calls: bitwise the same results wherever the slot sums are
+ * order-fixed (no launch above 64 workgroups); above that the order of the slot atomics varies from run to run of either form. */
+int tb_cg1_iteration(tb_pattern *pat, const double *d_nzval, const double *d_dinv, double *d_x, double *d_r, double *d_u, double *d_p, double *d_s, double *d_w,
+                     double *d_S);
 /* Halo pack / unpack of the multi-GPU path — new work: the reference is shared-memory only (README.md:7); what these stand in for on one device
  * is the plain indexing of device vectors its GPU extension relies on (ext/CuThunderboltExt.jl:126-170).  Sub-domain vectors hold the dofs
  * shared with a neighbouring rank at the positions d_idx (0-based Int32, distinct within one call; both sides list the shared dofs in the same

@@ -19,7 +19,7 @@ import Thunderbolt: AbstractGPUDevice, AbstractAssemblyStrategy, AbstractSolver,
 const libtbhip = get(ENV, "TBHIP_LIBRARY", "libtbhip.so")
 
 # revision of include/tbhip.h these ccalls were written against (TB_ABI_REVISION); a library of another revision reads / writes other buffer sizes
-const TB_ABI_REVISION = 6
+const TB_ABI_REVISION = 7
 const TB_ERR_UNSUPPORTED = Cint(-5) # include/tbhip.h
 function __init__()
     have = ccall((:tb_abi_revision, libtbhip), Cint, ())
@@ -593,6 +593,21 @@ function cgd_iteration!(A::HIPSparseMatrixCSR, dinv::HIPVector{Float64}, x::HIPV
 end
 function cgd_rotate!(S::HIPVector{Float64})
     check(ccall((:tb_cgd_rotate, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}), S.dev.handle, S.ptr))
+end
+
+# single-reduction (Chronopoulos–Gear) form: S = (γ, δ, ρ, flag, γ_prev, α_prev, δ accumulator) — seven doubles, include/tbhip.h.  Per iteration:
+# cg1_update! → w = A·u assembled, with mul_dot!(w, A, u, S) at offset 6 (the δ accumulator) → cg1_fold! → ONE allreduce_sum!(c, S, 0, 3); the host
+# reads S[3:4] (ρ = ‖r‖², flag) once per look.  cg1_iteration!: the same three launches from one call for a rank without shared dofs.
+function cg1_update!(S::HIPVector{Float64}, wt::HIPVector{Float64}, dinv::HIPVector{Float64}, w::HIPVector{Float64}, p::HIPVector{Float64}, s::HIPVector{Float64},
+                     x::HIPVector{Float64}, r::HIPVector{Float64}, u::HIPVector{Float64})
+    check(ccall((:tb_cg1_update, libtbhip), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        x.dev.handle, x.n, wt.ptr, dinv.ptr, w.ptr, p.ptr, s.ptr, x.ptr, r.ptr, u.ptr, S.ptr))
+end
+cg1_fold!(S::HIPVector{Float64}) = check(ccall((:tb_cg1_fold, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}), S.dev.handle, S.ptr))
+function cg1_iteration!(A::HIPSparseMatrixCSR, dinv::HIPVector{Float64}, x::HIPVector{Float64}, r::HIPVector{Float64}, u::HIPVector{Float64}, p::HIPVector{Float64},
+                        s::HIPVector{Float64}, w::HIPVector{Float64}, S::HIPVector{Float64})
+    check(ccall((:tb_cg1_iteration, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        A.ddh.pattern, A.nzval.ptr, dinv.ptr, x.ptr, r.ptr, u.ptr, p.ptr, s.ptr, w.ptr, S.ptr))
 end
 
 # ---------------------------------------------------------------- round 6: the rest of the boundary the hot path's rows of SURVEY §8 use, bound the same way

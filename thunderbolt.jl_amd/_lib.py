@@ -164,6 +164,9 @@ SIGNATURES = {
     "tb_comm_allreduce": (C.c_int, [vp, vp, C.c_int64, C.c_int]),
     "tb_comm_exchange_begin": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
     "tb_cgd_iteration": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "tb_cg1_update": (C.c_int, [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "tb_cg1_fold": (C.c_int, [vp, vp]),
+    "tb_cg1_iteration": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "tb_graph_begin": (C.c_int, [vp]),
     "tb_graph_end": (C.c_int, [vp, C.POINTER(vp)]),
     "tb_graph_launch": (C.c_int, [vp, C.c_double]),
@@ -206,7 +209,7 @@ def build_library(force=False):
 _lib = None
 
 
-TB_ABI_REVISION = 6   # include/tbhip.h: TB_ABI_REVISION
+TB_ABI_REVISION = 7   # include/tbhip.h: TB_ABI_REVISION
 
 
 def lib():

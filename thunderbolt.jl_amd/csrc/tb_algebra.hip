@@ -2104,6 +2104,90 @@ int launch_cgd_iteration(tb_pattern *pat, const double *A, const double *dinv, d
     return TB_OK;
 }
 
+// ---- single-reduction (Chronopoulos–Gear) form of the same Jacobi-CG: one all-reduce of {γ, δ, ρ} per iteration ----
+// Scalar block S (SEVEN doubles, include/tbhip.h): γ | δ | ρ | flag | γ_prev | α_prev | δ accumulator.  S[0:3] is the block the caller all-reduces;
+// γ_prev = 0 marks the first iteration (β = 0, α = γ/δ).  The recurrence s = A·p replaces the product A·p: the only product is w = A·u.
+// α and β from the scalar block, the same expression in the update kernel (every workgroup: the same bits) and in the fold (which keeps α for the
+// next iteration).  den = δ − β·γ/α_prev is pᵀAp of this iteration.
+__device__ __forceinline__ void cg1_scalars(const double *__restrict__ S, double &alpha, double &beta, double &den)
+{
+    const double gam = S[0], gp = S[4];
+    beta = gp != 0.0 ? gam / gp : 0.0;
+    den = beta != 0.0 ? S[1] - beta * gam / S[5] : S[1];
+    alpha = den > 0.0 ? gam / den : 0.0;
+}
+
+// p = u + β p, s = w + β s, x += α p, r −= α s, u = D⁻¹ r;  γ-partials Σ wt·r·u → group g_gam, ρ-partials Σ wt·r·r → group g_rho
+__global__ void __launch_bounds__(256)
+k_cg1_update(int64_t n, const double *__restrict__ wt, const double *__restrict__ dinv, const double *__restrict__ w, double *__restrict__ p,
+             double *__restrict__ s, double *__restrict__ x, double *__restrict__ r, double *__restrict__ u, double *__restrict__ S,
+             double *__restrict__ g_gam, double *__restrict__ g_rho)
+{
+    double alpha, beta, den;
+    cg1_scalars(S, alpha, beta, den);
+    // pᵀAp ≤ 0 while γ ≠ 0: not positive definite (or broken down) — the sticky flag of tb_cgd_update, in S[3]; the step is then empty in x and r
+    if (!(den > 0.0) && S[0] != 0.0 && blockIdx.x == 0 && threadIdx.x == 0) S[3] = den == 0.0 ? -1e-300 : den;
+    double a = 0.0, c = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const double pi = u[i] + beta * p[i];
+        const double si = w[i] + beta * s[i];
+        p[i] = pi; s[i] = si;
+        x[i] += alpha * pi;
+        const double ri = r[i] - alpha * si;
+        r[i] = ri;
+        const double ui = dinv ? dinv[i] * ri : ri;
+        u[i] = ui;
+        const double wi = wt ? wt[i] : 1.0;
+        a += wi * ri * ui;
+        c += wi * ri * ri;
+    }
+    block_sum2_slots(a, c, g_gam, g_rho);
+}
+
+// one wave: α of the iteration just updated is kept (α_prev ← α, γ_prev ← γ), then S[0:3] ← {Σ group g_gam, Σ group g_del + S[6], Σ group g_rho};
+// S[6] and the three groups back to zero.  The δ partial arrives either in group g_del (the one-call form) or in S[6] (tb_spmv_csr_dot folds into a
+// caller scalar); adding the other, zero, term is exact, so both forms leave the same sum.
+__global__ void __launch_bounds__(64) k_cg1_fold(double *__restrict__ S, double *__restrict__ g_del, double *__restrict__ g_gam, double *__restrict__ g_rho)
+{
+    const double gam = read_slots(g_gam), del = read_slots(g_del), rho = read_slots(g_rho);
+    const int l = RED_STRIDE * threadIdx.x;
+    g_del[l] = 0.0; g_gam[l] = 0.0; g_rho[l] = 0.0;
+    if (threadIdx.x == 0) {
+        double alpha, beta, den;
+        cg1_scalars(S, alpha, beta, den);
+        S[4] = S[0]; S[5] = alpha;
+        S[0] = gam; S[1] = del + S[6]; S[2] = rho; S[6] = 0.0;
+    }
+}
+
+int launch_cg1_update(tb_device *dev, int64_t n, const double *wt, const double *dinv, const double *w, double *p, double *s, double *x, double *r,
+                      double *u, double *d_S)
+{
+    // launched for n == 0 too (one workgroup, no elements): the breakdown test reads only the all-reduced scalars, so an empty part raises its flag
+    // in the same iteration as its peers
+    const unsigned g = n > 0 ? grid_for(dev, n, 256) : 1u;
+    hipLaunchKernelGGL(k_cg1_update, dim3(g), dim3(256), 0, dev->stream, n, wt, dinv, w, p, s, x, r, u, d_S, red_group(dev, 1), red_group(dev, 2));
+    TB_HIP(hipGetLastError());
+    return TB_OK;
+}
+int launch_cg1_fold(tb_device *dev, double *d_S)
+{
+    hipLaunchKernelGGL(k_cg1_fold, dim3(1), dim3(64), 0, dev->stream, d_S, red_group(dev, 0), red_group(dev, 1), red_group(dev, 2));
+    TB_HIP(hipGetLastError());
+    return TB_OK;
+}
+// One iteration on a sub-domain without shared dofs: update (weights = 1) → w = A·u with the partial of uᵀAu left in slot group 0 → fold.  Three launches.
+int launch_cg1_iteration(tb_pattern *pat, const double *A, const double *dinv, double *x, double *r, double *u, double *p, double *s, double *w, double *d_S)
+{
+    tb_device *dev = pat->mesh->dev;
+    const int64_t n = pat->n_rows;
+    int rc = launch_cg1_update(dev, n, nullptr, dinv, w, p, s, x, r, u, d_S);
+    if (rc) return rc;
+    if (n > 0 && (rc = launch_spmv_dot_slots(pat, A, u, w, red_group(dev, 0)))) return rc;
+    return launch_cg1_fold(dev, d_S);
+}
+
 // ---- halo pack / unpack and the packed interface rows of a product (multi-GPU path) ----
 __global__ void __launch_bounds__(256) k_gather_indexed(int64_t n, const double *__restrict__ vec, const int32_t *__restrict__ idx, double *__restrict__ out)
 {

@@ -1222,6 +1222,31 @@ int tb_cgd_iteration(tb_pattern *pat, const double *d_nzval, const double *d_din
     return launch_cgd_iteration(pat, d_nzval, d_dinv, d_x, d_r, d_p, d_Ap, d_S);
 }
 
+// Single-reduction (Chronopoulos–Gear) form of the sub-structured Jacobi-CG: the scalar block is SEVEN doubles (include/tbhip.h)
+int tb_cg1_update(tb_device *dev, int64_t n, const double *d_wt, const double *d_dinv, const double *d_w, double *d_p, double *d_s, double *d_x, double *d_r,
+                  double *d_u, double *d_S)
+{
+    TB_REQUIRE(dev && d_S && n >= 0 && ((d_w && d_p && d_s && d_x && d_r && d_u) || n == 0), "tb_cg1_update: bad argument");
+    TB_HIP(hipSetDevice(dev->id));
+    return launch_cg1_update(dev, n, d_wt, d_dinv, d_w, d_p, d_s, d_x, d_r, d_u, d_S);
+}
+
+int tb_cg1_fold(tb_device *dev, double *d_S)
+{
+    TB_REQUIRE(dev && d_S, "tb_cg1_fold: NULL argument");
+    TB_HIP(hipSetDevice(dev->id));
+    return launch_cg1_fold(dev, d_S);
+}
+
+// tb_cg1_update (weights = 1) → tb_spmv_csr_dot → tb_cg1_fold from one call, the δ partial kept in a slot group between the last two: three launches
+int tb_cg1_iteration(tb_pattern *pat, const double *d_nzval, const double *d_dinv, double *d_x, double *d_r, double *d_u, double *d_p, double *d_s, double *d_w,
+                     double *d_S)
+{
+    TB_REQUIRE(pat && d_nzval && d_dinv && d_x && d_r && d_u && d_p && d_s && d_w && d_S, "tb_cg1_iteration: NULL argument");
+    TB_HIP(hipSetDevice(pat->mesh->dev->id));
+    return launch_cg1_iteration(pat, d_nzval, d_dinv, d_x, d_r, d_u, d_p, d_s, d_w, d_S);
+}
+
 int tb_extract_diagonal(tb_pattern *pat, const double *d_nzval, double *d_diag)
 {
     TB_REQUIRE(pat && ((d_nzval && d_diag) || pat->n_rows == 0), "tb_extract_diagonal: NULL argument");

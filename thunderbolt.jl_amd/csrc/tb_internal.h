@@ -405,6 +405,10 @@ int launch_scatter_add_indexed(tb_device *dev, int64_t n, const double *in, cons
 int read_status_public(tb_device *dev); // status block → host, synchronises the stream (what check_status does when the status is not deferred)
 int launch_cgd_rotate(tb_device *dev, double *d_S);
 int launch_cgd_iteration(tb_pattern *pat, const double *A, const double *dinv, double *x, double *r, double *p, double *Ap, double *d_S);
+int launch_cg1_update(tb_device *dev, int64_t n, const double *wt, const double *dinv, const double *w, double *p, double *s, double *x, double *r,
+                      double *u, double *d_S);
+int launch_cg1_fold(tb_device *dev, double *d_S);
+int launch_cg1_iteration(tb_pattern *pat, const double *A, const double *dinv, double *x, double *r, double *u, double *p, double *s, double *w, double *d_S);
 int spmv_plans(tb_pattern *p); // builds the plans tb_spmv_csr would build on its first product
 int launch_scatter_indexed(tb_device *dev, int64_t n, const double *in, const int32_t *idx, double *vec);
 int launch_spmv_rows(tb_pattern *p, const double *nz, const double *x, int64_t n, const int32_t *rows, double *out);

@@ -393,11 +393,21 @@ class DistributedCG:
         without it `local_spmv` is called and its result packed afterwards (no overlap).
       * device=None: plain torch ops on whatever device the tensors live on (CPU in the gloo tests, where the oracle assembles).
 
+    variant="classic" (default): two scalar all-reduces per iteration, pᵀAp and then {r·z, ‖r‖²}.  variant="single_reduction": the
+    Chronopoulos–Gear form — the vectors x, r, u = D⁻¹r, w = A·u, p and s = A·p (by recurrence), and ONE all-reduce of {γ = r·u, δ = uᵀAu, ρ = ‖r‖²}
+    per iteration; α = γ / (δ − β γ / α_prev) is the same pᵀAp in exact arithmetic, so both forms take the same iterations up to rounding.  Device
+    path: tb_cg1_update → product (ordered for overlap as above) → tb_cg1_fold → all-reduce of the three doubles; tb_cg1_iteration from one call at
+    one rank without shared dofs.  `reductions_per_iteration` says which.
+
     The device's kernels and torch's work (all-reduces, the staging copies under gloo) must share one stream: the constructor puts the device
     on torch's current stream and `solve` refuses to run if that has changed."""
 
-    def __init__(self, local_spmv, local_diag, lower_idx, upper_idx, rank, world_size, dist, neighbours=None, device=None, look=1, operator=None):
+    def __init__(self, local_spmv, local_diag, lower_idx, upper_idx, rank, world_size, dist, neighbours=None, device=None, look=1, operator=None,
+                 variant="classic"):
         import torch
+        if variant not in ("classic", "single_reduction"):
+            raise ValueError("DistributedCG: variant must be 'classic' or 'single_reduction', not %r" % (variant,))
+        self.variant = variant
         self.torch, self.dist = torch, dist
         self.spmv, self.rank, self.world = local_spmv, rank, world_size
         self.dev, self.look, self.operator = device, max(1, int(look)), operator
@@ -418,11 +428,23 @@ class DistributedCG:
         self.w = 1.0 / mult                                         # a dof held by k ranks counts 1/k in every dot product
         self.breakdown = None
 
+    @property
+    def reductions_per_iteration(self):
+        """blocking scalar all-reduces of one iteration (at world size > 1): 2 for the classic form, 1 for the single-reduction form"""
+        return 1 if self.variant == "single_reduction" else 2
+
     def dot(self, a, b):
         s = (self.w * a * b).sum().reshape(1)
         if self.world > 1:
             all_reduce_sum(s, self.dist)
         return float(s.item())
+
+    def _sums(self, *terms):
+        """the sums of the given per-dof terms over all ranks, with ONE all-reduce"""
+        s = self.torch.stack([t.sum() for t in terms])
+        if self.world > 1:
+            all_reduce_sum(s, self.dist)
+        return s.tolist()
 
     def apply(self, x):
         if self.spmv is None:                                       # operator=(pattern, nz) given instead of a callable
@@ -439,6 +461,8 @@ class DistributedCG:
         """b: ASSEMBLED right-hand side (consistent), x: initial guess (consistent); returns (x, iterations, ‖r‖)."""
         if self.dev is not None and x.is_cuda:
             return self._solve_device(b, x, rtol, atol, maxiter)
+        if self.variant == "single_reduction":
+            return self._solve_single_reduction(b, x, rtol, atol, maxiter)
         r = b - self.apply(x)
         z = self.dinv * r
         p = z.clone()
@@ -456,15 +480,58 @@ class DistributedCG:
             x += alpha * p
             r -= alpha * Ap
             z = self.dinv * r
-            rz_new = self.dot(r, z)
-            rn = self.dot(r, r) ** 0.5
+            rz_new, rr = self._sums(self.w * r * z, self.w * r * r)   # one all-reduce of the two sums (the device path's S[2:4])
+            rn = rr ** 0.5
             p = z + (rz_new / rz) * p
             rz = rz_new
             it += 1
         return x, it, rn
 
-    def device_iteration(self, p, Ap, S):
-        """One product of the device path: Ap ← assembled A·p, S[1] ← pᵀAp (summed over the ranks).  S: device scalars rz | pAp | rz_new | rr | flag."""
+    def _local_product(self, u):
+        """(w, d): w = assembled A·u, d = this rank's uᵀA_p u before the halo sum (u is consistent: the sum over the ranks is uᵀAu)"""
+        if self.spmv is None:
+            from ._lib import check, lib
+            pattern, nz = self.operator
+            y = self.torch.empty_like(u)
+            check(lib().tb_spmv_csr(pattern.h, nz.ptr, u.data_ptr(), 1.0, 0.0, y.data_ptr()))
+        else:
+            y = self.spmv(u)
+        d = (u * y).sum()
+        self.halo.exchange_sum(y)
+        return y, d
+
+    def _solve_single_reduction(self, b, x, rtol, atol, maxiter):
+        """plain-torch statement of the single-reduction form (see the class docstring); the device path computes the same"""
+        r = b - self.apply(x)
+        u = self.dinv * r
+        w, d = self._local_product(u)
+        gam, dl, rho = self._sums(self.w * r * u, d, self.w * r * r)
+        rn = rho ** 0.5
+        tol = atol + rtol * rn
+        p, s = self.torch.zeros_like(x), self.torch.zeros_like(x)
+        gam_prev = alpha_prev = 0.0
+        it = 0
+        while rn > tol and it < maxiter:
+            beta = gam / gam_prev if gam_prev != 0.0 else 0.0
+            den = dl - beta * gam / alpha_prev if beta != 0.0 else dl          # = pᵀAp
+            if not den > 0.0:
+                self.breakdown = den
+                raise ArithmeticError("DistributedCG: pᵀAp = %g ≤ 0 at iteration %d — the operator is not positive definite" % (den, it))
+            alpha = gam / den
+            p = u + beta * p
+            s = w + beta * s
+            x += alpha * p
+            r -= alpha * s
+            u = self.dinv * r
+            w, d = self._local_product(u)
+            gam_prev, alpha_prev = gam, alpha
+            gam, dl, rho = self._sums(self.w * r * u, d, self.w * r * r)    # the one all-reduce of the iteration
+            rn = rho ** 0.5
+            it += 1
+        return x, it, rn
+
+    def _device_product(self, p, Ap, acc):
+        """Ap ← assembled A·p, acc (a one-double device tensor) += this rank's pᵀA_p p — no all-reduce"""
         import ctypes as C
         from ._lib import check, lib
         L, ptr = lib(), (lambda t: C.c_void_p(t.data_ptr()))
@@ -473,13 +540,17 @@ class DistributedCG:
             pattern, nz = self.operator
             self.halo.pack_product_rows(pattern, nz, p)              # interface rows first …
             self.halo.start()                                        # … their exchange in flight …
-            check(L.tb_spmv_csr_dot(pattern.h, nz.ptr, ptr(p), ptr(Ap), ptr(S[1:2])))   # … behind the whole local product + local pᵀA_p p
+            check(L.tb_spmv_csr_dot(pattern.h, nz.ptr, ptr(p), ptr(Ap), ptr(acc)))   # … behind the whole local product + local pᵀA_p p
             self.halo.finish(Ap, own_from_send=True)                 # interface rows: own (rows kernel) + received (the peer's rows kernel), bitwise symmetric
         else:
             y = self.spmv(p)
-            check(L.tb_cgd_dot(self.dev.h, n, None, ptr(p), ptr(y), ptr(S[1:2])))       # local quadratic form, before the halo sum
+            check(L.tb_cgd_dot(self.dev.h, n, None, ptr(p), ptr(y), ptr(acc)))       # local quadratic form, before the halo sum
             self.halo.exchange_sum(y)
             Ap.copy_(y)
+
+    def device_iteration(self, p, Ap, S):
+        """One product of the device path: Ap ← assembled A·p, S[1] ← pᵀAp (summed over the ranks).  S: device scalars rz | pAp | rz_new | rr | flag."""
+        self._device_product(p, Ap, S[1:2])
         if self.world > 1:
             all_reduce_sum(S[1:2], self.dist)
 
@@ -503,6 +574,42 @@ class DistributedCG:
         check(L.tb_cgd_direction(dev.h, n, ptr(self.dinv), ptr(r), ptr(p), ptr(S[0:1]), ptr(S[2:3])))
         check(L.tb_cgd_rotate(dev.h, ptr(S)))                        # rz ← rz_new, ‖r‖² → S[5], accumulators back to zero: one launch
 
+    def device_setup1(self, b, x):
+        """Set-up of the single-reduction device path: returns (r, u, p, s, w, S) with r = b − A x, u = D⁻¹ r, w = A u, p = s = 0 and the seven-double
+        scalar block S = {γ₀, δ₀, ρ₀, flag 0, γ_prev 0, α_prev 0, 0} (include/tbhip.h), S[0:3] all-reduced — ready for `device_step1`."""
+        import ctypes as C
+        from ._lib import check, lib
+        torch, L, n = self.torch, lib(), x.numel()
+        ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        S = torch.zeros(7, dtype=torch.float64, device=x.device)
+        r = b - self.apply(x)
+        u = self.dinv * r
+        w, p, s = torch.empty_like(x), torch.zeros_like(x), torch.zeros_like(x)
+        self._device_product(u, w, S[1:2])
+        check(L.tb_cgd_dot(self.dev.h, n, ptr(self.w), ptr(r), ptr(u), ptr(S[0:1])))
+        check(L.tb_cgd_dot(self.dev.h, n, ptr(self.w), ptr(r), ptr(r), ptr(S[2:3])))
+        if self.world > 1:
+            all_reduce_sum(S[0:3], self.dist)
+        return r, u, p, s, w, S
+
+    def device_step1(self, x, r, u, p, s, w, S):
+        """One whole iteration of the single-reduction device path, no host read: update of p, s, x, r, u with the partials of γ and ρ, product
+        w = A·u with the local δ, fold into S[0:3], ONE all-reduce of S[0:3].  S: the seven-double block of `device_setup1`."""
+        import ctypes as C
+        from ._lib import check, lib
+        L, dev, n = lib(), self.dev, x.numel()
+        ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        if self.world == 1 and not self.nb and self.operator is not None and self.one_call:
+            pattern, nz = self.operator                              # no shared dofs: the three launches from one library call (tb_cg1_iteration)
+            check(L.tb_cg1_iteration(pattern.h, nz.ptr, ptr(self.dinv), ptr(x), ptr(r), ptr(u), ptr(p), ptr(s), ptr(w), ptr(S)))
+            return
+        wt = ptr(self.w) if self.nb else None                        # no shared dofs: every weight is 1, the kernel skips the read
+        check(L.tb_cg1_update(dev.h, n, wt, ptr(self.dinv), ptr(w), ptr(p), ptr(s), ptr(x), ptr(r), ptr(u), ptr(S)))
+        self._device_product(u, w, S[6:7])                           # w = A·u, local uᵀA_p u into the δ accumulator
+        check(L.tb_cg1_fold(dev.h, ptr(S)))
+        if self.world > 1:
+            all_reduce_sum(S[0:3], self.dist)                        # the one all-reduce: {γ, δ, ρ}
+
     def _solve_device(self, b, x, rtol, atol, maxiter):
         import ctypes as C
         from ._lib import check, lib
@@ -510,6 +617,8 @@ class DistributedCG:
         if dev.stream_handle != int(torch.cuda.current_stream().cuda_stream):
             raise RuntimeError("DistributedCG: the MI355XDevice is not on torch's current stream (device.set_stream(torch.cuda.current_stream().cuda_stream)); "
                                "its kernels would race with the all-reduces and the exchange")
+        if self.variant == "single_reduction":
+            return self._solve_device1(b, x, rtol, atol, maxiter)
         L = lib()
         ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
         S = torch.zeros(6, dtype=torch.float64, device=x.device)    # rz | pAp | rz_new | rr | breakdown flag | ‖r‖² of the last step  (device-resident scalars)
@@ -533,4 +642,20 @@ class DistributedCG:
                 self.breakdown = float(h[0])
                 raise ArithmeticError("DistributedCG: pᵀAp = %g ≤ 0 — the operator is not positive definite (or the iteration broke down)" % self.breakdown)
             rn = float(h[1]) ** 0.5
+        return x, it, rn
+
+    def _solve_device1(self, b, x, rtol, atol, maxiter):
+        r, u, p, s, w, S = self.device_setup1(b, x)
+        rn = float(S[2].item()) ** 0.5
+        tol = atol + rtol * rn
+        it = 0
+        while rn > tol and it < maxiter:
+            for _ in range(min(self.look, maxiter - it)):
+                self.device_step1(x, r, u, p, s, w, S)
+                it += 1
+            h = S[2:4].cpu()                                         # the one host read of the look: ‖r‖² and the breakdown flag
+            if float(h[1]) != 0.0:
+                self.breakdown = float(h[1])
+                raise ArithmeticError("DistributedCG: pᵀAp = %g ≤ 0 — the operator is not positive definite (or the iteration broke down)" % self.breakdown)
+            rn = float(h[0]) ** 0.5
         return x, it, rn
