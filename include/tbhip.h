@@ -56,7 +56,15 @@ enum {
 
 /* cell kinds (Ferrite reference shapes; local vertex order as src/mesh/generators.jl:62-79) */
 enum { TB_QUAD4 = 2 /* bilinear quadrilateral in the plane z = 0 (2-D problems; xyz still n×3) */, TB_HEX8 = 3, TB_TET4 = 4,
-       TB_HEX27 = 5 /* Q2 field on trilinear HEX8 geometry */ };
+       TB_HEX27 = 5 /* Q2 field on trilinear HEX8 geometry */,
+       TB_TET10 = 6 /* P2 field on affine TB_TET4 geometry (vector fields, ncomp = 3: the quasi-static mechanics path) */ };
+/* Tetrahedra (believed to be Ferrite's RefTetrahedron conventions; unpinned like the others until julia/make_golden.jl has run):
+ *   reference simplex vertices (0,0,0), (1,0,0), (0,1,0), (0,0,1);  local facets (0,2,1), (0,1,3), (1,2,3), (0,3,2) (outward normals);
+ *   TB_TET10 local order: the four vertices, then the edge nodes of (0,1), (1,2), (2,0), (0,3), (1,3), (2,3).
+ * Quadrature of the mechanics path on tetrahedra: TB_TET4 displacement — the 4-point degree-2 rule (points (a,a,a,1−3a), a = 0.1381966…,
+ * weights 1/24); TB_TET10 — Keast's 8-point degree-3 rule (Keast 1986; two orbits (a,a,a,1−3a), a = 0.328054696711427 and 0.106952273932930,
+ * weights 0.138527966511862 and 0.111472033488138 of the volume: all positive, unlike the 5-point rule with its negative centroid weight).
+ * Triangular facets: the 3-point degree-2 rule (interior points (1/6,1/6,2/3)) for TB_TET4, Dunavant's 6-point degree-4 rule for TB_TET10. */
 
 /* assembly strategies — device analogues of the FerriteOperators strategies Thunderbolt re-exports
  * (src/Thunderbolt.jl:22-32; selected via FiniteElementDiscretization(; assembly_strategy), src/discretization/fem.jl:38-46) */
@@ -80,7 +88,7 @@ enum {
     TB_FORM_MASS = 0,      /* Mₑ[i,j] += ρ NᵢNⱼ dΩ          src/modeling/core/mass.jl:28-43       */
     TB_FORM_DIFFUSION = 1, /* Kₑ[i,j] -= ∇Nⱼ·D·∇Nᵢ dΩ       src/modeling/core/diffusion.jl:28-50  */
     TB_FORM_SOURCE = 2,    /* bₑ[j]  += f(x_q,t) Nⱼ dΩ      src/modeling/core/analytical_coefficient.jl:80-101 */
-    TB_FORM_FACET = 4,       /* weak boundary conditions on hexahedron facets   src/modeling/core/weak_boundary_conditions.jl */
+    TB_FORM_FACET = 4,       /* weak boundary conditions on hexahedron / tetrahedron facets   src/modeling/core/weak_boundary_conditions.jl */
     TB_FORM_HYPERELASTIC = 3 /* rₑ[i] += ∇δuᵢ⊡P dΩ, Kₑ[i,j] += (∇δuᵢ⊡𝔸)⊡∇δuⱼ dΩ   src/modeling/solid/elements.jl:177-313 */
 };
 
@@ -164,9 +172,10 @@ const char *tb_version(void);
  * the first missing symbol).  4: tb_cgd_update writes three doubles (d_out3; revisions ≤ 3 wrote two).  5: tb_graph_*, tb_comm_exchange_begin / _end,
  * tb_cgd_iteration, tb_last_kernel_name.  6: tb_host_locality_permutation; calls that wait for the device refuse inside an open capture
  * (TB_ERR_BAD_ARG) instead of invalidating it.  7: tb_cg1_update / tb_cg1_fold / tb_cg1_iteration (single-reduction CG, seven-double scalar block).
+ * 8: TB_TET10, hyperelastic and facet forms on tetrahedra (TB_TET4 / TB_TET10 vector fields), tb_host_generate_grid_tet.
  * A host binding compares tb_abi_revision() with the
  * TB_ABI_REVISION it was written against and refuses to run on a mismatch (julia/ThunderboltHIPBackend.jl does, in __init__) */
-#define TB_ABI_REVISION 7
+#define TB_ABI_REVISION 8
 int tb_abi_revision(void);
 
 /* ------------------------------------------------------------------ device (AbstractGPUDevice, src/devices.jl:3-4;
@@ -210,7 +219,8 @@ int tb_event_destroy(void *event);
  * dh.cell_dofs / dh.cell_dofs_offset).  The host supplies Ferrite's own node coordinates, cell
  * connectivity and dof table, so DoF indexing is inherited bit-exactly, never re-derived.
  *   xyz        n_nodes×3 (AoS);  conn  n_cells×nverts;  cell_dofs  n_cells×(nbasis·ncomp)
- *   field_kind TB_QUAD4 | TB_HEX8 | TB_TET4 | TB_HEX27 (must match geom_kind's shape); ncomp 1 (scalar) or 3.
+ *   field_kind TB_QUAD4 | TB_HEX8 | TB_TET4 | TB_HEX27 | TB_TET10 (must match geom_kind's shape; TB_TET10 with ncomp = 3 only: scalar forms on
+ *   the quadratic tetrahedron return TB_ERR_UNSUPPORTED); ncomp 1 (scalar) or 3.
  *   TB_QUAD4: two-dimensional meshes (the reference's GPU tests and the spiral-wave tutorial run on generate_grid(Quadrilateral, …)):
  *   coordinates are passed as n×3 with z = 0 and diffusion tensors as 3×3 with the 2×2 tensor in the upper-left block. */
 int tb_mesh_create(tb_device *dev, int geom_kind, int64_t n_nodes, const double *xyz, int64_t n_cells,
@@ -257,7 +267,13 @@ int tb_assemble_vector(tb_form *form, int strategy, double t, double *d_b);
 /* ------------------------------------------------------------------ quasi-static hyperelasticity (vector field, ncomp = 3)
  * setup_element_cache(QuasiStaticModel(:u, PK1Model(...), ()), qr, sdh) (test/test_elements.jl:99-125);
  * operator creation via setup_operator(strategy, volume_integrator, dh) (src/solver/time/homotopy.jl:61-67).
- * qorder 0 → max(2p−1, 2) (src/discretization/fem.jl:52-55): 2 for Q1, 3 for Q2. */
+ * qorder 0 → max(2p−1, 2) (src/discretization/fem.jl:52-55): 2 for Q1, 3 for Q2; on tetrahedra the DEGREE of the rule, 2 for TB_TET4 and 3 for
+ * TB_TET10 (the rules are named with the cell kinds above).
+ * Tetrahedra (TB_TET4 / TB_TET10 vector fields): every energy and penalty, constant and nodal microstructure ([cell][geometry node 0..3][f|s|n][3],
+ * n_cells·4·9 values), steady active stress (nodal state n_cells × 4), prestress, cell sets and all four strategy codes — TB_STRATEGY_ATOMIC runs
+ * the cell kernel with hardware atomics, TB_STRATEGY_PER_COLOR and TB_STRATEGY_ELEMENT run it colour by colour with plain read-modify-write (an
+ * ordered sum: bit-reproducible), TB_STRATEGY_PATCH the one measured faster for the field (TB_TET4: atomics, TB_TET10: colours); there is no
+ * LDS-accumulating patch kernel for tetrahedral mechanics.  Not on tetrahedra (TB_ERR_UNSUPPORTED): condensed internal variables, Hill frameworks. */
 int tb_hyperelastic_create(tb_mesh *mesh, int qorder, const tb_material *material, tb_form **out);
 /* residual!(op, residual, u, p) (src/solver/nonlinear/newton_raphson.jl:234): d_r overwritten */
 int tb_residual(tb_form *form, int strategy, const double *d_u, double t, double *d_r);
@@ -332,7 +348,9 @@ int tb_hyperelastic_local_solve_report(tb_form *form, int64_t *n_failed, int32_t
  * the hexahedron numbered as Ferrite.reference_facets(RefHexahedron); `facet_qpoints` = Gauss points per direction on the
  * facet (the reference uses the interpolation order, src/discretization/fem.jl:80-90; 0 selects that).
  * tb_facet_assemble ADDS to d_nzval / d_r (either may be NULL): the reference accumulates surface terms into the same
- * Kₑ / rₑ as the volume term (call it after tb_linearize / tb_residual).  Vector field on hexahedra only. */
+ * Kₑ / rₑ as the volume term (call it after tb_linearize / tb_residual).  Vector fields on hexahedra and on tetrahedra (local facets 0…3 as listed with
+ * the cell kinds; facet_qpoints 0 selects the 3-point degree-2 rule for TB_TET4 and the 6-point degree-4 rule for TB_TET10, other values are
+ * refused; nodal pressure data n_cells × 4; TB_BC_BENDING_SPRING is not implemented on tetrahedra). */
 enum { TB_BC_ROBIN = 0, TB_BC_NORMAL_SPRING = 1, TB_BC_PRESSURE = 2,
        TB_BC_BENDING_SPRING = 3, /* BendingSpringBC: energy ½ kᵇ |F⁻ᵀN − N|² (:47-57, :301-415) */
        TB_BC_PRESSURE_FIELD = 4  /* PressureFieldBC: p(x) = param · first-order nodal data per cell (tb_facet_form_set_field; NULL → param) */ };
@@ -634,6 +652,15 @@ int tb_host_generate_grid_hex(int nx, int ny, int nz, const double *left, const 
 /* generate_grid(Quadrilateral, (nx, ny), left, right): nodes x-fastest, xyz n×3 with z = 0, counter-clockwise cells */
 int tb_host_generate_grid_quad(int nx, int ny, const double *left, const double *right, double *xyz, int32_t *conn);
 int tb_host_perturb_nodes(int nx, int ny, int nz, double amplitude_rel, double *xyz);
+/* generate_grid(Tetrahedron, (nx, ny, nz), left, right): the node lattice of tb_host_generate_grid_hex, every lattice cell (vertices v0…v7 in the
+ * hexahedron's order) cut into the six tetrahedra of the Kuhn (Freudenthal) split around the main diagonal v0–v6, in this order:
+ *   (v0,v1,v2,v6) (v0,v5,v1,v6) (v0,v2,v3,v6) (v0,v3,v7,v6) (v0,v4,v5,v6) (v0,v7,v4,v6)
+ * — every tetrahedron positively oriented, and conforming: each lattice face is cut by the diagonal through its corner nearest v0 on both sides.
+ * conn: 6·nx·ny·nz × 4, cell 6·h + k the k-th tetrahedron of lattice cell h.  Ferrite's own split lives in Ferrite, not in the reference tree:
+ * one more unpinned convention (results do not depend on it beyond the discretisation error). */
+int tb_host_generate_grid_tet(int nx, int ny, int nz, const double *left, const double *right, double *xyz, int32_t *conn);
+/* close!(dh): entities numbered by first visit (cell by cell: vertices, then edges, faces, volume), components interleaved; TB_HEX27 and TB_TET10 number
+ * vertex and edge (face, volume) entities, the first-order kinds vertices only */
 int64_t tb_host_close_dofs(int field_kind, int ncomp, int64_t n_cells, int64_t n_nodes, const int32_t *conn,
                            int32_t *cell_dofs);
 /* two-pass: colidx == NULL → counts only (fills rowptr, returns nnz) */

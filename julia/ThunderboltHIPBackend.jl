@@ -19,7 +19,7 @@ import Thunderbolt: AbstractGPUDevice, AbstractAssemblyStrategy, AbstractSolver,
 const libtbhip = get(ENV, "TBHIP_LIBRARY", "libtbhip.so")
 
 # revision of include/tbhip.h these ccalls were written against (TB_ABI_REVISION); a library of another revision reads / writes other buffer sizes
-const TB_ABI_REVISION = 7
+const TB_ABI_REVISION = 8
 const TB_ERR_UNSUPPORTED = Cint(-5) # include/tbhip.h
 function __init__()
     have = ccall((:tb_abi_revision, libtbhip), Cint, ())
@@ -137,7 +137,7 @@ function DeviceDofHandler(dev::MI355XDevice, dh::DofHandler)
     celldofs = Int32.(dh.cell_dofs)                                                     # dh.cell_dofs / cell_dofs_offset, src/utils.jl:52-56
     kind = grid.cells[1] isa Quadrilateral ? Cint(2) : grid.cells[1] isa Hexahedron ? Cint(3) : Cint(4)   # TB_QUAD4 / TB_HEX8 / TB_TET4
     ip = Ferrite.getfieldinterpolation(sdh, first(sdh.field_names))
-    fkind = (kind == 3 && Ferrite.getorder(ip) == 2) ? Cint(5) : kind                  # TB_HEX27
+    fkind = (kind == 3 && Ferrite.getorder(ip) == 2) ? Cint(5) : (kind == 4 && Ferrite.getorder(ip) == 2) ? Cint(6) : kind   # TB_HEX27 / TB_TET10
     ncomp = Ferrite.n_components(ip)
     mesh = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:tb_mesh_create, libtbhip), Cint,

@@ -294,17 +294,37 @@ class Grid:
     def getcellset(self, name):
         return self.cellsets[name]
 
-    # Ferrite.reference_facets(RefHexahedron), 0-based vertex ids, in Ferrite's facet order
+    # Ferrite.reference_facets(RefHexahedron / RefTetrahedron), 0-based vertex ids, in Ferrite's facet order
     HEX_FACETS = ((0, 3, 2, 1), (0, 1, 5, 4), (1, 2, 6, 5), (2, 3, 7, 6), (0, 4, 7, 3), (4, 5, 6, 7))
+    TET_FACETS = ((0, 2, 1), (0, 1, 3), (1, 2, 3), (0, 3, 2))
+
+    def reference_facets(self):
+        if self.cell_kind == Hexahedron:
+            return self.HEX_FACETS
+        if self.cell_kind == Tetrahedron:
+            return self.TET_FACETS
+        raise NotImplementedError("facets: hexahedral and tetrahedral grids")
+
+    def boundary_facets(self):
+        """(cell, local facet) pairs, 0-based, of the facets that belong to one cell only (vectorised: tetrahedral meshes are large)."""
+        facets = np.asarray(self.reference_facets())
+        nodes = np.sort(self.conn[:, facets], axis=2).reshape(-1, facets.shape[1])       # (n_cells · n_facets, nodes per facet)
+        _, inverse, counts = np.unique(nodes, axis=0, return_inverse=True, return_counts=True)
+        once = np.flatnonzero(counts[inverse.ravel()] == 1)
+        return np.stack([once // len(facets), once % len(facets)], axis=1).astype(np.int32)
 
     def addfacetset(self, name, predicate, all=True, boundary_only=True):
         """addfacetset!(grid, name, x -> Bool; all = true) (Ferrite): the (cell, local facet) pairs — 0-based — whose nodes all (any)
         satisfy the predicate; boundary facets only, like Ferrite's default use on generated grids (boundary_only=False: internal ones too)."""
-        if self.cell_kind != Hexahedron:
-            raise NotImplementedError("addfacetset: hexahedral grids")
+        ref_facets = self.reference_facets()
         if getattr(self, "facetsets", None) is None:
             self.facetsets = {}
         ok = np.array([bool(predicate(x)) for x in self.xyz])
+        if self.cell_kind == Tetrahedron:
+            cand = self.boundary_facets() if boundary_only else np.stack(np.divmod(np.arange(self.n_cells * 4), 4), axis=1).astype(np.int32)
+            hit = ok[self.conn[cand[:, 0][:, None], np.asarray(ref_facets)[cand[:, 1]]]]
+            self.facetsets[name] = np.ascontiguousarray(cand[hit.all(axis=1) if all else hit.any(axis=1)], dtype=np.int32).reshape(-1, 2)
+            return self.facetsets[name]
         out = []
         count = {}
         if boundary_only:
@@ -350,8 +370,26 @@ def generate_mesh(cell_kind, nel, left=(-1.0, -1.0, -1.0), right=(1.0, 1.0, 1.0)
         check(lib().tb_host_generate_grid_quad(nx, ny, le.ctypes.data_as(L.c_dp), ri.ctypes.data_as(L.c_dp),
                                               xyz.ctypes.data_as(L.c_dp), conn.ctypes.data_as(L.c_i32p)))
         return Grid(cell_kind, xyz, conn, dims=(nx, ny))
+    if cell_kind == Tetrahedron:
+        # the hexahedral lattice, every lattice cell cut into six tetrahedra around one main diagonal (tbhip.h: tb_host_generate_grid_tet)
+        if perturb:
+            raise NotImplementedError("generate_mesh(Tetrahedron, …): perturb the returned grid's xyz yourself (the facet sets are found on the box)")
+        nx, ny, nz = nel
+        xyz = np.empty(((nx + 1) * (ny + 1) * (nz + 1), 3))
+        conn = np.empty((6 * nx * ny * nz, 4), dtype=np.int32)
+        le, ri = np.asarray(left, dtype=np.float64), np.asarray(right, dtype=np.float64)
+        check(lib().tb_host_generate_grid_tet(nx, ny, nz, le.ctypes.data_as(L.c_dp), ri.ctypes.data_as(L.c_dp),
+                                             xyz.ctypes.data_as(L.c_dp), conn.ctypes.data_as(L.c_i32p)))
+        g = Grid(cell_kind, xyz, conn, dims=(nx, ny, nz))
+        # the six facet sets of Ferrite's generate_grid: boundary facets whose nodes lie on the box face (lattice points on a face carry its coordinate exactly)
+        bf = g.boundary_facets()
+        fx = xyz[conn[bf[:, 0][:, None], np.asarray(Grid.TET_FACETS)[bf[:, 1]]]]                 # (n, 3 nodes, 3)
+        g.facetsets = {}
+        for name, (axis, val) in {"left": (0, le[0]), "right": (0, ri[0]), "front": (1, le[1]), "back": (1, ri[1]), "bottom": (2, le[2]), "top": (2, ri[2])}.items():
+            g.facetsets[name] = np.ascontiguousarray(bf[(fx[:, :, axis] == val).all(axis=1)], dtype=np.int32)
+        return g
     if cell_kind != Hexahedron:
-        raise NotImplementedError("generate_mesh: Hexahedron boxes and Quadrilateral rectangles are generated; pass your own Grid for others")
+        raise NotImplementedError("generate_mesh: Hexahedron / Tetrahedron boxes and Quadrilateral rectangles are generated; pass your own Grid for others")
     nx, ny, nz = nel
     nn = (nx + 1) * (ny + 1) * (nz + 1)
     xyz = np.empty((nn, 3))
@@ -372,11 +410,15 @@ class DofHandler:
         self.grid, self.ip = grid, ip
         if grid.cell_kind == Hexahedron:
             self.field_kind = L.TB_HEX8 if ip.order == 1 else L.TB_HEX27
+        elif grid.cell_kind == Tetrahedron and ip.order == 2:
+            if ip.ncomp != 3:
+                raise NotImplementedError("quadratic tetrahedra carry the 3-component displacement field only (scalar forms: first order)")
+            self.field_kind = L.TB_TET10
         else:
             if ip.order != 1:
-                raise NotImplementedError("only first-order tetrahedra / quadrilaterals")
+                raise NotImplementedError("only first-order quadrilaterals")
             self.field_kind = grid.cell_kind
-        nb = {L.TB_HEX8: 8, L.TB_HEX27: 27, L.TB_TET4: 4, L.TB_QUAD4: 4}[self.field_kind]
+        nb = {L.TB_HEX8: 8, L.TB_HEX27: 27, L.TB_TET4: 4, L.TB_QUAD4: 4, L.TB_TET10: 10}[self.field_kind]
         self.ndofs_per_cell = nb * ip.ncomp
         if cell_dofs is None:  # close!(dh)
             cd = np.empty((grid.n_cells, self.ndofs_per_cell), dtype=np.int32)
@@ -399,6 +441,37 @@ class DofHandler:
 
 def ndofs(dh):
     return dh.ndofs
+
+
+# tensor index (per direction 0, 1, 2 ↔ ξ = −1, 0, 1) of the nodes of Lagrange{RefHexahedron, 2} and the edges of Lagrange{RefTetrahedron, 2} (tbhip.h)
+_HEX27_TIX = ((0, 0, 0), (2, 0, 0), (2, 2, 0), (0, 2, 0), (0, 0, 2), (2, 0, 2), (2, 2, 2), (0, 2, 2), (1, 0, 0), (2, 1, 0), (1, 2, 0), (0, 1, 0), (1, 0, 2),
+              (2, 1, 2), (1, 2, 2), (0, 1, 2), (0, 0, 1), (2, 0, 1), (2, 2, 1), (0, 2, 1), (1, 1, 0), (1, 0, 1), (2, 1, 1), (1, 2, 1), (0, 1, 1), (1, 1, 2), (1, 1, 1))
+_HEX8_SIGNS = ((-1, -1, -1), (1, -1, -1), (1, 1, -1), (-1, 1, -1), (-1, -1, 1), (1, -1, 1), (1, 1, 1), (-1, 1, 1))
+TET10_EDGES = ((0, 1), (1, 2), (2, 0), (0, 3), (1, 3), (2, 3))
+
+
+def dof_coordinates(dh):
+    """Position of every dof, (ndofs, 3): the image of its node's reference position under the cell's geometry map (trilinear hexahedron / affine
+    tetrahedron) — vertices for first-order fields, plus edge midpoints (face centres, cell centre) of the reference cell for second-order ones.
+    What Ferrite users get from a loop over `reference_coordinates(ip)` and `spatial_coordinate`; the components of a node share its position."""
+    g, kind = dh.grid, dh.field_kind
+    X = g.xyz[g.conn]                                                            # (nc, nverts, 3)
+    if kind in (L.TB_HEX8, L.TB_TET4, L.TB_QUAD4):
+        pos = X
+    elif kind == L.TB_HEX27:
+        xi = np.asarray(_HEX27_TIX, dtype=np.float64) - 1.0
+        N = 0.125 * np.prod(1.0 + np.asarray(_HEX8_SIGNS, dtype=np.float64)[None, :, :] * xi[:, None, :], axis=2)
+        pos = np.einsum("ba,cak->cbk", N, X)
+    elif kind == L.TB_TET10:
+        e = np.asarray(TET10_EDGES)
+        pos = np.concatenate([X, 0.5 * (X[:, e[:, 0]] + X[:, e[:, 1]])], axis=1)
+    else:
+        raise NotImplementedError("dof_coordinates: field kind %d" % kind)
+    nc = dh.ip.ncomp
+    out = np.empty((dh.ndofs, 3))
+    for c in range(nc):
+        out[dh.cell_dofs[:, c::nc].ravel()] = pos.reshape(-1, 3)
+    return out
 
 
 def locality_permutation(grid, dh=None):

@@ -341,8 +341,12 @@ int tb_mesh_create(tb_device *dev, int geom_kind, int64_t n_nodes, const double 
     TB_REQUIRE(dev && out && xyz && conn && cell_dofs, "tb_mesh_create: NULL argument");
     *out = nullptr;
     TB_REQUIRE(geom_kind == TB_HEX8 || geom_kind == TB_TET4 || geom_kind == TB_QUAD4, "tb_mesh_create: geometry kind %d (need TB_QUAD4, TB_HEX8 or TB_TET4)", geom_kind);
-    TB_REQUIRE(field_kind == geom_kind || (geom_kind == TB_HEX8 && field_kind == TB_HEX27),
+    TB_REQUIRE(field_kind == geom_kind || (geom_kind == TB_HEX8 && field_kind == TB_HEX27) || (geom_kind == TB_TET4 && field_kind == TB_TET10),
                "tb_mesh_create: field kind %d does not live on geometry kind %d", field_kind, geom_kind);
+    if (field_kind == TB_TET10 && ncomp != 3) {
+        set_error("tb_mesh_create: TB_TET10 carries the 3-component displacement field only (scalar forms on the quadratic tetrahedron are not implemented)");
+        return TB_ERR_UNSUPPORTED;
+    }
     TB_REQUIRE(ncomp == 1 || ncomp == 3, "tb_mesh_create: ncomp must be 1 or 3 (got %d)", ncomp);
     TB_REQUIRE(index_base == 0 || index_base == 1, "tb_mesh_create: index_base must be 0 or 1");
     TB_REQUIRE(n_nodes > 0 && n_cells >= 0 && ndofs > 0 && n_nodes < 0x7fffffff && ndofs < 0x7fffffff,
@@ -585,7 +589,7 @@ int tb_hyperelastic_create(tb_mesh *mesh, int qorder, const tb_material *materia
     *out = nullptr;
     TB_REQUIRE(material->kind >= TB_MATERIAL_HOLZAPFEL_OGDEN_2009 && material->kind <= TB_MATERIAL_GUCCIONE_1991, "tb_hyperelastic_create: unknown material kind %d", material->kind);
     TB_REQUIRE(material->reserved >= TB_PENALTY_SIMPLE && material->reserved <= TB_PENALTY_HARTMANN_NEFF_3, "tb_hyperelastic_create: unknown compression penalty %d", material->reserved);
-    TB_REQUIRE(mesh->ncomp == 3 && mesh->geom_kind == TB_HEX8, "tb_hyperelastic_create: needs a 3-component field on hexahedra");
+    TB_REQUIRE(mesh->ncomp == 3 && (mesh->geom_kind == TB_HEX8 || mesh->geom_kind == TB_TET4), "tb_hyperelastic_create: needs a 3-component field on hexahedra or tetrahedra");
     // the kernels address a node's three dofs as consecutive ids (Ferrite: node-major, component-minor, io.jl:233-238)
     for (int64_t i = 0; i < mesh->n_cells * mesh->nb; ++i) {
         const int32_t *d = &mesh->h_cell_dofs[3 * i];
@@ -597,7 +601,7 @@ int tb_hyperelastic_create(tb_mesh *mesh, int qorder, const tb_material *materia
     f->mat.fsn_field = nullptr;
     f->act_tension = material->p[9];
     if (material->fsn_field) {
-        const int64_t need = mesh->n_cells * 72;
+        const int64_t need = mesh->n_cells * mesh->nverts * 9;
         TB_REQUIRE(material->fsn_field_len == need, "tb_hyperelastic_create: microstructure field needs %lld values, got %lld", (long long)need,
                    (long long)material->fsn_field_len);
         TB_HIP(hipMalloc((void **)&f->d_field, sizeof(double) * need));
@@ -614,7 +618,7 @@ int tb_hyperelastic_set_active_tension(tb_form *form, double tension, const doub
     tb_mesh *m = form->mesh;
     form->act_tension = tension;
     if (!state_field) { hipFree(form->d_act_field); form->d_act_field = nullptr; return TB_OK; }
-    TB_REQUIRE(len == m->n_cells * 8, "tb_hyperelastic_set_active_tension: state field needs %lld values (cells × 8), got %lld", (long long)(m->n_cells * 8), (long long)len);
+    TB_REQUIRE(len == m->n_cells * m->nverts, "tb_hyperelastic_set_active_tension: state field needs %lld values (cells × %d), got %lld", (long long)(m->n_cells * m->nverts), m->nverts, (long long)len);
     TB_HIP(hipSetDevice(m->dev->id));
     if (!form->d_act_field && len) TB_HIP(hipMalloc((void **)&form->d_act_field, sizeof(double) * len));
     if (len) {
@@ -681,6 +685,7 @@ int tb_hyperelastic_set_condensation(tb_form *form, int sarcomere_model, const d
 {
     TB_REQUIRE(form && form->kind == TB_FORM_HYPERELASTIC, "tb_hyperelastic_set_condensation: not a hyperelastic form");
     if (sarcomere_model < 0) { form->cond_model = 0; return TB_OK; }
+    if (form->mesh->geom_kind == TB_TET4) { set_error("tb_hyperelastic_set_condensation: condensed internal variables are not implemented on tetrahedra"); return TB_ERR_UNSUPPORTED; }
     TB_REQUIRE(sarcomere_model == TB_SARCOMERE_RDQ20MF, "tb_hyperelastic_set_condensation: sarcomere model %d has no internal state (TB_SARCOMERE_RDQ20MF)", sarcomere_model);
     TB_REQUIRE(params && n_params == 17, "tb_hyperelastic_set_condensation: RDQ20MF takes 17 parameters");
     TB_REQUIRE(local_tol >= 0.0 && local_max_iters >= 1, "tb_hyperelastic_set_condensation: need tol >= 0 and max_iters >= 1");
@@ -695,7 +700,7 @@ int tb_hyperelastic_set_condensation(tb_form *form, int sarcomere_model, const d
 int tb_hyperelastic_n_quadrature_points(tb_form *form, int64_t *n_points)
 {
     TB_REQUIRE(form && form->kind == TB_FORM_HYPERELASTIC && n_points, "tb_hyperelastic_n_quadrature_points: bad argument");
-    const int nq = form->qorder * form->qorder * form->qorder;
+    const int nq = form->mesh->field_kind == TB_TET4 ? 4 : form->mesh->field_kind == TB_TET10 ? 8 : form->qorder * form->qorder * form->qorder;
     *n_points = form->mesh->n_cells * nq;
     return TB_OK;
 }
@@ -757,6 +762,10 @@ int tb_hyperelastic_set_hill(tb_form *form, const tb_hill *hill)
 {
     TB_REQUIRE(form && form->kind == TB_FORM_HYPERELASTIC, "tb_hyperelastic_set_hill: not a hyperelastic form");
     if (hill) { int rc = validate_hill(hill, "tb_hyperelastic_set_hill"); if (rc) return rc; }
+    if (hill && hill->framework != TB_HILL_NONE && form->mesh->geom_kind == TB_TET4) {
+        set_error("tb_hyperelastic_set_hill: Hill frameworks are not implemented on tetrahedra");
+        return TB_ERR_UNSUPPORTED;
+    }
     store_hill(form, hill);
     return TB_OK;
 }
@@ -808,11 +817,19 @@ int tb_facet_form_create(tb_mesh *mesh, int bc_kind, double param, int facet_qpo
     TB_REQUIRE(mesh && out && (facets || n_facets == 0), "tb_facet_form_create: NULL argument");
     *out = nullptr;
     TB_REQUIRE(bc_kind >= TB_BC_ROBIN && bc_kind <= TB_BC_PRESSURE_FIELD, "tb_facet_form_create: unknown boundary condition %d", bc_kind);
-    TB_REQUIRE(mesh->ncomp == 3 && mesh->geom_kind == TB_HEX8, "tb_facet_form_create: needs a 3-component field on hexahedra");
+    TB_REQUIRE(mesh->ncomp == 3 && (mesh->geom_kind == TB_HEX8 || mesh->geom_kind == TB_TET4), "tb_facet_form_create: needs a 3-component field on hexahedra or tetrahedra");
     TB_REQUIRE(index_base == 0 || index_base == 1, "tb_facet_form_create: index_base must be 0 or 1");
     TB_REQUIRE(n_facets >= 0, "tb_facet_form_create: negative facet count");
+    const bool tet = mesh->geom_kind == TB_TET4;
+    const int nlf = tet ? 4 : 6;
+    if (tet) {
+        if (bc_kind == TB_BC_BENDING_SPRING) { set_error("tb_facet_form_create: the bending spring is not implemented on tetrahedra"); return TB_ERR_UNSUPPORTED; }
+        TB_REQUIRE(facet_qpoints == 0, "tb_facet_form_create: triangular facets integrate with the rule of the field (facet_qpoints = 0), got %d", facet_qpoints);
+        facet_qpoints = mesh->field_kind == TB_TET10 ? 6 : 3; // points of the rule
+    } else {
     if (facet_qpoints == 0) facet_qpoints = kind_order(mesh->field_kind);
     TB_REQUIRE(facet_qpoints >= 1 && facet_qpoints <= 3, "tb_facet_form_create: 1…3 Gauss points per facet direction (got %d)", facet_qpoints);
+    }
     for (int64_t i = 0; i < mesh->n_cells * mesh->nb; ++i) {
         const int32_t *d = &mesh->h_cell_dofs[3 * i];
         TB_REQUIRE(d[1] == d[0] + 1 && d[2] == d[0] + 2, "tb_facet_form_create: dofs of a node are not consecutive (cell %lld)", (long long)(i / mesh->nb));
@@ -820,7 +837,7 @@ int tb_facet_form_create(tb_mesh *mesh, int bc_kind, double param, int facet_qpo
     std::vector<int32_t> fl((size_t)2 * n_facets);
     for (int64_t i = 0; i < n_facets; ++i) {
         const int32_t c = facets[2 * i] - index_base, lf = facets[2 * i + 1] - index_base;
-        TB_REQUIRE(c >= 0 && c < mesh->n_cells && lf >= 0 && lf < 6, "tb_facet_form_create: facet %lld = (%d, %d) out of range", (long long)i, facets[2 * i], facets[2 * i + 1]);
+        TB_REQUIRE(c >= 0 && c < mesh->n_cells && lf >= 0 && lf < nlf, "tb_facet_form_create: facet %lld = (%d, %d) out of range", (long long)i, facets[2 * i], facets[2 * i + 1]);
         fl[2 * i] = c; fl[2 * i + 1] = lf;
     }
     auto f = std::make_unique<tb_form>();
@@ -837,7 +854,7 @@ int tb_facet_form_set_field(tb_form *form, const double *field, int64_t len)
     TB_REQUIRE(form && form->kind == TB_FORM_FACET && form->bc_kind == TB_BC_PRESSURE_FIELD, "tb_facet_form_set_field: not a PressureFieldBC form");
     tb_mesh *m = form->mesh;
     if (!field) { hipFree(form->d_field); form->d_field = nullptr; return TB_OK; }
-    TB_REQUIRE(len == m->n_cells * 8, "tb_facet_form_set_field: needs %lld values (cells × 8), got %lld", (long long)(m->n_cells * 8), (long long)len);
+    TB_REQUIRE(len == m->n_cells * m->nverts, "tb_facet_form_set_field: needs %lld values (cells × %d), got %lld", (long long)(m->n_cells * m->nverts), m->nverts, (long long)len);
     TB_HIP(hipSetDevice(m->dev->id));
     if (!form->d_field) TB_HIP(hipMalloc((void **)&form->d_field, sizeof(double) * len));
     TB_HIP(hipMemcpyAsync(form->d_field, field, sizeof(double) * len, hipMemcpyHostToDevice, m->dev->stream));
@@ -860,6 +877,7 @@ int tb_facet_assemble(tb_form *form, tb_pattern *pat, const double *d_u, double 
     TB_REQUIRE(!d_nzval || (pat && pat->mesh == form->mesh), "tb_facet_assemble: the tangent needs the pattern of the form's mesh");
     if (form->n_facets == 0) return TB_OK;
     TB_HIP(hipSetDevice(form->mesh->dev->id));
+    if (form->mesh->geom_kind == TB_TET4) return launch_facets_tet(form, pat, d_u, d_nzval, d_r);
     return launch_facets(form, pat, d_u, d_nzval, d_r);
 }
 

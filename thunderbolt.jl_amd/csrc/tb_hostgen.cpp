@@ -19,6 +19,9 @@ using namespace tb;
 namespace {
 
 constexpr int HEX_EDGES[12][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 0}, {4, 5}, {5, 6}, {6, 7}, {7, 4}, {0, 4}, {1, 5}, {2, 6}, {3, 7}};
+constexpr int TET_EDGES[6][2] = {{0, 1}, {1, 2}, {2, 0}, {0, 3}, {1, 3}, {2, 3}};
+// Kuhn split of a lattice cell around the diagonal v0–v6, positively oriented (tbhip.h: tb_host_generate_grid_tet)
+constexpr int HEX_TO_TETS[6][4] = {{0, 1, 2, 6}, {0, 5, 1, 6}, {0, 2, 3, 6}, {0, 3, 7, 6}, {0, 4, 5, 6}, {0, 7, 4, 6}};
 constexpr int HEX_FACES[6][4] = {{0, 3, 2, 1}, {0, 1, 5, 4}, {1, 2, 6, 5}, {2, 3, 7, 6}, {0, 4, 7, 3}, {4, 5, 6, 7}};
 
 struct EntityRef {
@@ -60,6 +63,20 @@ int tb_host_generate_grid_hex(int nx, int ny, int nz, const double *left, const 
                 e[4] = (int32_t)(b + px * py); e[5] = (int32_t)(b + 1 + px * py);
                 e[6] = (int32_t)(b + 1 + px + px * py); e[7] = (int32_t)(b + px + px * py);
             }
+    return TB_OK;
+}
+
+int tb_host_generate_grid_tet(int nx, int ny, int nz, const double *left, const double *right, double *xyz, int32_t *conn)
+{
+    TB_REQUIRE(nx > 0 && ny > 0 && nz > 0 && left && right && xyz && conn, "tb_host_generate_grid_tet: bad argument");
+    TB_REQUIRE(6 * (int64_t)nx * ny * nz < 0x7fffffff, "tb_host_generate_grid_tet: too many cells for Int32");
+    std::vector<int32_t> hex((size_t)8 * nx * ny * nz);
+    const int rc = tb_host_generate_grid_hex(nx, ny, nz, left, right, xyz, hex.data());
+    if (rc) return rc;
+#pragma omp parallel for schedule(static)
+    for (int64_t h = 0; h < (int64_t)nx * ny * nz; ++h)
+        for (int k = 0; k < 6; ++k)
+            for (int a = 0; a < 4; ++a) conn[(6 * h + k) * 4 + a] = hex[8 * h + HEX_TO_TETS[k][a]];
     return TB_OK;
 }
 
@@ -109,12 +126,12 @@ int tb_host_generate_grid_quad(int nx, int ny, const double *left, const double 
 int64_t tb_host_close_dofs(int field_kind, int ncomp, int64_t n_cells, int64_t n_nodes, const int32_t *conn, int32_t *cell_dofs)
 {
     if (!(conn && cell_dofs && n_cells >= 0 && n_nodes > 0 && ncomp >= 1) ||
-        !(field_kind == TB_HEX8 || field_kind == TB_TET4 || field_kind == TB_HEX27 || field_kind == TB_QUAD4)) {
+        !(field_kind == TB_HEX8 || field_kind == TB_TET4 || field_kind == TB_HEX27 || field_kind == TB_QUAD4 || field_kind == TB_TET10)) {
         set_error("tb_host_close_dofs: bad argument");
         return TB_ERR_BAD_ARG;
     }
-    const int nv = kind_nverts(field_kind == TB_HEX27 ? TB_HEX8 : field_kind);
-    const int slots = field_kind == TB_HEX27 ? 27 : nv; // entity slots per cell, in visiting order
+    const int nv = kind_nverts(field_kind);
+    const int slots = kind_nbasis(field_kind); // entity slots per cell, in visiting order
     const int nb = slots;
     // first visit of every entity = smallest (cell, slot) key that references it
     std::vector<int64_t> first_of_slot((size_t)n_cells * slots); // per (cell,slot): key of the entity's first visit
@@ -128,6 +145,22 @@ int64_t tb_host_close_dofs(int field_kind, int ncomp, int64_t n_cells, int64_t n
 #pragma omp parallel for schedule(static)
         for (int64_t c = 0; c < n_cells; ++c)
             for (int a = 0; a < nv; ++a) first_of_slot[c * slots + a] = first[conn[c * nv + a]];
+    }
+    if (field_kind == TB_TET10) { // vertices, then the six edges (first visit decides, as for the hexahedron's edges)
+        std::vector<EntityRef> refs((size_t)n_cells * 6);
+#pragma omp parallel for schedule(static)
+        for (int64_t c = 0; c < n_cells; ++c)
+            for (int e = 0; e < 6; ++e) {
+                int32_t a = conn[c * 4 + TET_EDGES[e][0]], b = conn[c * 4 + TET_EDGES[e][1]];
+                if (a > b) std::swap(a, b);
+                refs[c * 6 + e] = {{a, b, -1, -1}, c * 10 + 4 + e};
+            }
+        std::sort(refs.begin(), refs.end());
+        int64_t cur = -1;
+        for (size_t i = 0; i < refs.size(); ++i) {
+            if (i == 0 || refs[i].key != refs[i - 1].key) cur = refs[i].slot;
+            first_of_slot[refs[i].slot] = cur;
+        }
     }
     if (field_kind == TB_HEX27) {
         auto resolve = [&](std::vector<EntityRef> &refs) {

@@ -82,9 +82,9 @@ struct Status {
     long long cell;      // one offending cell (0-based)
 };
 
-inline int kind_nverts(int kind) { return kind == TB_TET4 || kind == TB_QUAD4 ? 4 : 8; }
-inline int kind_nbasis(int kind) { return kind == TB_TET4 || kind == TB_QUAD4 ? 4 : kind == TB_HEX27 ? 27 : 8; }
-inline int kind_order(int kind) { return kind == TB_HEX27 ? 2 : 1; }
+inline int kind_nverts(int kind) { return kind == TB_TET4 || kind == TB_QUAD4 || kind == TB_TET10 ? 4 : 8; }
+inline int kind_nbasis(int kind) { return kind == TB_TET4 || kind == TB_QUAD4 ? 4 : kind == TB_HEX27 ? 27 : kind == TB_TET10 ? 10 : 8; }
+inline int kind_order(int kind) { return kind == TB_HEX27 || kind == TB_TET10 ? 2 : 1; }
 
 // ---- assembly plans (built lazily on the host, cached on the mesh / pattern) ----
 struct ColorPlan {
@@ -390,6 +390,8 @@ int launch_cg(tb_pattern *pat, const double *A, const double *b, double *x, doub
 int launch_axpy(tb_device *dev, int64_t n, double a, const double *x, double *y);
 int launch_absmax(tb_device *dev, int64_t n, const double *x, int64_t stride, double *result);
 int launch_facets(tb_form *f, tb_pattern *p, const double *d_u, double *d_nz, double *d_r);
+int launch_hyperelastic_tet(tb_form *f, tb_pattern *p, int strategy, const double *d_u, double *d_nz, double *d_r); // tb_mech_tet.hip
+int launch_facets_tet(tb_form *f, tb_pattern *p, const double *d_u, double *d_nz, double *d_r);
 int ensure_blockpos(tb_pattern *p);
 int launch_apply_zero(tb_pattern *pat, double *nz, double *f, const uint8_t *flags, double diag);
 int launch_meandiag(tb_pattern *pat, const double *nz, double *result);

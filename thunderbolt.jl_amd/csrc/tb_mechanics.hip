@@ -1092,7 +1092,7 @@ __global__ void k_gather_residual(const int64_t *__restrict__ ptr, const int32_t
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static HOParams make_params(const tb_form *f)
+HOParams make_params(const tb_form *f)
 {
     HOParams p{};
     const double *q = f->mat.p;
@@ -1104,9 +1104,9 @@ static HOParams make_params(const tb_form *f)
 }
 
 static bool material_is_fast_path(const tb_material &mat) { return mat.kind == TB_MATERIAL_HOLZAPFEL_OGDEN_2009 && mat.reserved == PEN_SIMPLE; }
-static bool form_is_fast_path(const tb_form *f) { return material_is_fast_path(f->mat) && f->hill == 0 && !f->prestressed; }
+bool form_is_fast_path(const tb_form *f) { return material_is_fast_path(f->mat) && f->hill == 0 && !f->prestressed; }
 
-static EnergyParams make_energy_params(const tb_form *f)
+EnergyParams make_energy_params(const tb_form *f)
 {
     EnergyParams e{};
     e.energy = f->mat.kind; e.penalty = f->mat.reserved;
@@ -1636,6 +1636,7 @@ template <class FE> static int condensed_prepass(tb_form *f, const double *d_u, 
 int launch_hyperelastic(tb_form *f, tb_pattern *p, int strategy, const double *d_u, double *d_nz, double *d_r)
 {
     tb_mesh *m = f->mesh;
+    if (m->geom_kind == TB_TET4) return launch_hyperelastic_tet(f, p, strategy, d_u, d_nz, d_r);
     int rc = reset_status(m->dev);
     if (rc) return rc;
     const bool q2 = m->field_kind == TB_HEX27;
