@@ -2,8 +2,38 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+
+// The header also compiles with a plain host C++ compiler (tests/test_tt06_derived_constants.py measures exp_b and rsqrt_b against long double
+// there): the polynomials and Newton steps are the same code, only the two hardware seeds are stood in for (below).
+#if defined(__HIP_DEVICE_COMPILE__) || (defined(__clang__) && defined(__HIP__))
+#define TB_MATH_DEVICE 1
+#else
+#define TB_MATH_DEVICE 0
+#endif
+
 namespace tb {
 
+#if TB_MATH_DEVICE
+__device__ __forceinline__ double hw_rcp(double y) { return __builtin_amdgcn_rcp(y); }
+__device__ __forceinline__ double hw_rsq(double y) { return __builtin_amdgcn_rsq(y); }
+#else
+// host stand-ins of v_rcp_f64 / v_rsq_f64: the exact value cut to 23 significant bits (relative error < 2⁻²², no better than the hardware's seeds)
+inline double hw_cut23(double v)
+{
+    uint64_t b;
+    std::memcpy(&b, &v, 8);
+    b &= ~((uint64_t(1) << 30) - 1);
+    std::memcpy(&v, &b, 8);
+    return v;
+}
+inline double hw_rcp(double y) { return hw_cut23(1.0 / y); }
+inline double hw_rsq(double y) { return hw_cut23(1.0 / std::sqrt(y)); }
+#endif
+
+#if TB_MATH_DEVICE
 // workgroup barrier that orders LDS traffic only: __syncthreads() also drains vmcnt, i.e. waits for every global store and prefetch load in flight
 __device__ __forceinline__ void lds_barrier()
 {
@@ -11,21 +41,26 @@ __device__ __forceinline__ void lds_barrier()
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
+#endif
 
 // exp for bounded arguments (|x| ≲ 700; ionic-model arguments stay within ±100): k = rint(x·log₂e), r = x − k·ln2 in two
-// pieces (|r| ≤ 0.347), degree-13 Taylor polynomial (truncation 2·10⁻¹⁸ relative), one ldexp.  ≈21 instructions against ≈40 of
-// the library routine, which spends the rest on special cases that cannot occur here; agreement with libm ≤ 2 ulp
-// (tests/test_gpu_parity.py compares whole trajectories at 1e-12).  The reaction kernels are exp-bound, not HBM-bound.
+// pieces (|r| ≤ 0.347), 1 + r + r²·P(r) with P the degree-10 polynomial through the Chebyshev points of (eʳ − 1 − r)/r² on ±0.34658 (a near-minimax
+// polynomial of degree 12 in all; relative truncation 3.3·10⁻¹⁹ with the coefficients as rounded), one ldexp.  ≈20 instructions against ≈40 of the
+// library routine, which spends the rest on special cases that cannot occur here.  Largest error against long double over 1.7·10⁶ arguments of
+// [−700, 700], 8·10⁵ of them within a few ulp to 10⁻³ of a reduction boundary (k + ½)·ln2: 0.862 ulp; the degree-13 Taylor polynomial this replaces
+// (truncation 5.7·10⁻¹⁸): 0.870 ulp on the same arguments.  Degree 11 of the same construction truncates at 1.6·10⁻¹⁷, above the Taylor form: not taken.
+// tests/test_tt06_derived_constants.py repeats the measurement with the Taylor form as its comparison copy; tests/test_gpu_parity.py compares whole
+// trajectories at 1e-12.
 __device__ __forceinline__ double exp_b(double x)
 {
     x = fmin(fmax(x, -700.0), 700.0);
     const double kf = rint(x * 1.4426950408889634);
     double r = fma(kf, -6.93147180369123816490e-01, x);
     r = fma(kf, -1.90821492927058770002e-10, r);
-    const double c[12] = {1.6059043836821613e-10, 2.08767569878681e-09, 2.505210838544172e-08, 2.755731922398589e-07, 2.7557319223985893e-06, 2.48015873015873e-05, 0.0001984126984126984, 0.001388888888888889, 0.008333333333333333, 0.041666666666666664, 0.16666666666666666, 0.5};
+    const double c[11] = {2.0914680780540263e-09, 2.5105208339987698e-08, 2.7557273657975953e-07, 2.7557255421023506e-06, 2.4801587325536023e-05, 0.00019841269874804214, 0.0013888888888883752, 0.00833333333332614, 0.04166666666666667, 0.1666666666666667, 0.5};
     double q = c[0];
 #pragma unroll
-    for (int i = 1; i < 12; ++i) q = fma(q, r, c[i]);
+    for (int i = 1; i < 11; ++i) q = fma(q, r, c[i]);
     q = fma(q, r, 1.0); // … + r
     q = fma(q, r, 1.0); // 1 + r·(…)
     return ldexp(q, (int)kf);
@@ -35,9 +70,19 @@ __device__ __forceinline__ double exp_b(double x)
 // ≈12 of the IEEE division sequence (no scaling / fix-up: gate and buffer denominators are O(1) numbers)
 __device__ __forceinline__ double rcp_b(double y)
 {
-    double r = __builtin_amdgcn_rcp(y);
+    double r = hw_rcp(y);
     r = fma(fma(-y, r, 1.0), r, r);
     r = fma(fma(-y, r, 1.0), r, r);
+    return r;
+}
+
+// 1/√y for well-scaled positive arguments: hardware reciprocal square root refined by two Newton steps r ← r + (r/2)(1 − y r²) (≤ 1 ulp,
+// tests/test_tt06_derived_constants.py), 9 instructions in place of an IEEE square root followed by an IEEE division (1.49 ulp)
+__device__ __forceinline__ double rsqrt_b(double y)
+{
+    double r = hw_rsq(y);
+    r = fma(0.5 * r, fma(-(y * r), r, 1.0), r);
+    r = fma(0.5 * r, fma(-(y * r), r, 1.0), r);
     return r;
 }
 

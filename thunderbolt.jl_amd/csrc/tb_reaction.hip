@@ -24,10 +24,48 @@ struct CellParams {
 
 template <int MODEL> struct CellModel;
 
+// What a model's right-hand side computes from its parameters alone, formed on the host at every launch and passed by value next to CellParams.  gfx950
+// has no scalar FP64 unit: inside the kernel such an expression is evaluated by all 64 lanes and its value then holds a vector register pair for the
+// whole point loop.  Empty for the models that have none.
+template <int MODEL> struct CellDerived {
+    CellDerived() = default;
+    explicit CellDerived(const CellParams &) {}
+};
+
+// TT06: the Nernst factors, the logarithms of the external concentrations, the constant factors of IKr, INaK, INaCa and ICaL and the volume / capacitance
+// ratios of the concentration equations (CellModel<TB_CELL_TT06>::rhs_rates reads these and no longer Ko, Nao, Vc, Vsr, Vss, Cm, R, T, F,
+// GKr, knak, knaca, KmK, KmNai, KmCa, Kup, minsr, nn, Bufc, Bufsr, Bufss)
+template <> struct CellDerived<TB_CELL_TT06> {
+    double RTONF, hRTONF, FoRT, F_FoRT, nnFoRT, m01FoRT; // RT/F, RT/2F, F/RT, F²/RT, γ F/RT, −0.1 F/RT
+    double logKo, logNao, logKoNao, logCao;              // log Ko, log Nao, log(Ko + pKNa Nao), log Cao
+    double e30;                                          // exp(−30 F/RT)
+    double gkr, knak_ko, knaca_s, Nao3;                  // GKr √(Ko/5.4), knak Ko/(Ko + KmK), knaca/(KmNai³ + Nao³)/(KmCa + Cao), Nao³
+    double dsr, Kup2, BKc, BKsr, BKss;                   // maxsr − minsr, Kup², Bufc Kbufc, Bufsr Kbufsr, Bufss Kbufss
+    double Vsr_Vc, Vsr_Vss, Vc_Vss, Cm_VcF, Cm_2VcF, Cm_2VssF;
+    CellDerived() = default;
+    explicit CellDerived(const CellParams &P)
+    {
+        const double *p = P.p;
+        const double GKr = p[2], knak = p[10], knaca = p[11], Ko = p[12], Cao = p[13], Nao = p[14], Vc = p[15], Vsr = p[16], Vss = p[17], Bufc = p[18],
+                     Kbufc = p[19], Bufsr = p[20], Kbufsr = p[21], Bufss = p[22], Kbufss = p[23], Kup = p[25], maxsr = p[32], minsr = p[33], Cm = p[36],
+                     pKNa = p[37], KmK = p[38], KmNai = p[40], KmCa = p[41], nn = p[43], R = p[45], T = p[46], F = p[47];
+        RTONF = R * T / F; hRTONF = 0.5 * RTONF; FoRT = F / (R * T); F_FoRT = F * FoRT; nnFoRT = nn * FoRT; m01FoRT = -0.1 * FoRT;
+        logKo = log(Ko); logNao = log(Nao); logKoNao = log(Ko + pKNa * Nao); logCao = log(Cao);
+        e30 = exp(-30.0 * FoRT);
+        gkr = GKr * sqrt(Ko * (1.0 / 5.4));
+        knak_ko = knak * (Ko / (Ko + KmK));
+        knaca_s = knaca * (1.0 / (KmNai * KmNai * KmNai + Nao * Nao * Nao)) * (1.0 / (KmCa + Cao));
+        Nao3 = Nao * Nao * Nao;
+        dsr = maxsr - minsr; Kup2 = Kup * Kup; BKc = Bufc * Kbufc; BKsr = Bufsr * Kbufsr; BKss = Bufss * Kbufss;
+        Vsr_Vc = Vsr / Vc; Vsr_Vss = Vsr / Vss; Vc_Vss = Vc / Vss;
+        Cm_VcF = Cm / (Vc * F); Cm_2VcF = Cm / (2.0 * Vc * F); Cm_2VssF = Cm / (2.0 * Vss * F);
+    }
+};
+
 template <> struct CellModel<TB_CELL_FHN> {
     static constexpr int NS = 2, PHI = 0;
     static constexpr bool HAS_GATES = false;
-    __device__ __forceinline__ static void rhs(const CellParams &P, const double (&u)[NS], double, double (&du)[NS])
+    __device__ __forceinline__ static void rhs(const CellParams &P, const CellDerived<TB_CELL_FHN> &, const double (&u)[NS], double, double (&du)[NS])
     {
         const double a = P.p[0], b = P.p[1], c = P.p[2], d = P.p[3], e = P.p[4], f = P.p[5];
         const double phi = u[0], s = u[1];
@@ -39,7 +77,7 @@ template <> struct CellModel<TB_CELL_FHN> {
 template <> struct CellModel<TB_CELL_ALIEV_PANFILOV> {
     static constexpr int NS = 2, PHI = 1;
     static constexpr bool HAS_GATES = false; // state order (s, φₘ)
-    __device__ __forceinline__ static void rhs(const CellParams &P, const double (&u)[NS], double, double (&du)[NS])
+    __device__ __forceinline__ static void rhs(const CellParams &P, const CellDerived<TB_CELL_ALIEV_PANFILOV> &, const double (&u)[NS], double, double (&du)[NS])
     {
         const double ct = P.p[0], k = P.p[1], a = P.p[2], e0 = P.p[3], mu1 = P.p[4], mu2 = P.p[5];
         const double phi = u[1], s = u[0];
@@ -61,13 +99,14 @@ template <> struct CellModel<TB_CELL_PCG2019> {
     {
         return rcp_b(1.0 + exp_b(sign * (phi - E) * ik));
     }
-    __device__ __forceinline__ static void rhs(const CellParams &P, const double (&u)[NS], double t, double (&du)[NS])
+    __device__ __forceinline__ static void rhs(const CellParams &P, const CellDerived<TB_CELL_PCG2019> &D, const double (&u)[NS], double t, double (&du)[NS])
     {
         double rate[NS];
-        rhs_rates(P, u, t, du, rate);
+        rhs_rates(P, D, u, t, du, rate);
     }
     // rate[k] = 1/τ of gate k (0 for φₘ): the Rush–Larsen step advances gates with the exact solution of their linear ODE for frozen φₘ
-    __device__ __forceinline__ static void rhs_rates(const CellParams &P, const double (&u)[NS], double, double (&du)[NS], double (&rate)[NS])
+    __device__ __forceinline__ static void rhs_rates(const CellParams &P, const CellDerived<TB_CELL_PCG2019> &, const double (&u)[NS], double, double (&du)[NS],
+                                                     double (&rate)[NS])
     {
         const double *p = P.p;
         const double phi = u[0], h = u[1], m = u[2], f = u[3], s = u[4], xs = u[5], xr = u[6];
@@ -103,7 +142,8 @@ template <> struct CellModel<TB_CELL_PCG2019> {
 template <> struct CellModel<TB_CELL_FHN_HETEROGENEOUS> {
     static constexpr int NS = 2, PHI = 0;
     static constexpr bool HAS_GATES = false, USES_X = true;
-    __device__ __forceinline__ static void rhs_x(const CellParams &P, const double (&u)[NS], const float (&x)[3], double, double (&du)[NS])
+    __device__ __forceinline__ static void rhs_x(const CellParams &P, const CellDerived<TB_CELL_FHN_HETEROGENEOUS> &, const double (&u)[NS], const float (&x)[3], double,
+                                                 double (&du)[NS])
     {
         const double a = P.p[0], b = P.p[1], c = P.p[2], d = P.p[3];
         const double e = P.p[4] + P.p[5] * (double)x[0] + P.p[6] * (double)x[1] + P.p[7] * (double)x[2];
@@ -130,29 +170,29 @@ template <> struct CellModel<TB_CELL_TT06> {
     static constexpr bool HAS_GATES = true;
     // rate[k] = 1/τ_k for the Hodgkin–Huxley-type gates (dy/dt = (y∞ − y)/τ, y∞ and τ functions of V / Ca only), 0 otherwise:
     // what a Rush–Larsen step needs besides du (see k_reaction_rl)
-    __device__ __forceinline__ static void rhs(const CellParams &P, const double (&u)[NS], double t, double (&du)[NS])
+    __device__ __forceinline__ static void rhs(const CellParams &P, const CellDerived<TB_CELL_TT06> &D, const double (&u)[NS], double t, double (&du)[NS])
     {
         double rate[NS];
-        rhs_rates(P, u, t, du, rate);
+        rhs_rates(P, D, u, t, du, rate);
     }
-    __device__ __forceinline__ static void rhs_rates(const CellParams &P, const double (&u)[NS], double, double (&du)[NS], double (&rate)[NS])
+    // Everything that depends on the parameters alone comes in D (formed on the host, CellDerived<TB_CELL_TT06>): no logarithm, square root, exponential or
+    // IEEE division of parameters is left in here, and the volume / capacitance quotients of the concentration equations are multiplications
+    __device__ __forceinline__ static void rhs_rates(const CellParams &P, const CellDerived<TB_CELL_TT06> &D, const double (&u)[NS], double, double (&du)[NS],
+                                                     double (&rate)[NS])
     {
 #pragma unroll
         for (int k = 0; k < NS; ++k) rate[k] = 0.0;
         const double *p = P.p;
-        const double GNa = p[0], GK1 = p[1], GKr = p[2], GKs = p[3], Gto = p[4], GCaL = p[5], GbNa = p[6], GbCa = p[7], GpCa = p[8],
-                     GpK = p[9], knak = p[10], knaca = p[11], Ko = p[12], Cao = p[13], Nao = p[14], Vc = p[15], Vsr = p[16], Vss = p[17],
-                     Bufc = p[18], Kbufc = p[19], Bufsr = p[20], Kbufsr = p[21], Bufss = p[22], Kbufss = p[23], Vmaxup = p[24], Kup = p[25],
-                     Vrel = p[26], k1p = p[27], k2p = p[28], k3 = p[29], k4 = p[30], EC = p[31], maxsr = p[32], minsr = p[33],
-                     Vleak = p[34], Vxfer = p[35], Cm = p[36], pKNa = p[37], KmK = p[38], KmNa = p[39], KmNai = p[40], KmCa = p[41],
-                     ksat = p[42], nn = p[43], KpCa = p[44], R = p[45], T = p[46], F = p[47];
+        const double GNa = p[0], GK1 = p[1], GKs = p[3], Gto = p[4], GCaL = p[5], GbNa = p[6], GbCa = p[7], GpCa = p[8], GpK = p[9], Cao = p[13],
+                     Kbufc = p[19], Kbufsr = p[21], Kbufss = p[23], Vmaxup = p[24], Vrel = p[26], k1p = p[27], k2p = p[28], k3 = p[29], k4 = p[30],
+                     EC = p[31], maxsr = p[32], Vleak = p[34], Vxfer = p[35], pKNa = p[37], KmNa = p[39], ksat = p[42], KpCa = p[44];
         const double V = u[0], Cai = u[1], CaSR = u[2], CaSS = u[3], Nai = u[4], Ki = u[5], m = u[6], h = u[7], j = u[8], xr1 = u[9],
                      xr2 = u[10], xs = u[11], r = u[12], s = u[13], d = u[14], f = u[15], f2 = u[16], fCass = u[17], RR = u[18];
-        const double RTONF = R * T / F, FoRT = F / (R * T);
+        const double RTONF = D.RTONF, FoRT = D.FoRT;
         // reversal potentials
-        // log(a/b) = log a − log b: the numerators are parameters (their logarithms are loop invariants), the state-dependent ones take the bounded form
-        const double Ek = RTONF * (log(Ko) - log_b(Ki)), Ena = RTONF * (log(Nao) - log_b(Nai));
-        const double Eks = RTONF * (log(Ko + pKNa * Nao) - log_b(Ki + pKNa * Nai)), Eca = 0.5 * RTONF * (log(Cao) - log_b(Cai));
+        // log(a/b) = log a − log b: the numerators are parameters (their logarithms come in D), the state-dependent ones take the bounded form
+        const double Ek = RTONF * (D.logKo - log_b(Ki)), Ena = RTONF * (D.logNao - log_b(Nai));
+        const double Eks = RTONF * (D.logKoNao - log_b(Ki + pKNa * Nai)), Eca = D.hRTONF * (D.logCao - log_b(Cai));
         // shared exponentials of V (p = exp_b(V/k), q = 1/p)
         const double p5 = exp_b(V * (1.0 / 5.0)), q5 = rcp_b(p5);
         const double p10 = exp_b(V * (1.0 / 10.0)), q10 = rcp_b(p10);
@@ -166,36 +206,35 @@ template <> struct CellModel<TB_CELL_TT06> {
         const double eh = exp_b(-0.5 * vk);
         const double Bk1 = (3.0 * exp_b(0.0002 * (vk + 100.0)) + exp_b(0.1 * (vk - 10.0))) * sgm(eh);
         const double INa = GNa * m * m * m * h * j * (V - Ena);
-        const double e2 = w * w * exp_b(-30.0 * FoRT); // exp_b(2 (V − 15) F/RT)
-        const double ICaL = GCaL * d * f * f2 * fCass * 4.0 * (V - 15.0) * (F * FoRT) * (0.25 * e2 * CaSS - Cao) * rcp_b(e2 - 1.0);
+        const double e2 = w * w * D.e30; // exp_b(2 (V − 15) F/RT)
+        const double ICaL = GCaL * d * f * f2 * fCass * 4.0 * (V - 15.0) * D.F_FoRT * (0.25 * e2 * CaSS - Cao) * rcp_b(e2 - 1.0);
         const double Ito = Gto * r * s * vk;
-        const double IKr = GKr * sqrt(Ko * (1.0 / 5.4)) * xr1 * xr2 * vk;
+        const double IKr = D.gkr * xr1 * xr2 * vk;
         const double IKs = GKs * xs * xs * (V - Eks);
         const double IK1 = GK1 * (Ak1 * rcp_b(Ak1 + Bk1)) * vk;
-        const double en = exp_b(nn * V * FoRT), en1 = en * iw; // exp_b((γ − 1) V F/RT)
-        const double INaCa = knaca * (1.0 / (KmNai * KmNai * KmNai + Nao * Nao * Nao)) * (1.0 / (KmCa + Cao)) * rcp_b(1.0 + ksat * en1) *
-                             (en * Nai * Nai * Nai * Cao - en1 * Nao * Nao * Nao * Cai * 2.5);
-        const double INaK = knak * (Ko / (Ko + KmK)) * (Nai * rcp_b(Nai + KmNa)) * rcp_b(1.0 + 0.1245 * exp_b(-0.1 * V * FoRT) + 0.0353 * iw);
+        const double en = exp_b(V * D.nnFoRT), en1 = en * iw; // exp_b((γ − 1) V F/RT)
+        const double INaCa = D.knaca_s * rcp_b(1.0 + ksat * en1) * (en * Nai * Nai * Nai * Cao - en1 * D.Nao3 * Cai * 2.5);
+        const double INaK = D.knak_ko * (Nai * rcp_b(Nai + KmNa)) * rcp_b(1.0 + 0.1245 * exp_b(V * D.m01FoRT) + 0.0353 * iw);
         const double IpCa = GpCa * Cai * rcp_b(KpCa + Cai);
         const double IpK = GpK * sgm(exp_b((25.0 - V) * (1.0 / 5.98))) * vk;
         const double IbNa = GbNa * (V - Ena), IbCa = GbCa * (V - Eca);
         du[0] = -(IKr + IKs + IK1 + Ito + INa + IbNa + ICaL + IbCa + INaK + INaCa + IpCa + IpK);
         // calcium handling
         const double ecs = EC * rcp_b(CaSR);
-        const double kCaSR = maxsr - (maxsr - minsr) * rcp_b(1.0 + ecs * ecs);
+        const double kCaSR = maxsr - D.dsr * rcp_b(1.0 + ecs * ecs);
         const double k1 = k1p * rcp_b(kCaSR), k2 = k2p * kCaSR;
         du[18] = k4 * (1.0 - RR) - k2 * CaSS * RR;
         const double O = k1 * CaSS * CaSS * RR * rcp_b(k3 + k1 * CaSS * CaSS);
         const double Irel = Vrel * O * (CaSR - CaSS), Ileak = Vleak * (CaSR - Cai);
         // 1/(1 + a/x²) = x²/(x² + a): one reciprocal each
-        const double Iup = Vmaxup * (Cai * Cai) * rcp_b(Cai * Cai + Kup * Kup), Ixfer = Vxfer * (CaSS - Cai);
+        const double Iup = Vmaxup * (Cai * Cai) * rcp_b(Cai * Cai + D.Kup2), Ixfer = Vxfer * (CaSS - Cai);
         const double sc = (Cai + Kbufc) * (Cai + Kbufc), ssr = (CaSR + Kbufsr) * (CaSR + Kbufsr), sss = (CaSS + Kbufss) * (CaSS + Kbufss);
-        const double bc = sc * rcp_b(sc + Bufc * Kbufc), bsr = ssr * rcp_b(ssr + Bufsr * Kbufsr), bss = sss * rcp_b(sss + Bufss * Kbufss);
-        du[1] = bc * ((Ileak - Iup) * Vsr / Vc + Ixfer - (IbCa + IpCa - 2.0 * INaCa) * Cm / (2.0 * Vc * F));
+        const double bc = sc * rcp_b(sc + D.BKc), bsr = ssr * rcp_b(ssr + D.BKsr), bss = sss * rcp_b(sss + D.BKss);
+        du[1] = bc * ((Ileak - Iup) * D.Vsr_Vc + Ixfer - (IbCa + IpCa - 2.0 * INaCa) * D.Cm_2VcF);
         du[2] = bsr * (Iup - Irel - Ileak);
-        du[3] = bss * (-ICaL * Cm / (2.0 * Vss * F) + Irel * Vsr / Vss - Ixfer * Vc / Vss);
-        du[4] = -(INa + IbNa + 3.0 * INaK + 3.0 * INaCa) * Cm / (Vc * F);
-        du[5] = -(IK1 + Ito + IKr + IKs - 2.0 * INaK + IpK) * Cm / (Vc * F);
+        du[3] = bss * (-ICaL * D.Cm_2VssF + Irel * D.Vsr_Vss - Ixfer * D.Vc_Vss);
+        du[4] = -(INa + IbNa + 3.0 * INaK + 3.0 * INaCa) * D.Cm_VcF;
+        du[5] = -(IK1 + Ito + IKr + IKs - 2.0 * INaK + IpK) * D.Cm_VcF;
         // gates: dy/dt = (y∞ − y)/τ.  Constants below are exp_b(c/k) of the published arguments (V + c)/k, folded by the compiler.
         const double AM = sgm(q5 * 6.14421235332821e-06 /* exp_b(-60.0 * (1.0 / 5.0)) */);
         const double BM = 0.1 * sgm(p5 * 1096.6331584284585 /* exp_b(35.0 * (1.0 / 5.0)) */) + 0.1 * sgm(exp_b((V - 50.0) * (1.0 / 200.0)));
@@ -221,7 +260,7 @@ template <> struct CellModel<TB_CELL_TT06> {
         du[9] = (sgm(q7 * 0.02437284407327961 /* exp_b(-26.0 * (1.0 / 7.0)) */) - xr1) * rate[9];
         rate[10] = rcp_b((3.0 * sgm(q20 * 0.049787068367863944 /* exp_b(-3.0) */)) * (1.12 * sgm(p20 * 0.049787068367863944 /* exp_b(-3.0) */)));
         du[10] = (sgm(exp_b((V + 88.0) * (1.0 / 24.0))) - xr2) * rate[10];
-        rate[11] = rcp_b((1400.0 / sqrt(1.0 + q6 * 2.3009758908928246 /* exp_b(5.0 * (1.0 / 6.0)) */)) * sgm(exp_b((V - 35.0) * (1.0 / 15.0))) + 80.0);
+        rate[11] = rcp_b((1400.0 * rsqrt_b(1.0 + q6 * 2.3009758908928246 /* exp_b(5.0 * (1.0 / 6.0)) */)) * sgm(exp_b((V - 35.0) * (1.0 / 15.0))) + 80.0);
         du[11] = (sgm(exp_b((-5.0 - V) * (1.0 / 14.0))) - xs) * rate[11];
         rate[12] = rcp_b(9.5 * exp_b(-(V + 40.0) * (V + 40.0) * (1.0 / 1800.0)) + 0.8);
         du[12] = (sgm(q6 * 28.031624894526125 /* exp_b(20.0 * (1.0 / 6.0)) */) - r) * rate[12];
@@ -251,10 +290,10 @@ template <> struct CellModel<TB_CELL_ORD11> {
     static constexpr int NS = 41, PHI = 0;
     static constexpr bool HAS_GATES = true;
     __device__ __forceinline__ static double sg(double x) { return rcp_b(1.0 + exp_b(x)); } // 1/(1 + e^x)
-    __device__ __forceinline__ static void rhs(const CellParams &P, const double (&u)[NS], double t, double (&du)[NS])
+    __device__ __forceinline__ static void rhs(const CellParams &P, const CellDerived<TB_CELL_ORD11> &D, const double (&u)[NS], double t, double (&du)[NS])
     {
         double rate[NS];
-        rhs_rates(P, u, t, du, rate);
+        rhs_rates(P, D, u, t, du, rate);
     }
     // The right-hand side in two parts, so that a kernel can retire the 13 non-gate states before it touches the dynamics of the 28 gates (below):
     // currents(): everything that reads gate VALUES — the currents, fluxes and the rates of V, the concentrations, nca, Jrel and CaMK (du[0…8], du[30],
@@ -460,7 +499,8 @@ template <> struct CellModel<TB_CELL_ORD11> {
         emit(33, xrss, rcp_b(txrf)); emit(34, xrss, rcp_b(txrs)); emit(35, xs1ss, rcp_b(txs1)); emit(36, xs1ss, txs2_r); emit(37, xk1ss, txk1_r);
     }
     __device__ __forceinline__ static bool is_gate(int k) { return (k >= 9 && k <= 29) || (k >= 31 && k <= 37); }
-    __device__ __forceinline__ static void rhs_rates(const CellParams &P, const double (&u)[NS], double, double (&du)[NS], double (&rate)[NS])
+    __device__ __forceinline__ static void rhs_rates(const CellParams &P, const CellDerived<TB_CELL_ORD11> &, const double (&u)[NS], double, double (&du)[NS],
+                                                     double (&rate)[NS])
     {
 #pragma unroll
         for (int k = 0; k < NS; ++k) rate[k] = 0.0;
@@ -474,18 +514,18 @@ template <class M> struct uses_x<M, std::enable_if_t<M::USES_X>> : std::true_typ
 
 // cell_rhs!(du, u, x, t, p) (partitioned_solver.jl:88-92): x = the point's coordinate (Vec{sdim, Float32}, coordinate_systems.jl:43-49) for the
 // models that read it, nothing for the others
-template <class M>
-__device__ __forceinline__ void cell_rhs(const CellParams &P, const double (&u)[M::NS], const float (&x)[3], double t, double (&du)[M::NS])
+template <class M, class DV>
+__device__ __forceinline__ void cell_rhs(const CellParams &P, const DV &D, const double (&u)[M::NS], const float (&x)[3], double t, double (&du)[M::NS])
 {
-    if constexpr (uses_x<M>::value) M::rhs_x(P, u, x, t, du);
-    else M::rhs(P, u, t, du);
+    if constexpr (uses_x<M>::value) M::rhs_x(P, D, u, x, t, du);
+    else M::rhs(P, D, u, t, du);
 }
 
 // TS: storage type of the states (double, or float for the Float32 value type of the boundary: states read and rounded once per call, arithmetic in
 // Float64 — the same result as converting, stepping and converting back, in one pass over half the bytes)
 template <int MODEL, int LAYOUT, bool WRITE_DU, class TS = double>
 __global__ void __launch_bounds__(256)
-k_reaction(CellParams P, TS *__restrict__ u, TS *__restrict__ du_out, int64_t n, double t, double dt, int substeps,
+k_reaction(CellParams P, CellDerived<MODEL> D, TS *__restrict__ u, TS *__restrict__ du_out, int64_t n, double t, double dt, int substeps,
            double threshold, unsigned long long *__restrict__ rmax_key, const float *__restrict__ xs, int sdim, const double *__restrict__ tslot)
 {
     if (tslot) t = tslot[0]; // replayed from a graph: the time of this launch sits on the device (tb_graph.hip)
@@ -501,7 +541,7 @@ k_reaction(CellParams P, TS *__restrict__ u, TS *__restrict__ du_out, int64_t n,
         if constexpr (uses_x<M>::value) {
             if (xs) for (int d = 0; d < sdim; ++d) xp[d] = xs[i * sdim + d];
         }
-        cell_rhs<M>(P, ul, xp, t, dul);
+        cell_rhs<M>(P, D, ul, xp, t, dul);
         if (substeps <= 1 || fabs(dul[M::PHI]) < threshold) {
 #pragma unroll
             for (int j = 0; j < NS; ++j) ul[j] += dt * dul[j];
@@ -510,7 +550,7 @@ k_reaction(CellParams P, TS *__restrict__ u, TS *__restrict__ du_out, int64_t n,
 #pragma unroll
             for (int j = 0; j < NS; ++j) ul[j] += dts * dul[j];
             for (int s = 2; s <= substeps; ++s) {
-                cell_rhs<M>(P, ul, xp, t + (s - 1) * dts, dul);
+                cell_rhs<M>(P, D, ul, xp, t + (s - 1) * dts, dul);
 #pragma unroll
                 for (int j = 0; j < NS; ++j) ul[j] += dts * dul[j];
             }
@@ -555,7 +595,7 @@ __device__ __forceinline__ double expm1_b(double z)
 // in one evaluation instead of twenty forward-Euler sub-steps.
 template <int MODEL, int LAYOUT>
 __global__ void __launch_bounds__(256)
-k_reaction_rl(CellParams P, double *__restrict__ u, int64_t n, double t, double dt, const double *__restrict__ tslot)
+k_reaction_rl(CellParams P, CellDerived<MODEL> D, double *__restrict__ u, int64_t n, double t, double dt, const double *__restrict__ tslot)
 {
     if (tslot) t = tslot[0];
     using M = CellModel<MODEL>;
@@ -565,7 +605,7 @@ k_reaction_rl(CellParams P, double *__restrict__ u, int64_t n, double t, double 
         double ul[NS], dul[NS], rate[NS];
 #pragma unroll
         for (int j = 0; j < NS; ++j) ul[j] = LAYOUT == TB_LAYOUT_SOA ? u[i + j * n] : u[i * NS + j];
-        M::rhs_rates(P, ul, t, dul, rate);
+        M::rhs_rates(P, D, ul, t, dul, rate);
 #pragma unroll
         for (int j = 0; j < NS; ++j) {
             const double h = rate[j] != 0.0 ? -expm1_b(-dt * rate[j]) * rcp_b(rate[j]) : dt;
@@ -588,8 +628,10 @@ int launch_reaction_rl(tb_device *dev, int model, const double *params, int n_pa
     if (nb > cap) nb = (nb + (nb + cap - 1) / cap - 1) / ((nb + cap - 1) / cap); // balanced: every thread ⌈nb / cap⌉ points
     if (n == 0) return TB_OK;
     const double *ts = dev->capturing ? (dev->tslot_used = true, dev->d_tslot) : nullptr;
-#define TB_RL(MODEL) do { if (layout == TB_LAYOUT_SOA) hipLaunchKernelGGL((k_reaction_rl<MODEL, TB_LAYOUT_SOA>), dim3((unsigned)nb), dim3(256), 0, dev->stream, P, d_u, n, t, dt, ts); \
-                          else hipLaunchKernelGGL((k_reaction_rl<MODEL, TB_LAYOUT_AOS>), dim3((unsigned)nb), dim3(256), 0, dev->stream, P, d_u, n, t, dt, ts); } while (0)
+    // (the derived block is formed here, from the parameters of THIS call: nothing is kept between launches)
+#define TB_RL(MODEL) do { const CellDerived<MODEL> D(P); \
+                          if (layout == TB_LAYOUT_SOA) hipLaunchKernelGGL((k_reaction_rl<MODEL, TB_LAYOUT_SOA>), dim3((unsigned)nb), dim3(256), 0, dev->stream, P, D, d_u, n, t, dt, ts); \
+                          else hipLaunchKernelGGL((k_reaction_rl<MODEL, TB_LAYOUT_AOS>), dim3((unsigned)nb), dim3(256), 0, dev->stream, P, D, d_u, n, t, dt, ts); } while (0)
     if (model == TB_CELL_TT06) TB_RL(TB_CELL_TT06); else if (model == TB_CELL_ORD11) TB_RL(TB_CELL_ORD11); else TB_RL(TB_CELL_PCG2019);
 #undef TB_RL
     TB_HIP(hipGetLastError());
@@ -601,6 +643,7 @@ static int run(tb_device *dev, const CellParams &P, TS *u, TS *du, int64_t n, in
                double thr, unsigned long long *rmax_key, const float *xs, int sdim)
 {
     const int bs = 256;
+    const CellDerived<MODEL> D(P); // from the parameters of THIS call, at every launch: a caller who changes a parameter between two calls gets its values
     // Grid: a multiple of what is resident (`occ` workgroups per CU: 2 for the 19-state model at 243 registers, 8 for the two-state ones), every thread the
     // same number of points.  Two generations of resident workgroups for large arrays, ONE for small ones (≤ 12 generations of single-point workgroups: the
     // 27-layer slab of a strong-scaling run) — measured at steady clocks, TT06 (profiles/r05_v2/ab_reaction_grid.log): 216³ 0.715 ms against 0.721 at
@@ -618,7 +661,7 @@ static int run(tb_device *dev, const CellParams &P, TS *u, TS *du, int64_t n, in
         const int64_t resident = (int64_t)dev->n_cu * occ;
         const int64_t cap = per_cu_env > 0 ? (int64_t)dev->n_cu * per_cu_env : per_cu_env == 0 ? nb : (nb <= 12 * resident ? resident : 2 * resident);
         if (nb > cap) nb = (nb + (nb + cap - 1) / cap - 1) / ((nb + cap - 1) / cap); // every thread the same number of points (⌈nb / cap⌉ each)
-        hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(bs), 0, dev->stream, P, u, du, n, t, dt, substeps, thr, rmax_key, xs, sdim,
+        hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(bs), 0, dev->stream, P, D, u, du, n, t, dt, substeps, thr, rmax_key, xs, sdim,
                            dev->capturing ? (dev->tslot_used = true, (const double *)dev->d_tslot) : (const double *)nullptr);
         return TB_OK;
     };
