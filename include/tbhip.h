@@ -89,6 +89,7 @@ enum {
     TB_FORM_DIFFUSION = 1, /* Kₑ[i,j] -= ∇Nⱼ·D·∇Nᵢ dΩ       src/modeling/core/diffusion.jl:28-50  */
     TB_FORM_SOURCE = 2,    /* bₑ[j]  += f(x_q,t) Nⱼ dΩ      src/modeling/core/analytical_coefficient.jl:80-101 */
     TB_FORM_FACET = 4,       /* weak boundary conditions on hexahedron / tetrahedron facets   src/modeling/core/weak_boundary_conditions.jl */
+    TB_FORM_CHAMBER = 5,     /* 3D–0D chamber coupling on hexahedron facets (tb_chamber_form_create)   src/modeling/coupler/fsi.jl:118-185 */
     TB_FORM_HYPERELASTIC = 3 /* rₑ[i] += ∇δuᵢ⊡P dΩ, Kₑ[i,j] += (∇δuᵢ⊡𝔸)⊡∇δuⱼ dΩ   src/modeling/solid/elements.jl:177-313 */
 };
 
@@ -173,9 +174,10 @@ const char *tb_version(void);
  * tb_cgd_iteration, tb_last_kernel_name.  6: tb_host_locality_permutation; calls that wait for the device refuse inside an open capture
  * (TB_ERR_BAD_ARG) instead of invalidating it.  7: tb_cg1_update / tb_cg1_fold / tb_cg1_iteration (single-reduction CG, seven-double scalar block).
  * 8: TB_TET10, hyperelastic and facet forms on tetrahedra (TB_TET4 / TB_TET10 vector fields), tb_host_generate_grid_tet.
+ * 9: tb_chamber_form_create / tb_chamber_assemble (3D–0D chamber coupling).
  * A host binding compares tb_abi_revision() with the
  * TB_ABI_REVISION it was written against and refuses to run on a mismatch (julia/ThunderboltHIPBackend.jl does, in __init__) */
-#define TB_ABI_REVISION 8
+#define TB_ABI_REVISION 9
 int tb_abi_revision(void);
 
 /* ------------------------------------------------------------------ device (AbstractGPUDevice, src/devices.jl:3-4;
@@ -363,6 +365,28 @@ int tb_facet_form_create(tb_mesh *mesh, int bc_kind, double param, int facet_qpo
 int tb_facet_form_set_param(tb_form *form, double param);
 int tb_facet_assemble(tb_form *form, tb_pattern *pat, const double *d_u, double t, double *d_nzval, double *d_r);
 int tb_host_material_eval(const tb_material *material, const double *F, double *psi, double *P, double *A);
+
+/* 3D–0D chamber coupling of Regazzoni et al. 2022: the chamber pressure p is an unknown tied to the cavity volume by a Lagrange-multiplier row
+ * (Pressure3D0DVolumeCouplerIntegrator, src/modeling/coupler/fsi.jl:118-185).  Volume integrands V(x, d, F, n₀):
+ *   TB_VOLUME_RSAFDQ2022      −J ((h ⊗ h)(x + d − b)) · F⁻ᵀ n₀   (RSAFDQ2022SurrogateVolume, src/modeling/rsafdq2022.jl:75-85)
+ *   TB_VOLUME_HIRSCHVOGEL2017 −J (x + d) · F⁻ᵀ n₀                (Hirschvogel2017SurrogateVolume, fsi.jl:53-58) */
+enum { TB_VOLUME_RSAFDQ2022 = 0, TB_VOLUME_HIRSCHVOGEL2017 = 1 };
+/* fsi.jl:87-110 (setup_boundary_cache) and rsafdq2022.jl:22-63 (compute_chamber_volume, which integrates with facet_qpoints = 2·order).
+ * `facets`: n_facets pairs (cell, local facet) as for tb_facet_form_create; facet_qpoints 1…3 Gauss points per facet direction, 0 = the interpolation
+ * order.  method_params: h[3], b[3] of TB_VOLUME_RSAFDQ2022 (NULL: h = (0,1,0), b = (0,0,−0.1), the reference's defaults); ignored for
+ * TB_VOLUME_HIRSCHVOGEL2017.  Three-component TB_HEX8 / TB_HEX27 fields on hexahedra; tetrahedral meshes return TB_ERR_UNSUPPORTED.
+ * Destroyed with tb_form_destroy. */
+int tb_chamber_form_create(tb_mesh *mesh, int volume_method, const double *method_params, int facet_qpoints, const int32_t *facets, int64_t n_facets,
+                           int index_base, tb_form **out);
+/* fsi.jl:118-185 (assemble_facet!) for all facets of the form at displacement d_u and chamber pressure p.  ADDS to every non-NULL output, like
+ * tb_facet_assemble (the caller zeroes col, row and volume):
+ *   d_nzval  += p (δJ cofF + J δcofF) n₀ · δuᵢ dΓ   (:150-163; needs `pat`)      d_r[i]   += p J (F⁻ᵀ n₀) · δuᵢ dΓ          (:152)
+ *   d_col[i] += J (F⁻ᵀ n₀) · δuᵢ dΓ   (:164, the J_dp block, n_dofs)             d_row[j] += (∂V/∂d · δuⱼ + ∂V/∂F : ∇δuⱼ) dΓ   (:173-181, J_pd, n_dofs)
+ *   d_volume[0] += Σ V dΓ   (:171; one device double)
+ * The volume stays on the device: the call does not read it.  det F ≤ 0 at a facet point or a non-positive geometry Jacobian returns TB_ERR_NEG_DETJ.
+ * Several chambers, or several facet sets of one chamber, are several calls. */
+int tb_chamber_assemble(tb_form *form, tb_pattern *pat, const double *d_u, double p, double *d_nzval, double *d_r, double *d_col, double *d_row,
+                        double *d_volume);
 
 /* ------------------------------------------------------------------ pointwise sarcomere dynamics
  * Sarcomere models with internal state (src/modeling/solid/contraction.jl:337-632).  TB_SARCOMERE_RDQ20MF: 20 states per point

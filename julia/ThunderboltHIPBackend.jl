@@ -19,7 +19,7 @@ import Thunderbolt: AbstractGPUDevice, AbstractAssemblyStrategy, AbstractSolver,
 const libtbhip = get(ENV, "TBHIP_LIBRARY", "libtbhip.so")
 
 # revision of include/tbhip.h these ccalls were written against (TB_ABI_REVISION); a library of another revision reads / writes other buffer sizes
-const TB_ABI_REVISION = 8
+const TB_ABI_REVISION = 9
 const TB_ERR_UNSUPPORTED = Cint(-5) # include/tbhip.h
 function __init__()
     have = ccall((:tb_abi_revision, libtbhip), Cint, ())
@@ -721,6 +721,25 @@ facet_set_param!(form::Ptr{Cvoid}, param::Real) = check(ccall((:tb_facet_form_se
 facet_set_field!(form::Ptr{Cvoid}, field::Vector{Float64}) = check(ccall((:tb_facet_form_set_field, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), form, field, length(field)))
 facet_assemble!(form::Ptr{Cvoid}, A::HIPSparseMatrixCSR{Float64}, u::HIPVector{Float64}, r::HIPVector{Float64}, t::Real) =
     check(ccall((:tb_facet_assemble, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Float64}), form, A.ddh.pattern, u.ptr, t, A.nzval.ptr, r.ptr))
+# 3D–0D chamber coupling (src/modeling/coupler/fsi.jl:118-185, src/modeling/rsafdq2022.jl:22-85): one form per chamber surface; chamber_assemble! ADDS the
+# follower-load tangent / residual at pressure p, the J_dp column, the J_pd row and the chamber volume (one device double).  Every output is optional:
+# `nothing` passes C_NULL and the library skips it (chamber_assemble!(form, nothing, u, 0.0; volume = v) is compute_chamber_volume)
+const TB_VOLUME_RSAFDQ2022 = Cint(0)
+const TB_VOLUME_HIRSCHVOGEL2017 = Cint(1)
+function chamber_form(ddh::DeviceDofHandler, volume_method::Integer, facets::Vector{Int32}; params::Union{Nothing, Vector{Float64}} = nothing, facet_qpoints = 0)
+    form = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:tb_chamber_form_create, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Cint, Ptr{Int32}, Int64, Cint, Ref{Ptr{Cvoid}}),
+        ddh.mesh, volume_method, params === nothing ? C_NULL : params, facet_qpoints, facets, length(facets) ÷ 2, 1, form))
+    return form[]
+end
+const OptionalHIPVector = Union{Nothing, HIPVector{Float64}}
+device_pointer_or_null(v::OptionalHIPVector) = v === nothing ? Ptr{Float64}(C_NULL) : v.ptr
+function chamber_assemble!(form::Ptr{Cvoid}, A::Union{Nothing, HIPSparseMatrixCSR{Float64}}, u::HIPVector{Float64}, p::Real;
+        r::OptionalHIPVector = nothing, col::OptionalHIPVector = nothing, row::OptionalHIPVector = nothing, volume::OptionalHIPVector = nothing)
+    check(ccall((:tb_chamber_assemble, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        form, A === nothing ? C_NULL : A.ddh.pattern, u.ptr, p, A === nothing ? Ptr{Float64}(C_NULL) : A.nzval.ptr,
+        device_pointer_or_null(r), device_pointer_or_null(col), device_pointer_or_null(row), device_pointer_or_null(volume)))
+end
 # sarcomere models (RDQ20-MF …): explicit and implicit pointwise steps (src/modeling/solid/materials.jl:1403-1640 condenses them per quadrature point)
 function sarcomere_model_info(model::Integer)
     ns = Ref{Cint}(0); np = Ref{Cint}(0)

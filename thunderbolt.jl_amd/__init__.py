@@ -12,3 +12,8 @@ from .coordinates import (compute_lv_coordinate_system, compute_midmyocardial_se
                           create_lumped_microstructure_model, ODB25LTMicrostructureParameters, evaluate_coordinate_axes, evaluate_coordinate,
                           wrap_rotational, apicobasal_from_laplace)
 from .meshgen import generate_ring_mesh, generate_open_ring_mesh, generate_ideal_lv_mesh_hex, ideal_lv_microstructure, uniform_refinement  # noqa: F401
+from . import chamber  # noqa: F401
+from .chamber import (RSAFDQ2022SurrogateVolume, Hirschvogel2017SurrogateVolume, ConstantChamberVolume, ChamberVolumeCoupling,  # noqa: F401
+                      LumpedFluidSolidCoupler, ChamberForm, ChamberTying, compute_chamber_volume, SchurComplementLinearSolver, BlockedChamberSystem,
+                      RSAFDQ2022LumpedCicuitModel, DummyLumpedCircuitModel, Φ_RSAFDQ2022, Phi_RSAFDQ2022, elastance_RSAFDQ2022, integrate_circuit,
+                      prepace_circuit, RSAFDQ2022Model, RSAFDQ2022Split, RSAFDQ2022Function, semidiscretize_rsafdq, RSAFDQ2022Integrator)

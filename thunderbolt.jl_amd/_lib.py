@@ -15,6 +15,7 @@ TB_STRATEGY_ATOMIC, TB_STRATEGY_PER_COLOR, TB_STRATEGY_ELEMENT, TB_STRATEGY_PATC
 TB_FORM_MASS, TB_FORM_DIFFUSION, TB_FORM_SOURCE, TB_FORM_HYPERELASTIC = 0, 1, 2, 3
 TB_MATERIAL_HOLZAPFEL_OGDEN_2009 = 0
 TB_BC_ROBIN, TB_BC_NORMAL_SPRING, TB_BC_PRESSURE, TB_BC_BENDING_SPRING, TB_BC_PRESSURE_FIELD = 0, 1, 2, 3, 4
+TB_VOLUME_RSAFDQ2022, TB_VOLUME_HIRSCHVOGEL2017 = 0, 1
 TB_COEF_CONST_SCALAR, TB_COEF_CONST_TENSOR, TB_COEF_FIELD_SCALAR = 0, 1, 2
 TB_COEF_SPECTRAL_CONST, TB_COEF_SPECTRAL_FIELD, TB_COEF_TRANSVERSE_CONST = 3, 4, 5
 TB_SRC_CONST, TB_SRC_NORM_PLUS_T, TB_SRC_COS_EXP, TB_SRC_TABULATED = 0, 1, 2, 3
@@ -118,6 +119,8 @@ SIGNATURES = {
     "tb_facet_form_set_field": (C.c_int, [vp, c_dp, C.c_int64]),
     "tb_facet_form_set_param": (C.c_int, [vp, C.c_double]),
     "tb_facet_assemble": (C.c_int, [vp, vp, vp, C.c_double, vp, vp]),
+    "tb_chamber_form_create": (C.c_int, [vp, C.c_int, c_dp, C.c_int, c_i32p, C.c_int64, C.c_int, C.POINTER(vp)]),
+    "tb_chamber_assemble": (C.c_int, [vp, vp, vp, C.c_double, vp, vp, vp, vp, vp]),
     "tb_host_material_eval": (C.c_int, [C.POINTER(tb_material), c_dp, c_dp, c_dp, c_dp]),
     "tb_reaction_step": (C.c_int, [vp, C.c_int, c_dp, C.c_int, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_double,
                                    C.c_double, C.c_int, C.c_double]),
@@ -210,7 +213,7 @@ def build_library(force=False):
 _lib = None
 
 
-TB_ABI_REVISION = 8   # include/tbhip.h: TB_ABI_REVISION
+TB_ABI_REVISION = 9   # include/tbhip.h: TB_ABI_REVISION
 
 
 def lib():

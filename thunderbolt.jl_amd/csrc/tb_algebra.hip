@@ -1182,8 +1182,8 @@ __device__ __forceinline__ void block_sum2_to(double a, double c, double *out)
 // one line: 51 µs; the CG update kernel on a 27-layer slab spent 23 of its 37 µs there).  The partial of workgroup b goes to slot b mod 64 of a GROUP of 64
 // slots 128 B apart instead (3 µs for the same 2 048), and whoever needs the sum adds the 64 slots: the next kernel of a fused sequence (read_slots: the
 // same xor tree in every wave, so every workgroup sees the same bits), or k_fold_slots (one wave) into a caller-owned scalar for the public one-kernel
-// entries.  Groups live in tb_device::d_slots and are zero between uses; launches of one device are stream-ordered.
-constexpr int RED_SLOTS = 64, RED_STRIDE = 16, RED_GROUP = RED_SLOTS * RED_STRIDE; // doubles
+// entries.  Groups live in tb_device::d_slots and are zero between uses; launches of one device are stream-ordered.  RED_SLOTS, RED_STRIDE and
+// RED_GROUP are in tb_internal.h (tb_chamber.hip folds its volume through group 0 as well).
 __device__ __forceinline__ void block_sum_slots(double v, double *group)
 {
 #pragma unroll

@@ -881,6 +881,55 @@ int tb_facet_assemble(tb_form *form, tb_pattern *pat, const double *d_u, double 
     return launch_facets(form, pat, d_u, d_nzval, d_r);
 }
 
+int tb_chamber_form_create(tb_mesh *mesh, int volume_method, const double *method_params, int facet_qpoints, const int32_t *facets, int64_t n_facets,
+                           int index_base, tb_form **out)
+{
+    TB_REQUIRE(mesh && out && (facets || n_facets == 0), "tb_chamber_form_create: NULL argument");
+    *out = nullptr;
+    TB_REQUIRE(volume_method == TB_VOLUME_RSAFDQ2022 || volume_method == TB_VOLUME_HIRSCHVOGEL2017, "tb_chamber_form_create: unknown volume method %d", volume_method);
+    if (mesh->geom_kind == TB_TET4) { set_error("tb_chamber_form_create: chamber facets are not implemented on tetrahedra"); return TB_ERR_UNSUPPORTED; }
+    TB_REQUIRE(mesh->ncomp == 3 && mesh->geom_kind == TB_HEX8 && (mesh->field_kind == TB_HEX8 || mesh->field_kind == TB_HEX27),
+               "tb_chamber_form_create: needs a 3-component TB_HEX8 or TB_HEX27 field on hexahedra");
+    TB_REQUIRE(index_base == 0 || index_base == 1, "tb_chamber_form_create: index_base must be 0 or 1");
+    TB_REQUIRE(n_facets >= 0, "tb_chamber_form_create: negative facet count");
+    if (facet_qpoints == 0) facet_qpoints = kind_order(mesh->field_kind);
+    TB_REQUIRE(facet_qpoints >= 1 && facet_qpoints <= 3, "tb_chamber_form_create: 1…3 Gauss points per facet direction (got %d)", facet_qpoints);
+    for (int64_t i = 0; i < mesh->n_cells * mesh->nb; ++i) {
+        const int32_t *d = &mesh->h_cell_dofs[3 * i];
+        TB_REQUIRE(d[1] == d[0] + 1 && d[2] == d[0] + 2, "tb_chamber_form_create: dofs of a node are not consecutive (cell %lld)", (long long)(i / mesh->nb));
+    }
+    std::vector<int32_t> fl((size_t)2 * n_facets);
+    for (int64_t i = 0; i < n_facets; ++i) {
+        const int32_t c = facets[2 * i] - index_base, lf = facets[2 * i + 1] - index_base;
+        TB_REQUIRE(c >= 0 && c < mesh->n_cells && lf >= 0 && lf < 6, "tb_chamber_form_create: facet %lld = (%d, %d) out of range", (long long)i, facets[2 * i], facets[2 * i + 1]);
+        fl[2 * i] = c; fl[2 * i + 1] = lf;
+    }
+    auto f = std::make_unique<tb_form>();
+    f->mesh = mesh; f->kind = TB_FORM_CHAMBER; f->facet_q = facet_qpoints; f->n_facets = n_facets; f->chamber_method = volume_method;
+    if (volume_method == TB_VOLUME_RSAFDQ2022) {
+        const double dflt[6] = {0.0, 1.0, 0.0, 0.0, 0.0, -0.1}; // rsafdq2022.jl:75-78
+        const double *mp = method_params ? method_params : dflt;
+        for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) f->chamber_H[3 * i + j] = mp[i] * mp[j]; f->chamber_b[i] = mp[3 + i]; }
+    } else {
+        for (int i = 0; i < 3; ++i) f->chamber_H[4 * i] = 1.0;
+    }
+    TB_HIP(hipSetDevice(mesh->dev->id));
+    int rc = upload(mesh->dev, fl, &f->d_facets);
+    if (rc) return rc;
+    *out = f.release();
+    return TB_OK;
+}
+
+int tb_chamber_assemble(tb_form *form, tb_pattern *pat, const double *d_u, double p, double *d_nzval, double *d_r, double *d_col, double *d_row, double *d_volume)
+{
+    TB_REQUIRE(form && d_u && (d_nzval || d_r || d_col || d_row || d_volume), "tb_chamber_assemble: NULL argument");
+    TB_REQUIRE(form->kind == TB_FORM_CHAMBER, "tb_chamber_assemble: form is not a chamber coupling");
+    TB_REQUIRE(!d_nzval || (pat && pat->mesh == form->mesh), "tb_chamber_assemble: the tangent needs the pattern of the form's mesh");
+    if (form->n_facets == 0) return TB_OK;
+    TB_HIP(hipSetDevice(form->mesh->dev->id));
+    return launch_chamber(form, pat, d_u, p, d_nzval, d_r, d_col, d_row, d_volume);
+}
+
 int tb_host_material_eval(const tb_material *material, const double *F, double *psi, double *P, double *A)
 {
     TB_REQUIRE(material && F, "tb_host_material_eval: NULL argument");

@@ -181,6 +181,10 @@ struct VecPatchPlan {
     int32_t *d_pdof = nullptr;      // global dof of every patch node
 };
 
+// Reduction slots (tb_algebra.hip "reduction slots", tb_chamber.hip): a group is RED_SLOTS partial sums RED_STRIDE doubles (128 B) apart; the groups
+// of a device live in tb_device::d_slots and are zero between uses.  Every user launches on the device's one stream, which is what orders them.
+constexpr int RED_SLOTS = 64, RED_STRIDE = 16, RED_GROUP = RED_SLOTS * RED_STRIDE; // doubles
+
 } // namespace tb
 
 struct tb_pattern;
@@ -325,6 +329,9 @@ struct tb_form {
     double bc_param = 0.0;
     int32_t *d_facets = nullptr; // (cell, local facet) pairs, 0-based
     int64_t n_facets = 0;
+    // chamber volume coupling (TB_FORM_CHAMBER): V = −J (H (x + d − b)) · F⁻ᵀ n₀
+    int chamber_method = 0;
+    double chamber_H[9] = {0}, chamber_b[3] = {0};
 };
 
 namespace tb {
@@ -391,6 +398,7 @@ int launch_axpy(tb_device *dev, int64_t n, double a, const double *x, double *y)
 int launch_absmax(tb_device *dev, int64_t n, const double *x, int64_t stride, double *result);
 int launch_facets(tb_form *f, tb_pattern *p, const double *d_u, double *d_nz, double *d_r);
 int launch_hyperelastic_tet(tb_form *f, tb_pattern *p, int strategy, const double *d_u, double *d_nz, double *d_r); // tb_mech_tet.hip
+int launch_chamber(tb_form *f, tb_pattern *p, const double *d_u, double pressure, double *d_nz, double *d_r, double *d_col, double *d_row, double *d_volume); // tb_chamber.hip
 int launch_facets_tet(tb_form *f, tb_pattern *p, const double *d_u, double *d_nz, double *d_r);
 int ensure_blockpos(tb_pattern *p);
 int launch_apply_zero(tb_pattern *pat, double *nz, double *f, const uint8_t *flags, double diag);

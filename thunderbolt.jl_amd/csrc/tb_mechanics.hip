@@ -27,6 +27,7 @@
 #include "tb_math.hpp"
 #include "tb_mech_common.hpp"
 #include "tb_mech_split.hpp"
+#include "tb_facet_geom.hpp"
 
 #ifdef TB_ABLATION
 #define TB_IF_ABLATION(...) __VA_ARGS__
@@ -1670,30 +1671,7 @@ int launch_hyperelastic(tb_form *f, tb_pattern *p, int strategy, const double *d
 // mapped gradients and the few tensors the integrand needs are parked in LDS, then every thread sums its (i, j) pairs over
 // the points and adds the result to the CSR entry / residual entry with one atomic each (surface terms are O(n²) work, the
 // volume term O(n³): this kernel is not on the critical path).  FacetValues conventions are Ferrite's (tbhip.h).
-__host__ __device__ constexpr int facet_fix(int lf) { constexpr int v[6] = {2, 1, 0, 1, 0, 2}; return v[lf]; }
-__host__ __device__ constexpr double facet_val(int lf) { constexpr double v[6] = {-1, -1, 1, 1, -1, 1}; return v[lf]; }
-__host__ __device__ constexpr int facet_s(int lf) { constexpr int v[6] = {1, 0, 1, 2, 2, 0}; return v[lf]; }
-__host__ __device__ constexpr int facet_t(int lf) { constexpr int v[6] = {0, 2, 2, 0, 1, 1}; return v[lf]; }
-
-template <int NB>
-__device__ inline void shape_at(int a, const double (&xi)[3], double &N, double (&dN)[3])
-{
-    if (NB == 8) {
-        const double f[3] = {1.0 + hex_sgn(a, 0) * xi[0], 1.0 + hex_sgn(a, 1) * xi[1], 1.0 + hex_sgn(a, 2) * xi[2]};
-        N = 0.125 * f[0] * f[1] * f[2];
-        dN[0] = 0.125 * hex_sgn(a, 0) * f[1] * f[2];
-        dN[1] = 0.125 * f[0] * hex_sgn(a, 1) * f[2];
-        dN[2] = 0.125 * f[0] * f[1] * hex_sgn(a, 2);
-    } else {
-        double v[3], d[3];
-        for (int k = 0; k < 3; ++k) { v[k] = quad1d(hex27_tix(a, k), xi[k]); d[k] = dquad1d(hex27_tix(a, k), xi[k]); }
-        N = v[0] * v[1] * v[2];
-        dN[0] = d[0] * v[1] * v[2];
-        dN[1] = v[0] * d[1] * v[2];
-        dN[2] = v[0] * v[1] * d[2];
-    }
-}
-
+// (numbering, Gauss points and the geometry stage: tb_facet_geom.hpp)
 template <int NB>
 __global__ void __launch_bounds__(64)
 k_facets(MechMesh m, const int32_t *__restrict__ facets, int bc, double param, int fq, const double *__restrict__ pfield, const double *__restrict__ u, double *__restrict__ nz,
@@ -1710,40 +1688,7 @@ k_facets(MechMesh m, const int32_t *__restrict__ facets, int bc, double param, i
     for (int i = tid; i < 24; i += 64) s_x[i] = m.xyz[3 * (int64_t)m.conn[cell * 8 + i / 3] + i % 3];
     __syncthreads();
     const int nq = fq * fq;
-    const double gx[3][3] = {{0.0, 0.0, 0.0}, {-0.5773502691896258, 0.5773502691896258, 0.0}, {-0.7745966692414834, 0.0, 0.7745966692414834}};
-    const double gw[3][3] = {{2.0, 0.0, 0.0}, {1.0, 1.0, 0.0}, {0.5555555555555556, 0.8888888888888888, 0.5555555555555556}};
-    // geometry + shape values per point: thread (q, a)
-    for (int idx = tid; idx < nq * NB; idx += 64) {
-        const int q = idx / NB, a = idx % NB;
-        double xi[3];
-        xi[facet_fix(lf)] = facet_val(lf);
-        xi[facet_s(lf)] = gx[fq - 1][q % fq];
-        xi[facet_t(lf)] = gx[fq - 1][q / fq];
-        double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-        for (int v = 0; v < 8; ++v) {
-            double Mv, dM[3];
-            shape_at<8>(v, xi, Mv, dM);
-            for (int i = 0; i < 3; ++i) for (int k = 0; k < 3; ++k) J[i][k] += s_x[3 * v + i] * dM[k];
-        }
-        const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1], c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2], c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-        const double det = J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02, id = 1.0 / det;
-        const double Ji[3][3] = {{c00 * id, (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id, (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id},
-                                 {c01 * id, (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id, (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id},
-                                 {c02 * id, (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id, (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id}};
-        double Na, dNa[3];
-        shape_at<NB>(a, xi, Na, dNa);
-        s_N[q][a] = Na;
-        for (int k = 0; k < 3; ++k) s_G[q][a][k] = dNa[0] * Ji[0][k] + dNa[1] * Ji[1][k] + dNa[2] * Ji[2][k];
-        if (a == 0) {
-            if (!(det > 0.0)) { st->neg_detj = 1; st->cell = cell; }
-            const int cs = facet_s(lf), ct = facet_t(lf);
-            const double av[3] = {J[0][cs], J[1][cs], J[2][cs]}, bv[3] = {J[0][ct], J[1][ct], J[2][ct]};
-            const double nw[3] = {av[1] * bv[2] - av[2] * bv[1], av[2] * bv[0] - av[0] * bv[2], av[0] * bv[1] - av[1] * bv[0]};
-            const double len = sqrt(nw[0] * nw[0] + nw[1] * nw[1] + nw[2] * nw[2]);
-            s_q[q][0] = len * gw[fq - 1][q % fq] * gw[fq - 1][q / fq];
-            for (int k = 0; k < 3; ++k) s_q[q][1 + k] = nw[k] / len;
-        }
-    }
+    facet_geometry_stage<NB>(tid, cell, lf, fq, s_x, s_N, s_G, s_q, st); // shape values, mapped gradients, dΓ and n₀ per point
     __syncthreads();
     // field values per point (one thread per point): u_q, F, and the tensors of the integrand
     //   slots: [4..6] g = residual vector density (δuᵢ·g), [7..15] H (Robin / spring: Hessian; pressure: invF), [16] J, [17..19] cofF·n₀,
@@ -1769,9 +1714,7 @@ k_facets(MechMesh m, const int32_t *__restrict__ facets, int bc, double param, i
             double pq = param;
             if (bc == TB_BC_PRESSURE_FIELD && pfield) { // evaluate_coefficient(pc, cell, qp, t): nodal data × M_a at the facet point
                 double xi[3];
-                xi[facet_fix(lf)] = facet_val(lf);
-                xi[facet_s(lf)] = gx[fq - 1][q % fq];
-                xi[facet_t(lf)] = gx[fq - 1][q / fq];
+                facet_xi(lf, fq, q, xi);
                 double v = 0.0;
                 for (int a = 0; a < 8; ++a) { double Ma, dMa[3]; shape_at<8>(a, xi, Ma, dMa); v += Ma * pfield[cell * 8 + a]; }
                 pq = param * v;

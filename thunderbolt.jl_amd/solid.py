@@ -585,7 +585,7 @@ class HomotopyPathSolver:
         self.controller = controller or Deuflhard2004_B_DiscreteContinuationControllerVariant()
         self.steps = []                      # (t, dt, newton iterations, accepted)
 
-    def solve(self, u, op, ch, tspan, dt, adaptive=True, dtmin=1e-6, maxiters=200):
+    def solve(self, u, op, ch, tspan, dt, adaptive=True, dtmin=1e-6, maxiters=200, system=None):
         if getattr(op, "internal", None) is not None:
             # check_internal_variables_are_rate_free (homotopy.jl:22-58): continuation has neither a previous solution nor a timestep
             raise ValueError("the material carries an internal variable with a time derivative, which HomotopyPathSolver cannot integrate: "
@@ -597,8 +597,9 @@ class HomotopyPathSolver:
             if len(self.steps) >= maxiters:
                 return False
             h = min(dt, t_end - t)
-            u0 = u.to_host()
-            solved = nlsolve(u, op, ch, ns, t=t + h)
+            sys_ = system if system is not None else DisplacementSystem(op, ch)
+            u0 = sys_.save_state(u)
+            solved = nlsolve(u, op, ch, ns, t=t + h, system=sys_)
             thetas = [th for th in ns.theta if np.isfinite(th)] if solved else list(ns.theta)
             ok = solved and (not adaptive or self.controller.should_accept_step(thetas, ns.enforce_monotonic_convergence))
             self.steps.append((t + h, h, ns.iter, bool(ok)))
@@ -607,7 +608,7 @@ class HomotopyPathSolver:
                 if adaptive:
                     dt = self.controller.adapt_dt(h, thetas)
             else:
-                u.copy_from_host(u0)                           # rollback_state!
+                sys_.restore_state(u, u0)                      # rollback_state!
                 if not adaptive:
                     return False
                 dt = 0.5 * h if not solved else self.controller.reject_step(h, thetas)
@@ -749,18 +750,24 @@ class EisenstatWalkerForcing:
         return self.eta
 
 
+class BlockedLinearSolver:
+    """Base of the linear solvers of blocked systems (chamber.py: SchurComplementLinearSolver).  NewtonRaphsonSolver accepts one as its
+    inner_solver, as the reference does; it is used by the blocked system handed to nlsolve and cannot solve the displacement block alone."""
+
+
 class NewtonRaphsonSolver:
     """NewtonRaphsonSolver(; max_iter, tol, inner_solver, forcing, simplified_newton) (src/solver/nonlinear/newton_raphson.jl:1-60); nlsolve!
     follows :215-320 — update_linearization!, eliminate constraints, residual norm over the free dofs, linear solve,
     eliminate the increment, u .-= Δu, Θₖ contraction monitor, early exits.  inner_solver: "cg" (Jacobi-PCG; symmetric positive
     definite tangents) or "gmres" (restarted, right-Jacobi; the reference's default KrylovJL_GMRES — for indefinite or
     non-symmetric tangents), or — LinearSolve.jl's pluggability — any callable (pattern, J, residual, Δu) → iterations that leaves the
-    solution of J Δu = residual in Δu (device vectors; the CSR structure is `pattern.sp.rowptr/colidx` on the host, J its values on the device)."""
+    solution of J Δu = residual in Δu (device vectors; the CSR structure is `pattern.sp.rowptr/colidx` on the host, J its values on the device),
+    or a BlockedLinearSolver for a blocked system (nlsolve(…, system=…))."""
 
     def __init__(self, max_iter=100, tol=1e-4, inner_rtol=1e-8, inner_atol=1e-14, inner_maxiter=5000, enforce_monotonic_convergence=True,
                  inner_solver="cg", gmres_restart=50, inner_precond=None, simplified_newton=False, forcing=None, strict_inner_solve=True):
-        if inner_solver not in ("cg", "gmres") and not callable(inner_solver):
-            raise ValueError("inner_solver: 'cg', 'gmres' or a callable (pattern, J, residual, Δu) -> linear iterations")
+        if not isinstance(inner_solver, BlockedLinearSolver) and inner_solver not in ("cg", "gmres") and not callable(inner_solver):
+            raise ValueError("inner_solver: 'cg', 'gmres', a callable (pattern, J, residual, Δu) -> linear iterations or a BlockedLinearSolver")
         self.inner_solver, self.gmres_restart = inner_solver, gmres_restart
         self.inner_precond = inner_precond          # None (Jacobi, device-scalar CG), L1GSPrecBuilder(partsize) or ChebyshevPrecBuilder(degree)
         # simplified_newton: the tangent of the first iteration is reused, later iterations assemble the residual only (residual!);
@@ -778,9 +785,64 @@ class NewtonRaphsonSolver:
         self.strict_inner_solve = bool(strict_inner_solve)
 
 
-def nlsolve(u, op, ch, solver, t=0.0):
-    """nlsolve!(u, stage, cache, t) → Bool.  `u` must already satisfy the Dirichlet values (apply!(u, ch))."""
+def inner_linear_solve(solver, pattern, J, b, x, inner_rtol):
+    """One inner solve J x = b with the solver's choice ("cg", "gmres", preconditioned CG or a callable) → (iterations, residual norm or None)."""
+    if isinstance(solver.inner_solver, BlockedLinearSolver):
+        raise TypeError("%s solves blocked systems: pass the blocked system of the problem to nlsolve" % type(solver.inner_solver).__name__)
+    if callable(solver.inner_solver):
+        return solver.inner_solver(pattern, J, b, x), None
+    if solver.inner_solver == "cg" and solver.inner_precond is not None:
+        return pcg_solve(pattern, J, b, x, inner_rtol, solver.inner_atol, solver.inner_maxiter, solver.inner_precond)
+    if solver.inner_solver == "gmres":
+        return gmres_solve(pattern, J, b, x, inner_rtol, solver.inner_atol, solver.inner_maxiter, solver.gmres_restart, True)
+    return cg_solve(pattern, J, b, x, inner_rtol, solver.inner_atol, solver.inner_maxiter, True)
+
+
+class DisplacementSystem:
+    """What nlsolve iterates on: the unknowns, their linearisation and how an increment is found.  This one is the displacement block alone
+    (the quasi-static problem); a blocked problem (chamber.py: [u_d; p]) overrides the four steps and reuses the loop."""
+
+    def __init__(self, op, ch):
+        self.op, self.ch = op, ch
+        self.failure_detail = None                            # what solve_increment has to say about a failure without a residual norm
+
+    def linearize(self, u, res, t, tangent):
+        """residual (and, with `tangent`, the Jacobian) at u with the constraints eliminated"""
+        op, ch = self.op, self.ch
+        if tangent:
+            update_linearization(op, u, t, residual=res)
+            apply_zero(op.J, res, ch, pattern=op.pattern)
+        else:
+            residual(op, res, u, t)                            # the eliminated tangent of iteration 0 stays in op.J
+            apply_zero(None, res, ch, pattern=op.pattern)
+
+    def residual_norm(self, res):
+        return norm(res)                                      # prescribed entries are zero: this is the norm over the free dofs
+
+    def solve_increment(self, solver, res, du, inner_rtol):
+        """J Δu = residual → (iterations, residual norm or None, converged).  Not converged with a residual norm: Δu is an inexact increment and
+        strict_inner_solve decides; not converged without one: there is no increment and the step fails."""
+        its, lres = inner_linear_solve(solver, self.op.pattern, self.op.J, res, du, inner_rtol)
+        return its, lres, lres is None or solve_converged(self.op.pattern, lres)
+
+    def apply_increment(self, u, du):
+        """eliminate_constraints_from_increment!, u .-= Δu → ‖Δu‖"""
+        apply_zero(None, du, self.ch, pattern=self.op.pattern)
+        check(lib().tb_axpy(u.dev.h, u.n, -1.0, du.ptr, u.ptr))
+        return norm(du)
+
+    def save_state(self, u):
+        return u.to_host()
+
+    def restore_state(self, u, state):
+        u.copy_from_host(state)                               # rollback_state!
+
+
+def nlsolve(u, op, ch, solver, t=0.0, system=None):
+    """nlsolve!(u, stage, cache, t) → Bool.  `u` must already satisfy the Dirichlet values (apply!(u, ch)).  `system`: the unknowns the loop
+    runs on (default: the displacement block, DisplacementSystem(op, ch))."""
     dev = u.dev
+    sys_ = system if system is not None else DisplacementSystem(op, ch)
     res = DeviceVector(dev, u.n)
     du = DeviceVector(dev, u.n)
     solver.iter, solver.theta, solver.residual_norms, solver.linear_iters = -1, [], [], []
@@ -788,14 +850,9 @@ def nlsolve(u, op, ch, solver, t=0.0):
     eps = np.finfo(np.float64).eps
     while True:
         solver.iter += 1
-        if solver.simplified_newton and solver.iter > 0:
-            residual(op, res, u, t)                            # the eliminated tangent of iteration 0 stays in op.J
-            apply_zero(None, res, ch, pattern=op.pattern)
-        else:
-            update_linearization(op, u, t, residual=res)
-            apply_zero(op.J, res, ch, pattern=op.pattern)
+        sys_.linearize(u, res, t, not (solver.simplified_newton and solver.iter > 0))
         solver.jacobian_is_fresh = not (solver.simplified_newton and solver.iter > 0)
-        rnorm = norm(res)                                     # prescribed entries are zero: this is the norm over the free dofs
+        rnorm = sys_.residual_norm(res)
         solver.residual_norms.append(rnorm)
         if rnorm < solver.tol and solver.iter > 0:
             solver.theta.append(0.0)
@@ -806,19 +863,13 @@ def nlsolve(u, op, ch, solver, t=0.0):
         du.fill_zero()
         inner_rtol = solver.inner_rtol if solver.forcing is None else solver.forcing.prestep(rnorm, solver.iter)
         try:
-            if callable(solver.inner_solver):
-                its = solver.inner_solver(op.pattern, op.J, res, du)
-            elif solver.inner_solver == "cg" and solver.inner_precond is not None:
-                its, lres = pcg_solve(op.pattern, op.J, res, du, inner_rtol, solver.inner_atol, solver.inner_maxiter, solver.inner_precond)
-            elif solver.inner_solver == "gmres":
-                its, lres = gmres_solve(op.pattern, op.J, res, du, inner_rtol, solver.inner_atol, solver.inner_maxiter, solver.gmres_restart, True)
-            else:
-                its, lres = cg_solve(op.pattern, op.J, res, du, inner_rtol, solver.inner_atol, solver.inner_maxiter, True)
-            if not callable(solver.inner_solver) and not solve_converged(op.pattern, lres):
+            its, lres, converged = sys_.solve_increment(solver, res, du, inner_rtol)
+            if not converged:
                 # newton_raphson.jl:266-269 `solve_succeeded || return false`: an inner solve that ran into its iteration limit fails the step
                 # unless the solver was built with strict_inner_solve=False (inexact Newton step, event recorded)
-                solver.linear_failure = "inner linear solve stopped at %d iterations with residual %.3e above its tolerance" % (its, lres)
-                if solver.strict_inner_solve:
+                solver.linear_failure = "inner linear solve stopped at %d iterations with residual %.3e above its tolerance" % (its, lres) \
+                    if lres is not None else "inner linear solve failed after %d iterations%s" % (its, ": %s" % sys_.failure_detail if sys_.failure_detail else "")
+                if solver.strict_inner_solve or lres is None:
                     solver.linear_iters.append(its)
                     solver.theta.append(np.inf)
                     return False
@@ -829,9 +880,7 @@ def nlsolve(u, op, ch, solver, t=0.0):
             solver.theta.append(np.inf)
             return False
         solver.linear_iters.append(its)
-        apply_zero(None, du, ch, pattern=op.pattern)          # eliminate_constraints_from_increment!
-        check(lib().tb_axpy(dev.h, u.n, -1.0, du.ptr, u.ptr))  # u .-= Δu
-        inorm = norm(du)
+        inorm = sys_.apply_increment(u, du)
         if solver.iter > 0:
             theta = min(rnorm / rprev, inorm / iprev) if rprev > 0.0 and iprev > 0.0 else 0.0
             solver.theta.append(theta)
