@@ -1230,6 +1230,42 @@ def test_deferred_status_reports_at_the_poll(tb, device):
     assert rel_err(tb.update_operator(good, 0.0).A.to_host(), ref) < 1e-14
 
 
+def test_deferred_status_cell_survives_the_scalar_reductions(tb, device):
+    """The calls that hand one scalar to the host (tb_dot, tb_absmax, tb_max) leave it in a device line of their own, not in the `cell` field of the
+    status block: with the status deferred, a detJ ≤ 0 raised by an assembly and polled after three such reductions names the same cell as a poll
+    right after the assembly."""
+    import ctypes as C
+    g = tb.generate_mesh(tb.Hexahedron, (2, 2, 2))
+    conn = g.conn.copy()
+    conn[5] = conn[5, [0, 3, 2, 1, 4, 7, 6, 5]]                      # one inverted cell: raises the status flag, no fault
+    dh = tb.DofHandler(tb.Grid(tb.Hexahedron, g.xyz, conn))
+    op = tb.setup_operator(tb.PatchAssemblyStrategy(device), tb.BilinearMassIntegrator(tb.ConstantCoefficient(1.0)), dh, tb.allocate_matrix(dh))
+    xh, yh = np.array([1.5, -2.5, 0.25, -7.0, 3.0]), np.array([2.0, 1.0, -4.0, 0.5, 1.0])
+    x, y = device.to_device(xh), device.to_device(yh)
+
+    def poll_after(reductions):
+        device.defer_status(True)
+        try:
+            tb.update_operator(op, 0.0)
+            vals = []
+            if reductions:
+                for fn, args in ((tb.lib().tb_dot, (x.ptr, y.ptr)), (tb.lib().tb_absmax, (x.ptr, 1)), (tb.lib().tb_max, (x.ptr, 1))):
+                    out = C.c_double()
+                    tb.check(fn(device.h, len(xh), *args, C.byref(out)))
+                    vals.append(out.value)
+            with pytest.raises(tb.TBError) as e:
+                device.poll_status()
+        finally:
+            device.defer_status(False)
+        assert e.value.code == tb._lib.TB_ERR_NEG_DETJ
+        return str(e.value), vals
+
+    plain, _ = poll_after(False)
+    after, vals = poll_after(True)
+    assert "cell" in plain and after == plain, (after, plain)
+    assert vals == [float(xh @ yh), 7.0, 3.0]                        # (sums of five exactly representable products: exact)
+
+
 def test_hyperelastic_negative_jacobian_and_bad_field(tb, device):
     g = tb.generate_mesh(tb.Hexahedron, (2, 2, 2))
     bad = tb.Grid(tb.Hexahedron, g.xyz, g.conn[:, [0, 3, 2, 1, 4, 7, 6, 5]])
@@ -2934,6 +2970,55 @@ def test_cg_from_initial_residual_matches_the_plain_solve(tb, device):
     x3 = device.to_device(u0)
     it3, _ = tb.cg_solve(M.pattern, A, b, x3, rtol=1e-10, atol=0.0, maxiter=300, jacobi=2)
     assert it3 == it1 and np.abs(x3.to_host() - x1.to_host()).max() < 1e-12 * np.abs(u0).max()
+
+
+def test_jacobi_reuse_survives_other_solvers_on_the_shared_workspace(tb, device):
+    """The Krylov solvers of a pattern share one workspace, and TB_JACOBI_REUSE relies on the D⁻¹ the previous CG left in it: a GMRES or a Chebyshev
+    PCG solve of another matrix in between (one grows the workspace, the other only overwrites it) makes the reusing CG extract its diagonal again —
+    same iteration count as the first solve, same solution to the solver's own tolerance in the residual norm."""
+    import ctypes as C
+    import scipy.sparse as ssp
+    g = tb.generate_mesh(tb.Hexahedron, (5, 4, 3), (0, 0, 0), (1, 1, 1), perturb=0.2)
+    dh = tb.DofHandler(g)
+    sp = tb.allocate_matrix(dh)
+    n = dh.ndofs
+    assert n == 120
+    st = tb.PatchAssemblyStrategy(device)
+    kap = np.diag([4.5e-5, 2.0e-5, 2.0e-5])
+    D = tb.ConductivityToDiffusivityCoefficient(tb.ConstantCoefficient(kap), tb.ConstantCoefficient(1.0), tb.ConstantCoefficient(1.0))
+    M = tb.update_operator(tb.setup_operator(st, tb.BilinearMassIntegrator(tb.ConstantCoefficient(1.0)), dh, sp), 0.0)
+    K = tb.update_operator(tb.setup_operator(st, tb.BilinearDiffusionIntegrator(D), dh, sp), 0.0)
+    pat = M.pattern
+    A1 = tb.heat_system_matrix(device, M, K, 0.01)
+    A2 = device.to_device(3.0 * tb.heat_system_matrix(device, M, K, 10.0).to_host())    # another SPD matrix on the pattern, another diagonal
+    A1h = ssp.csr_matrix((A1.to_host(), sp.colidx, sp.rowptr), shape=(n, n))
+    rng = np.random.default_rng(7)
+    bh, x0 = rng.normal(size=n), rng.normal(size=n)
+    b = device.to_device(bh)
+    kw = dict(rtol=1e-10, atol=0.0, maxiter=300)
+
+    def between_gmres():
+        its, _ = tb.gmres_solve(pat, A2, b, device.to_device(x0), rtol=1e-8, atol=0.0, maxiter=100, restart=10, jacobi=True)
+        assert its > 0
+
+    def between_chebyshev():
+        its, _ = tb.pcg_solve(pat, A2, b, device.to_device(x0), rtol=1e-8, atol=0.0, maxiter=100, precond=tb.ChebyshevPrecBuilder(4))
+        assert its > 0
+
+    for between in (between_gmres, between_chebyshev):
+        x1 = device.to_device(x0)
+        it1, res1 = tb.cg_solve(pat, A1, b, x1, jacobi=1, **kw)
+        assert 0 < it1 < 300 and tb.solve_converged(pat, res1)
+        between()
+        x3 = device.to_device(x0)
+        it3, res3 = tb.cg_solve(pat, A1, b, x3, jacobi=2, **kw)                          # 2 = TB_JACOBI_REUSE
+        tol = C.c_double()
+        tb.check(tb.lib().tb_solver_last_tolerance(pat.h, C.byref(tol)))
+        print("jacobi reuse after %s: iterations %d / %d, |A (x3 - x1)| %.3e, tolerance %.3e" % (between.__name__, it1, it3,
+              np.linalg.norm(A1h @ (x3.to_host() - x1.to_host())), tol.value))
+        assert it3 == it1, (between.__name__, it1, it3)
+        assert res3 <= tol.value
+        assert np.linalg.norm(A1h @ (x3.to_host() - x1.to_host())) <= tol.value, between.__name__
 
 
 # ------------------------------------------------------------------------------------------- the reference's own GPU tests

@@ -1,5 +1,5 @@
 // tb_api.cpp — C-ABI entry points (include/tbhip.h): objects, memory, argument checking, error strings.
-// No arithmetic of the path lives here; kernels are in tb_assembly.hip / tb_reaction.hip / tb_algebra.hip.
+// No arithmetic of the path lives here; kernels are in tb_assembly.hip / tb_reaction.hip / tb_algebra.hip / tb_spmv.hip / tb_krylov.hip.
 #include <algorithm>
 #include <mutex>
 #include <cmath>
@@ -140,6 +140,8 @@ int tb_device_create(int hip_device_id, tb_device **out)
     TB_HIP(hipMalloc((void **)&dev->d_status, sizeof(Status)));
     TB_HIP(hipMalloc((void **)&dev->d_slots, 8 * 1024 * sizeof(double)));
     TB_HIP(hipMemset(dev->d_slots, 0, 8 * 1024 * sizeof(double)));
+    TB_HIP(hipMalloc((void **)&dev->d_readback, 16 * sizeof(double)));
+    TB_HIP(hipMemset(dev->d_readback, 0, 16 * sizeof(double)));
     TB_HIP(hipHostMalloc((void **)&dev->h_status, sizeof(Status), hipHostMallocDefault));
     *out = dev.release();
     return TB_OK;
@@ -157,6 +159,7 @@ int tb_device_destroy(tb_device *dev)
     if (dev->d_scratch) hipFree(dev->d_scratch);
     if (dev->d_tslot) hipFree(dev->d_tslot);
     if (dev->d_slots) hipFree(dev->d_slots);
+    if (dev->d_readback) hipFree(dev->d_readback);
     delete dev;
     return TB_OK;
 }
@@ -435,7 +438,7 @@ int tb_pattern_destroy(tb_pattern *p)
 {
     if (!p) return TB_OK;
     { std::lock_guard<std::mutex> lock(g_mirrored_mutex); g_mirrored.erase(std::remove(g_mirrored.begin(), g_mirrored.end(), p), g_mirrored.end()); }
-    hipFree(p->d_rowptr); hipFree(p->d_colidx); hipFree(p->d_blkrow); hipFree(p->d_blkrec); hipFree(p->d_rowsig); hipFree(p->d_sigoff); hipFree(p->d_wrunrec); for (double *q : p->d_mir) hipFree(q); hipFree(p->d_mir_base); hipFree(p->d_mir_off); hipFree(p->d_bcol); hipFree(p->d_diagpos); hipFree(p->d_emap); hipFree(p->d_blockpos); hipFree(p->d_cg_ws); hipFree(p->d_gmres_ws); hipFree(p->d_pcg_ws); hipFree(p->d_cheb_ws); hipFree(p->d_q2pos); hipFree(p->d_q2pos_t); hipFree(p->d_kebuf); hipFree(p->d_qpbuf); hipFree(p->d_gnodes);
+    hipFree(p->d_rowptr); hipFree(p->d_colidx); hipFree(p->d_blkrow); hipFree(p->d_blkrec); hipFree(p->d_rowsig); hipFree(p->d_sigoff); hipFree(p->d_wrunrec); for (double *q : p->d_mir) hipFree(q); hipFree(p->d_mir_base); hipFree(p->d_mir_off); hipFree(p->d_bcol); hipFree(p->d_diagpos); hipFree(p->d_emap); hipFree(p->d_blockpos); hipFree(p->d_krylov_ws); hipFree(p->d_q2pos); hipFree(p->d_q2pos_t); hipFree(p->d_kebuf); hipFree(p->d_qpbuf); hipFree(p->d_gnodes);
     free_patch_mat_plan(p);
     free_patch_fused_plan(p);
     delete p;
@@ -1209,8 +1212,9 @@ int tb_l1gs_apply(tb_pattern *pat, const double *d_Anz, int partsize, int sweep,
     TB_REQUIRE(partsize >= 1 && partsize <= 1024, "tb_l1gs_apply: partition size must be in 1..1024 (got %d)", partsize);
     TB_REQUIRE(sweep == TB_SWEEP_FORWARD || sweep == TB_SWEEP_SYMMETRIC, "tb_l1gs_apply: sweep must be TB_SWEEP_FORWARD or TB_SWEEP_SYMMETRIC");
     TB_HIP(hipSetDevice(pat->mesh->dev->id));
-    if (!pat->d_pcg_ws) TB_HIP(hipMalloc((void **)&pat->d_pcg_ws, sizeof(double) * (5 * pat->n_rows + 8)));
-    double *dtl = pat->d_pcg_ws + 4 * pat->n_rows;
+    double *dtl = krylov_ws(pat, (size_t)pat->n_rows); // D̃
+    if (!dtl) return TB_ERR_HIP;
+    pat->cg_dinv_of = nullptr; // the workspace no longer holds launch_cg's D⁻¹
     int rc = launch_l1gs_setup(pat, d_Anz, partsize, dtl);
     if (rc) return rc;
     return launch_l1gs_apply(pat, d_Anz, dtl, partsize, sweep == TB_SWEEP_SYMMETRIC, d_r, d_z);

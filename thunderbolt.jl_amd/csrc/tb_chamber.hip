@@ -13,7 +13,7 @@
 // the second being the follower-load tangent of k_facets contracted with w instead of δuᵢ.
 //
 // One 64-lane workgroup per (cell, local facet), the geometry stage shared with k_facets (tb_facet_geom.hpp).  The volume partial of a workgroup goes to
-// one of 64 slots 128 B apart (the reduction-slot scheme of tb_algebra.hip: same-line atomics serialise in L2) and k_chamber_fold adds the slots to the
+// one of 64 slots 128 B apart (the reduction-slot scheme of tb_reduce.hpp: same-line atomics serialise in L2) and k_chamber_fold adds the slots to the
 // caller's scalar; the host never reads it here.
 #include <hip/hip_runtime.h>
 

@@ -63,6 +63,13 @@ const char *last_kernel();
         TB_HIP(hipStreamSynchronize((dev_)->stream));     \
     } while (0)
 
+// a call that returns a TB_* code: pass a failure on
+#define TB_TRY(call)                      \
+    do {                                  \
+        const int rc__ = (call);          \
+        if (rc__) return rc__;            \
+    } while (0)
+
 // TB_PLAN_VERBOSE=1: wall time of the host-side plan builders, stage by stage, on stderr (what `setup_s.first_step_incl_plan_build` of bench.py is made of)
 struct PlanTimer {
     const char *name;
@@ -181,7 +188,7 @@ struct VecPatchPlan {
     int32_t *d_pdof = nullptr;      // global dof of every patch node
 };
 
-// Reduction slots (tb_algebra.hip "reduction slots", tb_chamber.hip): a group is RED_SLOTS partial sums RED_STRIDE doubles (128 B) apart; the groups
+// Reduction slots (tb_reduce.hpp "reduction slots", tb_chamber.hip): a group is RED_SLOTS partial sums RED_STRIDE doubles (128 B) apart; the groups
 // of a device live in tb_device::d_slots and are zero between uses.  Every user launches on the device's one stream, which is what orders them.
 constexpr int RED_SLOTS = 64, RED_STRIDE = 16, RED_GROUP = RED_SLOTS * RED_STRIDE; // doubles
 
@@ -200,7 +207,8 @@ struct tb_device {
     bool defer_status = false;      // tb_device_defer_status: assembly calls return without reading the status block; tb_device_poll_status reads it
     void *d_scratch = nullptr;      // Float64 arena behind the *_f32 entry points (tb_f32.hip), grown on demand
     size_t scratch_bytes = 0;
-    double *d_slots = nullptr;      // reduction slots (tb_algebra.hip: block_sum_slots): RED_GROUPS groups of 64 partial sums, 128 B apart, zero between uses
+    double *d_slots = nullptr;      // reduction slots (tb_reduce.hpp: block_sum_slots): RED_GROUPS groups of 64 partial sums, 128 B apart, zero between uses
+    double *d_readback = nullptr;   // one 128-byte line: where a call that returns a scalar to the host has its kernel leave it (read_back); never the status block
     double *d_tslot = nullptr;      // {t, cos 2πt}: where time-dependent kernels read the time while a graph capture is open (tb_graph.hip)
     bool capturing = false, defer_before_capture = false, tslot_used = false; // tslot_used: a captured launch was handed the slot
     hipStream_t aux_stream = nullptr; // second queue of the chunked mechanics linearisation (gather of chunk k beside the integration of chunk k + 1)
@@ -241,8 +249,10 @@ struct tb_pattern {
     std::vector<int32_t> h_colidx;
     bool map64 = false;
     void *d_emap = nullptr; // [ndpc*ndpc][n_cells] nz index of (cell,i,j): int32 (nnz < 2^31) or int64
-    double *d_cg_ws = nullptr;      // CG workspace (r, p, Ap, D⁻¹, 2 scalars)
-    const double *cg_dinv_of = nullptr; // the nz array whose diagonal the D⁻¹ slot of d_cg_ws holds (TB_JACOBI_REUSE re-extracts for any other)
+    double *d_krylov_ws = nullptr;  // workspace of the Krylov solver that ran last (krylov_ws: grow-only, each solver lays its vectors and scalars out from the start)
+    size_t krylov_ws_doubles = 0;
+    const double *cg_dinv_of = nullptr; // the nz array whose diagonal the D⁻¹ slot of launch_cg's layout holds (TB_JACOBI_REUSE re-extracts for any other); NULL once
+                                        // the workspace grew or another solver used it
     double last_tol = 0.0;          // atol + rtol·‖r₀‖ of the latest Krylov solve on this pattern (tb_solver_last_tolerance)
     int32_t *d_bcol = nullptr;      // block SpMV of 3-dof-per-node patterns: one column (node) index per 3×3 block
     int b3 = 0, b3_lanes = 16;      // b3: 0 = not examined, 1 = CSR of 3×3 blocks, −1 = not
@@ -271,10 +281,6 @@ struct tb_pattern {
     int64_t n_wrun = 0;
     uint16_t *d_q2pos = nullptr;    // scalar Q2 forms: position of col dof(j) in row dof(i), per cell and pair
     uint16_t *d_q2pos_t = nullptr;  // the same in the order of the stored element matrices (element strategy: tensor order, k_matrix_q2_sf)
-    double *d_pcg_ws = nullptr;     // general-preconditioner PCG workspace (r, z, p, Ap, D̃, scalars)
-    double *d_cheb_ws = nullptr;    // Chebyshev-preconditioned CG workspace (r, z, p, Ap, D⁻¹, d, w, scalars)
-    double *d_gmres_ws = nullptr;   // GMRES workspace: (restart+1) basis vectors + 3 vectors + scalars
-    int gmres_m = 0;
     double *d_kebuf = nullptr;      // element-matrix buffer of the ElementAssemblyStrategy (vector fields)
     size_t kebuf_bytes = 0;
     double *d_qpbuf = nullptr;      // quadrature-point records of the split mechanics linearisation (k_mech_points → k_mech_contract), one launch's worth
@@ -357,22 +363,31 @@ int launch_assemble_hex8_patch(tb_form *fK, tb_form *fM, tb_pattern *p, double t
 bool hex8_patch_applicable(const tb_form *f, const tb_pattern *p);
 int launch_assemble_tet4_patch(tb_form *fK, tb_form *fM, tb_pattern *p, double t, double *d_nzK, double *d_nzM); // linear tetrahedra; either form may be NULL
 bool tet4_patch_applicable(const tb_form *f, const tb_pattern *p);
+int ensure_aux_stream(tb_device *dev); // second queue + two events of the chunked element assemblies (tb_mechanics.hip, scalar Q2 forms)
 
-// ---- kernel launchers (tb_assembly.hip / tb_reaction.hip / tb_algebra.hip) ----
+// ---- kernel launchers, by the file that defines them ----
+// tb_assembly.hip
 int ensure_emap(tb_pattern *p);
+int ensure_cell_xyz(tb_mesh *m); // builds tb_mesh::d_cell_xyz on first use
 int launch_assemble_matrix(tb_form *f, tb_pattern *p, int strategy, double t, double *d_nz);
 int launch_assemble_vector(tb_form *f, int strategy, double t, double *d_b);
+// tb_mechanics.hip, tb_mech_tet.hip, tb_chamber.hip
 int launch_hyperelastic(tb_form *f, tb_pattern *p, int strategy, const double *d_u, double *d_nz, double *d_r);
 int host_material_eval_form(tb_form *form, const double *F9, double *psi, double *P, double *A);
 int host_material_eval(const tb_material *mat, const double *F9, double *psi, double *P, double *A);
+int launch_facets(tb_form *f, tb_pattern *p, const double *d_u, double *d_nz, double *d_r);
+int ensure_blockpos(tb_pattern *p);
+int launch_hyperelastic_tet(tb_form *f, tb_pattern *p, int strategy, const double *d_u, double *d_nz, double *d_r);
+int launch_facets_tet(tb_form *f, tb_pattern *p, const double *d_u, double *d_nz, double *d_r);
+int launch_chamber(tb_form *f, tb_pattern *p, const double *d_u, double pressure, double *d_nz, double *d_r, double *d_col, double *d_row, double *d_volume);
+// tb_reaction.hip
 int launch_reaction(tb_device *dev, int model, const double *params, int n_params, double *d_u, double *d_du,
                     int64_t n_points, int layout, double t, double dt, int substeps, double thr, double *rmax /*nullable, host*/,
                     const float *d_x = nullptr, int sdim = 0);
 int launch_reaction_f32(tb_device *dev, int model, const double *params, int n_params, float *d_u, float *d_du, int64_t n_points, int layout, double t, double dt,
                         int substeps, double thr, const float *d_x, int sdim);
 int launch_reaction_rl(tb_device *dev, int model, const double *params, int n_params, double *d_u, int64_t n, int layout, double t, double dt);
-int launch_heat_matrix(tb_device *dev, int64_t nnz, const double *M, const double *K, double dt, double *A);
-int launch_spmv(tb_pattern *p, const double *nz, const double *x, double alpha, double beta, double *y);
+// tb_sarcomere.hip
 int launch_sarcomere(tb_device *dev, const double *params, double *d_state, int64_t n, const double *d_stretch, const double *d_velocity,
                      const double *d_calcium, double stretch, double velocity, double calcium, double dt, int substeps, int rate_independent,
                      double *d_tension, double *d_stiffness);
@@ -386,50 +401,74 @@ void host_sarcomere_derivatives(const double *params, const double *u, double st
                                 double *gv, double *rhs);
 void host_sarcomere_eval(const double *params, const double *u, double stretch, double velocity, double calcium, double *du, double *tension,
                          double *stiffness);
-int launch_l1gs_setup(tb_pattern *pat, const double *A, int ps, double *d_dtilde);
-int launch_l1gs_apply(tb_pattern *pat, const double *A, const double *d_dtilde, int ps, int symmetric, const double *r, double *z);
-int launch_pcg_chebyshev(tb_pattern *pat, const double *A, const double *b, double *x, double rtol, double atol, int maxiter, int degree, int *iters, double *resnorm);
-int launch_pcg_l1gs(tb_pattern *pat, const double *A, const double *b, double *x, double rtol, double atol, int maxiter, int ps, int *iters, double *resnorm);
-int launch_gmres(tb_pattern *pat, const double *A, const double *b, double *x, double rtol, double atol, int maxiter, int restart, int jacobi,
-                 int *iters, double *resnorm);
-int launch_cg(tb_pattern *pat, const double *A, const double *b, double *x, double rtol, double atol, int maxiter, int jacobi, int *iters,
-              double *resnorm, bool b_is_residual = false);
+// tb_algebra.hip
+int launch_heat_matrix(tb_device *dev, int64_t nnz, const double *M, const double *K, double dt, double *A);
 int launch_axpy(tb_device *dev, int64_t n, double a, const double *x, double *y);
 int launch_absmax(tb_device *dev, int64_t n, const double *x, int64_t stride, double *result);
-int launch_facets(tb_form *f, tb_pattern *p, const double *d_u, double *d_nz, double *d_r);
-int launch_hyperelastic_tet(tb_form *f, tb_pattern *p, int strategy, const double *d_u, double *d_nz, double *d_r); // tb_mech_tet.hip
-int launch_chamber(tb_form *f, tb_pattern *p, const double *d_u, double pressure, double *d_nz, double *d_r, double *d_col, double *d_row, double *d_volume); // tb_chamber.hip
-int launch_facets_tet(tb_form *f, tb_pattern *p, const double *d_u, double *d_nz, double *d_r);
-int ensure_blockpos(tb_pattern *p);
+int launch_max(tb_device *dev, int64_t n, const double *x, int64_t stride, double *result);
+double decode_ordered_key(unsigned long long k);
+int launch_dot(tb_device *dev, int64_t n, const double *a, const double *b, double *result);
+void enqueue_dot(tb_device *dev, int64_t n, const double *a, const double *b, double *d_out); // *d_out += a·b, nothing read back
+void fold_slots(tb_device *dev, int first_group, double *d_out, int ngroups); // d_out[k] += the sum of slot group first_group + k, the groups back to zero (tb_reduce.hpp)
 int launch_apply_zero(tb_pattern *pat, double *nz, double *f, const uint8_t *flags, double diag);
 int launch_meandiag(tb_pattern *pat, const double *nz, double *result);
-int launch_dot(tb_device *dev, int64_t n, const double *a, const double *b, double *result);
+int launch_gather_indexed(tb_device *dev, int64_t n, const double *vec, const int32_t *idx, double *out);
+int launch_scatter_indexed(tb_device *dev, int64_t n, const double *in, const int32_t *idx, double *vec);
+int launch_scatter_add_indexed(tb_device *dev, int64_t n, const double *in, const int32_t *idx, double *vec);
+// tb_spmv.hip
+int spmv_plans(tb_pattern *p); // builds the plans tb_spmv_csr would build on its first product
+int launch_spmv(tb_pattern *p, const double *nz, const double *x, double alpha, double beta, double *y);
+int launch_spmv_dot(tb_pattern *pat, const double *A, const double *x, double *y, double *d_dot);        // y = A x, *d_dot += xᵀy
+int launch_spmv_dot_slots(tb_pattern *pat, const double *A, const double *x, double *y, double *group);  // the same with the sum left in a slot group: the
+                                                                                                         // one place that picks the product kernel of every CG form
+int launch_spmv_rows(tb_pattern *p, const double *nz, const double *x, int64_t n, const int32_t *rows, double *out);
+int launch_mirror_bind(tb_pattern *p, const double *nz); // tb_spmv_mirror
+int launch_extract_diagonal(tb_pattern *p, const double *nz, double *diag);
+int launch_extract_inverse_diagonal(tb_pattern *p, const double *nz, double *dinv); // D⁻¹ of the Jacobi preconditioner (1 where no diagonal is stored)
+// tb_krylov.hip
+double *krylov_ws(tb_pattern *pat, size_t doubles); // the pattern's one solver workspace, grown to at least `doubles` (contents lost when it grows); NULL + error on failure
+int launch_cg(tb_pattern *pat, const double *A, const double *b, double *x, double rtol, double atol, int maxiter, int jacobi, int *iters,
+              double *resnorm, bool b_is_residual = false);
+int launch_gmres(tb_pattern *pat, const double *A, const double *b, double *x, double rtol, double atol, int maxiter, int restart, int jacobi,
+                 int *iters, double *resnorm);
+int launch_l1gs_setup(tb_pattern *pat, const double *A, int ps, double *d_dtilde);
+int launch_l1gs_apply(tb_pattern *pat, const double *A, const double *d_dtilde, int ps, int symmetric, const double *r, double *z);
+int launch_pcg_l1gs(tb_pattern *pat, const double *A, const double *b, double *x, double rtol, double atol, int maxiter, int ps, int *iters, double *resnorm);
+int launch_pcg_chebyshev(tb_pattern *pat, const double *A, const double *b, double *x, double rtol, double atol, int maxiter, int degree, int *iters, double *resnorm);
 int launch_cgd_dot(tb_device *dev, int64_t n, const double *w, const double *a, const double *b, double *d_out);
 int launch_cgd_update(tb_device *dev, int64_t n, const double *w, const double *dinv, const double *p, const double *Ap, double *x, double *r,
                       const double *d_rz, const double *d_pAp, double *d_out3);
 int launch_cgd_direction(tb_device *dev, int64_t n, const double *dinv, const double *r, double *p, const double *d_rz, const double *d_rz_new);
-int launch_max(tb_device *dev, int64_t n, const double *x, int64_t stride, double *result);
-int ensure_cell_xyz(tb_mesh *m); // tb_assembly.hip: builds tb_mesh::d_cell_xyz on first use
-int launch_gather_indexed(tb_device *dev, int64_t n, const double *vec, const int32_t *idx, double *out);
-int launch_scatter_add_indexed(tb_device *dev, int64_t n, const double *in, const int32_t *idx, double *vec);
-int read_status_public(tb_device *dev); // status block → host, synchronises the stream (what check_status does when the status is not deferred)
 int launch_cgd_rotate(tb_device *dev, double *d_S);
 int launch_cgd_iteration(tb_pattern *pat, const double *A, const double *dinv, double *x, double *r, double *p, double *Ap, double *d_S);
 int launch_cg1_update(tb_device *dev, int64_t n, const double *wt, const double *dinv, const double *w, double *p, double *s, double *x, double *r,
                       double *u, double *d_S);
 int launch_cg1_fold(tb_device *dev, double *d_S);
 int launch_cg1_iteration(tb_pattern *pat, const double *A, const double *dinv, double *x, double *r, double *u, double *p, double *s, double *w, double *d_S);
-int spmv_plans(tb_pattern *p); // builds the plans tb_spmv_csr would build on its first product
-int launch_scatter_indexed(tb_device *dev, int64_t n, const double *in, const int32_t *idx, double *vec);
-int launch_spmv_rows(tb_pattern *p, const double *nz, const double *x, int64_t n, const int32_t *rows, double *out);
-int launch_mirror_bind(tb_pattern *p, const double *nz); // tb_spmv_mirror
-int ensure_aux_stream(tb_device *dev); // second queue + two events of the chunked element assemblies (tb_mechanics.hip, scalar Q2 forms)
-int launch_extract_diagonal(tb_pattern *p, const double *nz, double *diag);
-int launch_spmv_dot(tb_pattern *pat, const double *A, const double *x, double *y, double *d_dot);
-double decode_ordered_key(unsigned long long k);
 
+// ---- status block and host readback (tb_api.cpp) ----
+int read_status_public(tb_device *dev); // status block → host, synchronises the stream (what check_status does when the status is not deferred)
 int check_status(tb_device *dev);
 int reset_status(tb_device *dev);
+
+// `count` doubles from device memory to the host on the device's stream.  read_back waits for them; where launches follow the copy before the wait
+// (launch_cg's convergence look) the two halves are used apart.  No call may read back while a graph capture is open.
+inline int read_back_enqueue(tb_device *dev, double *host, const double *d_src, size_t count)
+{
+    TB_NO_CAPTURE(dev);
+    TB_HIP(hipMemcpyAsync(host, d_src, count * sizeof(double), hipMemcpyDeviceToHost, dev->stream));
+    return TB_OK;
+}
+inline int read_back_wait(tb_device *dev)
+{
+    TB_SYNC_STREAM(dev);
+    return TB_OK;
+}
+inline int read_back(tb_device *dev, double *host, const double *d_src, size_t count)
+{
+    TB_TRY(read_back_enqueue(dev, host, d_src, count));
+    return read_back_wait(dev);
+}
 
 template <class T>
 int upload(tb_device *dev, const std::vector<T> &h, T **d)

@@ -3,7 +3,6 @@
 #include "tb_mech_tet.hpp"
 
 namespace tb {
-int launch_hyperelastic_tet4(tb_form *f, tb_pattern *p, int strategy, const double *d_u, double *d_nz, double *d_r);
 
 int launch_hyperelastic_tet(tb_form *f, tb_pattern *p, int strategy, const double *d_u, double *d_nz, double *d_r)
 {

@@ -371,4 +371,6 @@ static int dispatch_tet(tb_form *f, tb_pattern *p, int strategy, const double *d
 #undef TB_TET_RUN
 }
 
+int launch_hyperelastic_tet4(tb_form *f, tb_pattern *p, int strategy, const double *d_u, double *d_nz, double *d_r); // tb_mech_tet4.hip: the first-order instances
+
 } // namespace tb

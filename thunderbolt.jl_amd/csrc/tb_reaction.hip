@@ -696,7 +696,7 @@ int launch_reaction(tb_device *dev, int model, const double *params, int n_param
     unsigned long long *key = nullptr;
     if (rmax) {
         TB_NO_CAPTURE(dev); // the largest rate goes to the host
-        key = (unsigned long long *)&dev->d_status->cell; // 8-byte scratch inside the status block
+        key = (unsigned long long *)dev->d_readback;
         TB_HIP(hipMemsetAsync(key, 0, sizeof *key, dev->stream));
     }
     int rc = TB_ERR_BAD_ARG;

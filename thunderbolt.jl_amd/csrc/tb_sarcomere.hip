@@ -333,7 +333,7 @@ int launch_sarcomere_implicit(tb_device *dev, const double *params, double *d_Q,
     const SarcomereInputs in{d_stretch, d_velocity, d_calcium, stretch, velocity, calcium};
     const int64_t n_work = d_cells ? n_cells_listed * nq : n;
     if (n_work == 0) { if (n_failed) *n_failed = 0; return TB_OK; }
-    unsigned long long *cnt = (unsigned long long *)&dev->d_status->cell; // 8-byte scratch inside the status block
+    unsigned long long *cnt = (unsigned long long *)dev->d_readback;
     TB_HIP(hipMemsetAsync(cnt, 0, sizeof *cnt, dev->stream));
     int64_t nb = (n_work + 15) / 16;
     const int64_t cap = (int64_t)dev->n_cu * 8;
