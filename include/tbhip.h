@@ -43,6 +43,7 @@ typedef struct tb_device tb_device;
 typedef struct tb_mesh tb_mesh;
 typedef struct tb_pattern tb_pattern;
 typedef struct tb_form tb_form;
+typedef struct tb_locator tb_locator;
 
 enum {
     TB_OK = 0,
@@ -175,9 +176,10 @@ const char *tb_version(void);
  * (TB_ERR_BAD_ARG) instead of invalidating it.  7: tb_cg1_update / tb_cg1_fold / tb_cg1_iteration (single-reduction CG, seven-double scalar block).
  * 8: TB_TET10, hyperelastic and facet forms on tetrahedra (TB_TET4 / TB_TET10 vector fields), tb_host_generate_grid_tet.
  * 9: tb_chamber_form_create / tb_chamber_assemble (3D–0D chamber coupling).
+ * 10: tb_locator_* (device point location and evaluation of a nodal field at the located points: nodal inter-grid interpolation).
  * A host binding compares tb_abi_revision() with the
  * TB_ABI_REVISION it was written against and refuses to run on a mismatch (julia/ThunderboltHIPBackend.jl does, in __init__) */
-#define TB_ABI_REVISION 9
+#define TB_ABI_REVISION 10
 int tb_abi_revision(void);
 
 /* ------------------------------------------------------------------ device (AbstractGPUDevice, src/devices.jl:3-4;
@@ -387,6 +389,38 @@ int tb_chamber_form_create(tb_mesh *mesh, int volume_method, const double *metho
  * Several chambers, or several facet sets of one chamber, are several calls. */
 int tb_chamber_assemble(tb_form *form, tb_pattern *pat, const double *d_u, double p, double *d_nzval, double *d_r, double *d_col, double *d_row,
                         double *d_volume);
+
+/* ------------------------------------------------------------------ point location and nodal inter-grid interpolation
+ * NodalIntergridInterpolation / transfer! (src/ferrite-addons/transfer_operators.jl:20-161), which the reference builds on Ferrite's
+ * PointEvalHandler (:116) and evaluate_at_points (:159-160); the first thing both ECG caches call (src/modeling/electrophysiology/ecg.jl:251,342).
+ * A locator holds, for n points, the source cell that contains each (int32, −1 = none) and the point's reference coordinates ξ there (3 doubles;
+ * ξ₃ = 0 on TB_QUAD4, whose points are still n×3 with z ignored).
+ * The located cell is the LOWEST-numbered source cell that contains the point within `tol`, in reference coordinates (1e-10 is the usual choice):
+ *   hexahedron / quadrilateral  all |ξₖ| ≤ 1 + tol          tetrahedron  ξₖ ≥ −tol and Σ ξₖ ≤ 1 + tol
+ * so a point on a face shared by several cells gets the same cell in every run, whatever order the search structure lists them in.  The geometry
+ * map is inverted directly on tetrahedra and by Newton's method from ξ = 0 (≤ 20 iterations, until ‖Δξ‖∞ < 1e-14) on tri- / bilinear cells; a
+ * candidate whose Jacobian is singular or inverted at an iterate does not contain the point.  A point in no cell is not an error — its cell is
+ * −1, it is counted (tb_locator_nmissing; the warning of transfer_operators.jl:118-120 is the host's to print) and it evaluates to NaN, as in
+ * Ferrite.  There is no extrapolation and no nearest-cell fallback.
+ * The search structure (a uniform grid of bins over the source mesh, built on the device) depends on `from` alone and is kept by
+ * tb_locator_relocate, which locates another set of points (any n) with it.  `from` must outlive the locator; its field kind plays no part.
+ * tb_locator_create and tb_locator_relocate read the number of missing points back: they wait for the device and refuse inside an open graph
+ * capture (TB_ERR_BAD_ARG). */
+int tb_locator_create(tb_mesh *from, int64_t n_points, const double *d_points, double tol, tb_locator **out);
+int tb_locator_relocate(tb_locator *locator, int64_t n_points, const double *d_points);
+int tb_locator_destroy(tb_locator *locator);
+int64_t tb_locator_npoints(const tb_locator *locator);
+int64_t tb_locator_nmissing(const tb_locator *locator); /* sum(x -> x === nothing, ph.cells), transfer_operators.jl:118 */
+const int32_t *tb_locator_cells_device(const tb_locator *locator); /* n_points cell ids, 0-based (ph.cells) */
+const double *tb_locator_xi_device(const tb_locator *locator);     /* n_points × 3 (ph.local_coords) */
+/* Ferrite.evaluate_at_points(ph, dh_from, u_from, field) and the indexed store of transfer! (transfer_operators.jl:153-161) in one kernel:
+ *   d_out[idx(i, c)] = Σₐ Nₐ(ξᵢ) · d_u[cell_dofs[cellᵢ, a·ncomp + c]]      idx(i, c) = d_scatter ? d_scatter[i·ncomp + c] : i·ncomp + c
+ * for every point i and component c < ncomp of `field_mesh`, a tb_mesh over the SAME grid as the locator's (same geometry kind and cell count, else
+ * TB_ERR_BAD_ARG) whose field may be of any kind: TB_QUAD4, TB_HEX8, TB_TET4, TB_HEX27, TB_TET10; ncomp 1 or 3.  The sum runs a = 0 … nb − 1 in that
+ * order: two calls give identical bits.  Points without a cell store NaN; entries of d_out that no point addresses are not touched.  d_scatter
+ * (0-based, n_points·ncomp entries, device) is the node_to_dof_map of the target.  The call only enqueues — no allocation, no wait, no
+ * read-back — and may be made inside tb_graph_begin … tb_graph_end. */
+int tb_locator_evaluate(tb_locator *locator, tb_mesh *field_mesh, const double *d_u, double *d_out, const int32_t *d_scatter);
 
 /* ------------------------------------------------------------------ pointwise sarcomere dynamics
  * Sarcomere models with internal state (src/modeling/solid/contraction.jl:337-632).  TB_SARCOMERE_RDQ20MF: 20 states per point

@@ -19,7 +19,7 @@ import Thunderbolt: AbstractGPUDevice, AbstractAssemblyStrategy, AbstractSolver,
 const libtbhip = get(ENV, "TBHIP_LIBRARY", "libtbhip.so")
 
 # revision of include/tbhip.h these ccalls were written against (TB_ABI_REVISION); a library of another revision reads / writes other buffer sizes
-const TB_ABI_REVISION = 9
+const TB_ABI_REVISION = 10
 const TB_ERR_UNSUPPORTED = Cint(-5) # include/tbhip.h
 function __init__()
     have = ccall((:tb_abi_revision, libtbhip), Cint, ())
@@ -740,6 +740,37 @@ function chamber_assemble!(form::Ptr{Cvoid}, A::Union{Nothing, HIPSparseMatrixCS
         form, A === nothing ? C_NULL : A.ddh.pattern, u.ptr, p, A === nothing ? Ptr{Float64}(C_NULL) : A.nzval.ptr,
         device_pointer_or_null(r), device_pointer_or_null(col), device_pointer_or_null(row), device_pointer_or_null(volume)))
 end
+# Point location and nodal inter-grid interpolation (src/ferrite-addons/transfer_operators.jl:20-161).  A HIPPointEvalHandler plays Ferrite's
+# PointEvalHandler for a source DeviceDofHandler: per point the lowest-numbered cell that contains it within `tol` (reference coordinates) and ξ there.
+# A Thunderbolt maintainer backs transfer! with it like this: build node_to_dof_map and the node positions exactly as transfer_operators.jl:69-114
+# does (host code, unchanged), upload `nodes` (3 × n, Float64) and Int32.(node_to_dof_map .- 1), then
+#     ph = HIPPointEvalHandler(ddh_from, nodes_dev, n);  n_missing(ph) == 0 || @warn …      (:116-120)
+#     transfer!(u_to, ph, ddh_from_field, u_from, scatter_dev)                               (:153-161; no host trip, no allocation)
+# `ddh_from_field` may carry any field over the same grid (Q1, Q2, P1, P2; 1 or 3 components).
+mutable struct HIPPointEvalHandler
+    handle::Ptr{Cvoid}
+    ddh::DeviceDofHandler      # keeps the source mesh alive: the locator reads its coordinates and connectivity
+end
+function HIPPointEvalHandler(ddh::DeviceDofHandler, points::HIPVector{Float64}, npoints::Integer; tol::Real = 1e-10)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:tb_locator_create, libtbhip), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Cdouble, Ref{Ptr{Cvoid}}), ddh.mesh, npoints, points.ptr, tol, h))
+    ph = HIPPointEvalHandler(h[], ddh)
+    finalizer(p -> (ccall((:tb_locator_destroy, libtbhip), Cint, (Ptr{Cvoid},), p.handle); p.handle = C_NULL), ph)
+    return ph
+end
+relocate!(ph::HIPPointEvalHandler, points::HIPVector{Float64}, npoints::Integer) =
+    check(ccall((:tb_locator_relocate, libtbhip), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}), ph.handle, npoints, points.ptr))
+n_points(ph::HIPPointEvalHandler) = Int(ccall((:tb_locator_npoints, libtbhip), Int64, (Ptr{Cvoid},), ph.handle))
+n_missing(ph::HIPPointEvalHandler) = Int(ccall((:tb_locator_nmissing, libtbhip), Int64, (Ptr{Cvoid},), ph.handle))
+cells_device(ph::HIPPointEvalHandler) = ccall((:tb_locator_cells_device, libtbhip), Ptr{Int32}, (Ptr{Cvoid},), ph.handle)      # 0-based, −1 = not found
+local_coords_device(ph::HIPPointEvalHandler) = ccall((:tb_locator_xi_device, libtbhip), Ptr{Float64}, (Ptr{Cvoid},), ph.handle)
+# Ferrite.evaluate_at_points(ph, dh, u): out[i·ncomp + c]; NaN where the point was not found
+evaluate_at_points!(out::HIPVector{Float64}, ph::HIPPointEvalHandler, field::DeviceDofHandler, u::HIPVector{Float64}) =
+    check(ccall((:tb_locator_evaluate, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), ph.handle, field.mesh, u.ptr, out.ptr, C_NULL))
+# Thunderbolt.transfer!(u_to, operator, u_from): u_to[node_to_dof_map] .= evaluate_at_points(…), the indexed store fused into the kernel
+transfer!(u_to::HIPVector{Float64}, ph::HIPPointEvalHandler, field::DeviceDofHandler, u_from::HIPVector{Float64}, node_to_dof_map0::HIPVector{Int32}) =
+    check(ccall((:tb_locator_evaluate, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), ph.handle, field.mesh, u_from.ptr, u_to.ptr,
+        node_to_dof_map0.ptr))
 # sarcomere models (RDQ20-MF …): explicit and implicit pointwise steps (src/modeling/solid/materials.jl:1403-1640 condenses them per quadrature point)
 function sarcomere_model_info(model::Integer)
     ns = Ref{Cint}(0); np = Ref{Cint}(0)

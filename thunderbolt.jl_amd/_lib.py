@@ -121,6 +121,14 @@ SIGNATURES = {
     "tb_facet_assemble": (C.c_int, [vp, vp, vp, C.c_double, vp, vp]),
     "tb_chamber_form_create": (C.c_int, [vp, C.c_int, c_dp, C.c_int, c_i32p, C.c_int64, C.c_int, C.POINTER(vp)]),
     "tb_chamber_assemble": (C.c_int, [vp, vp, vp, C.c_double, vp, vp, vp, vp, vp]),
+    "tb_locator_create": (C.c_int, [vp, C.c_int64, vp, C.c_double, C.POINTER(vp)]),
+    "tb_locator_relocate": (C.c_int, [vp, C.c_int64, vp]),
+    "tb_locator_destroy": (C.c_int, [vp]),
+    "tb_locator_npoints": (C.c_int64, [vp]),
+    "tb_locator_nmissing": (C.c_int64, [vp]),
+    "tb_locator_cells_device": (vp, [vp]),
+    "tb_locator_xi_device": (vp, [vp]),
+    "tb_locator_evaluate": (C.c_int, [vp, vp, vp, vp, vp]),
     "tb_host_material_eval": (C.c_int, [C.POINTER(tb_material), c_dp, c_dp, c_dp, c_dp]),
     "tb_reaction_step": (C.c_int, [vp, C.c_int, c_dp, C.c_int, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_double,
                                    C.c_double, C.c_int, C.c_double]),
@@ -213,7 +221,7 @@ def build_library(force=False):
 _lib = None
 
 
-TB_ABI_REVISION = 9   # include/tbhip.h: TB_ABI_REVISION
+TB_ABI_REVISION = 10  # include/tbhip.h: TB_ABI_REVISION
 
 
 def lib():
