@@ -44,6 +44,7 @@ typedef struct tb_mesh tb_mesh;
 typedef struct tb_pattern tb_pattern;
 typedef struct tb_form tb_form;
 typedef struct tb_locator tb_locator;
+typedef struct tb_ecg tb_ecg;
 
 enum {
     TB_OK = 0,
@@ -177,6 +178,7 @@ const char *tb_version(void);
  * 8: TB_TET10, hyperelastic and facet forms on tetrahedra (TB_TET4 / TB_TET10 vector fields), tb_host_generate_grid_tet.
  * 9: tb_chamber_form_create / tb_chamber_assemble (3Dâ€“0D chamber coupling).
  * 10: tb_locator_* (device point location and evaluation of a nodal field at the located points: nodal inter-grid interpolation).
+ * Added under 10, purely additive (no existing entry changes what it reads or writes): tb_ecg_*, tb_scrub_scale (pseudo-ECG).
  * A host binding compares tb_abi_revision() with the
  * TB_ABI_REVISION it was written against and refuses to run on a mismatch (julia/ThunderboltHIPBackend.jl does, in __init__) */
 #define TB_ABI_REVISION 10
@@ -421,6 +423,40 @@ const double *tb_locator_xi_device(const tb_locator *locator);     /* n_points Ã
  * (0-based, n_pointsÂ·ncomp entries, device) is the node_to_dof_map of the target.  The call only enqueues â€” no allocation, no wait, no
  * read-back â€” and may be made inside tb_graph_begin â€¦ tb_graph_end. */
 int tb_locator_evaluate(tb_locator *locator, tb_mesh *field_mesh, const double *d_u, double *d_out, const int32_t *d_scatter);
+
+/* ------------------------------------------------------------------ pseudo-ECG (src/modeling/electrophysiology/ecg.jl)
+ * The arithmetic of the reference's three ECG caches; the caches themselves (operators, transfer, ground constraint, solves) are the host's
+ * (thunderbolt.jl_amd/ecg.py).  A tb_ecg is Plonsey1964ECGGaussCache: it numbers the quadrature points of the form's mesh
+ * point = cell Â· n_qp + q (8 per TB_HEX8 cell, 4 per TB_TET4 cell: the rule of the diffusion assembly) and holds, per point, xÌƒ and dÎ© = detJÂ·w
+ * (built once on the device; the geometry does not change) and the flux Îºâˆ‡Ï†â‚˜ (3 doubles, zero until the first update).
+ * tb_ecg_create takes a TB_FORM_DIFFUSION form (else TB_ERR_BAD_ARG) of a scalar first-order field on a TB_HEX8 or TB_TET4 mesh, 2-point rule,
+ * no cell set (else TB_ERR_UNSUPPORTED).  D and the quadrature are the form's, as the reference takes them from op.integrator: any coefficient
+ * kind the form accepts â€” its constant tensor, or its table at the quadrature points, which is built here as the first assembly would if it has
+ * not been yet.  Forms are evaluated at their creation time (the reference passes the function `time` at ecg.jl:29 by mistake).  detJ â‰¤ 0 at a
+ * point: TB_ERR_NEG_DETJ.  The form and its mesh must outlive the cache.  Waits for the device: refused inside an open graph capture.
+ * tb_ecg_update:  flux[p] = Î£áµ¢ (D(x_q)Â·âˆ‡Náµ¢) d_phi[dof(cell, i)], i in index order; D multiplies from the left.  Overwrites the buffer (the
+ * reference's fill-then-accumulate, ecg.jl:145-146, amounts to the same).
+ * tb_ecg_evaluate:  d_out[e] = âˆ’1/(4Ï€ Îºâ‚œ) Î£_p flux[p]Â·(xÌƒ_p âˆ’ x_e)/â€–xÌƒ_p âˆ’ x_eâ€–Â³ dÎ©_p for e < n_electrodes, d_x = n_electrodes Ã— 3 doubles on the
+ * device.  All electrodes are served in one pass over the points (register tiles of 16; more electrodes pass over the points again per tile).
+ * sqrt and division are correctly rounded.  A point that coincides with an electrode gives Inf / NaN as in the reference: there is NO guard.
+ * tb_ecg_leads:  d_out[i] = Î± Î£â±¼ d_Z[iÂ·ldz + j] d_v[j], i < n_leads, j < n â‰¤ ldz â€” the per-time-step product âˆ’ZÂ·(Káµ¢Ï†â‚˜) of the lead-field
+ * method with Î± = âˆ’1; one pass reads d_v once for a tile of rows.
+ * tb_scrub_scale:  d_x[i] = Î± Â· (isnan(d_x[i]) ? 0 : d_x[i]) â€” the NaN scrub and the move to the right-hand side of the torso methods in one pass.
+ * Reproducibility: tb_ecg_evaluate and tb_ecg_leads use no floating-point atomics.  Every workgroup reduces by wave shuffles and LDS and stores its
+ * partial sums to a workspace [workgroup][output]; a second kernel adds the workgroups in index order.  The grid is min(âŒˆn / 256âŒ‰, 8 Â· CUs), a
+ * function of the point count (n) and the device only: two calls give identical bits (the reference's test asserts ==).
+ * Workspace and capture: the workspace (grid Ã— outputs doubles) belongs to the device and grows outside a capture only; a call inside
+ * tb_graph_begin â€¦ tb_graph_end that would have to grow it fails with TB_ERR_BAD_ARG (make it once with the same sizes before the capture).
+ * Otherwise tb_ecg_update, tb_ecg_evaluate, tb_ecg_leads and tb_scrub_scale only enqueue â€” no allocation, no wait, no read-back â€” so a captured
+ * time step can leave sample k at d_out + kÂ·n. */
+int tb_ecg_create(tb_form *diffusion, tb_ecg **out);            /* Plonsey1964ECGGaussCache(op, Ï†â‚˜), ecg.jl:55-69 */
+int tb_ecg_destroy(tb_ecg *ecg);
+int64_t tb_ecg_npoints(const tb_ecg *ecg);                      /* n_cells Â· n_qp, point = cell Â· n_qp + q */
+const double *tb_ecg_fluxes_device(const tb_ecg *ecg);          /* 3 doubles per point: Îºâˆ‡Ï†â‚˜ (cache.Îºâˆ‡Ï†â‚˜) */
+int tb_ecg_update(tb_ecg *ecg, const double *d_phi);            /* update_ecg! â†’ compute_quadrature_fluxes!, ecg.jl:1-37,140-147 */
+int tb_ecg_evaluate(tb_ecg *ecg, int64_t n_electrodes, const double *d_x, double kappa_t, double *d_out); /* evaluate_ecg, ecg.jl:80-137 */
+int tb_ecg_leads(tb_device *dev, int64_t n_leads, int64_t n, const double *d_Z, int64_t ldz, const double *d_v, double alpha, double *d_out); /* evaluate_ecg(::Geselowitzâ€¦), ecg.jl:617-619 */
+int tb_scrub_scale(tb_device *dev, int64_t n, double alpha, double *d_x);  /* x = Î±Â·(isnan(x) ? 0 : x): ecg.jl:345-347, 612 */
 
 /* ------------------------------------------------------------------ pointwise sarcomere dynamics
  * Sarcomere models with internal state (src/modeling/solid/contraction.jl:337-632).  TB_SARCOMERE_RDQ20MF: 20 states per point

@@ -771,6 +771,33 @@ evaluate_at_points!(out::HIPVector{Float64}, ph::HIPPointEvalHandler, field::Dev
 transfer!(u_to::HIPVector{Float64}, ph::HIPPointEvalHandler, field::DeviceDofHandler, u_from::HIPVector{Float64}, node_to_dof_map0::HIPVector{Int32}) =
     check(ccall((:tb_locator_evaluate, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), ph.handle, field.mesh, u_from.ptr, u_to.ptr,
         node_to_dof_map0.ptr))
+# ---------------------------------------------------------------- pseudo-ECG (src/modeling/electrophysiology/ecg.jl)
+# Plonsey1964ECGGaussCache on the device: x̃ and dΩ per quadrature point are built once, update_ecg! writes κ∇φₘ (3 per point, D from the left),
+# evaluate_ecg serves all electrodes in one pass.  The reductions are ordered (no floating-point atomics): two evaluations are == (test_ecg.jl).
+mutable struct HIPPlonseyECGCache{Tv}
+    handle::Ptr{Cvoid}
+    op::HIPBilinearOperator{Tv}   # keeps the diffusion form (D, quadrature) and its mesh alive
+end
+function Plonsey1964ECGGaussCache(op::HIPBilinearOperator{Tv}, φₘ::HIPVector{Tv}) where {Tv}
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:tb_ecg_create, libtbhip), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), op.form, h))
+    cache = HIPPlonseyECGCache{Tv}(h[], op)
+    finalizer(c -> (ccall((:tb_ecg_destroy, libtbhip), Cint, (Ptr{Cvoid},), c.handle); c.handle = C_NULL), cache)
+    update_ecg!(cache, φₘ)
+    return cache
+end
+n_quadrature_points(cache::HIPPlonseyECGCache) = Int(ccall((:tb_ecg_npoints, libtbhip), Int64, (Ptr{Cvoid},), cache.handle))
+fluxes_device(cache::HIPPlonseyECGCache) = ccall((:tb_ecg_fluxes_device, libtbhip), Ptr{Float64}, (Ptr{Cvoid},), cache.handle)   # cache.κ∇φₘ, 3 per point
+update_ecg!(cache::HIPPlonseyECGCache, φₘ::HIPVector{Float64}) = check(ccall((:tb_ecg_update, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}), cache.handle, φₘ.ptr))
+# evaluate_ecg(cache, x, κₜ) for `n` electrodes (x: 3 × n on the device) → out[1:n]; the reference's vector method (ecg.jl:100-106) keeps the last scalar only
+evaluate_ecg!(out::HIPVector{Float64}, cache::HIPPlonseyECGCache, x::HIPVector{Float64}, n::Integer, κₜ::Real) =
+    check(ccall((:tb_ecg_evaluate, libtbhip), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Cdouble, Ptr{Float64}), cache.handle, n, x.ptr, κₜ, out.ptr))
+# evaluate_ecg(::Geselowitz1989ECGLeadCache) = -cache.Z * cache.κ∇φₘ_t (ecg.jl:617-619) with Z dense, row-major (one lead per row of length ldz) on the device
+evaluate_leads!(out::HIPVector{Float64}, Z::HIPVector{Float64}, nleads::Integer, ldz::Integer, v::HIPVector{Float64}; α::Real = -1.0) =
+    check(ccall((:tb_ecg_leads, libtbhip), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Cdouble, Ptr{Float64}), v.dev.handle, nleads, v.n, Z.ptr, ldz, v.ptr, α, out.ptr))
+# κ∇φₘ_t[isnan.(κ∇φₘ_t)] .= 0.0; κ∇φₘ_t .*= α (ecg.jl:345-347, 612) in one pass
+scrub_scale!(x::HIPVector{Float64}, α::Real) = check(ccall((:tb_scrub_scale, libtbhip), Cint, (Ptr{Cvoid}, Int64, Cdouble, Ptr{Float64}), x.dev.handle, x.n, α, x.ptr))
+
 # sarcomere models (RDQ20-MF …): explicit and implicit pointwise steps (src/modeling/solid/materials.jl:1403-1640 condenses them per quadrature point)
 function sarcomere_model_info(model::Integer)
     ns = Ref{Cint}(0); np = Ref{Cint}(0)

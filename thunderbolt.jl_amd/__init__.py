@@ -19,3 +19,6 @@ from .chamber import (RSAFDQ2022SurrogateVolume, Hirschvogel2017SurrogateVolume,
                       prepace_circuit, RSAFDQ2022Model, RSAFDQ2022Split, RSAFDQ2022Function, semidiscretize_rsafdq, RSAFDQ2022Integrator)
 # `transfer` below is the function (transfer! of the reference); its module stays importable as thunderbolt_jl_amd.transfer through sys.modules
 from .transfer import PointEvalHandler, evaluate_at_points, NodalIntergridInterpolation, intergrid_dofs, transfer  # noqa: F401
+from . import ecg  # noqa: F401
+from .ecg import (Plonsey1964ECGGaussCache, PoissonECGReconstructionCache, Geselowitz1989ECGLeadCache, update_ecg, evaluate_ecg,  # noqa: F401
+                  get_closest_vertex, cellset_coefficient, lead_right_hand_sides, vertex_dofs, scrub_scale)

@@ -129,6 +129,14 @@ SIGNATURES = {
     "tb_locator_cells_device": (vp, [vp]),
     "tb_locator_xi_device": (vp, [vp]),
     "tb_locator_evaluate": (C.c_int, [vp, vp, vp, vp, vp]),
+    "tb_ecg_create": (C.c_int, [vp, C.POINTER(vp)]),
+    "tb_ecg_destroy": (C.c_int, [vp]),
+    "tb_ecg_npoints": (C.c_int64, [vp]),
+    "tb_ecg_fluxes_device": (vp, [vp]),
+    "tb_ecg_update": (C.c_int, [vp, vp]),
+    "tb_ecg_evaluate": (C.c_int, [vp, C.c_int64, vp, C.c_double, vp]),
+    "tb_ecg_leads": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int64, vp, C.c_double, vp]),
+    "tb_scrub_scale": (C.c_int, [vp, C.c_int64, C.c_double, vp]),
     "tb_host_material_eval": (C.c_int, [C.POINTER(tb_material), c_dp, c_dp, c_dp, c_dp]),
     "tb_reaction_step": (C.c_int, [vp, C.c_int, c_dp, C.c_int, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_double,
                                    C.c_double, C.c_int, C.c_double]),

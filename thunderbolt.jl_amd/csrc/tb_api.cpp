@@ -160,6 +160,7 @@ int tb_device_destroy(tb_device *dev)
     if (dev->d_tslot) hipFree(dev->d_tslot);
     if (dev->d_slots) hipFree(dev->d_slots);
     if (dev->d_readback) hipFree(dev->d_readback);
+    if (dev->d_ecg_ws) hipFree(dev->d_ecg_ws);
     delete dev;
     return TB_OK;
 }

@@ -683,7 +683,8 @@ static int tabulate_diffusion_field_t(tb_form *f)
     (void)hipFree(f->d_field); f->d_field = nullptr;
     return TB_OK;
 }
-int tabulate_diffusion_field(tb_form *f) { return tabulate_diffusion_field_t<Hex8<2>>(f); } // for tb_patch_fused.hip
+int tabulate_diffusion_field(tb_form *f) { return tabulate_diffusion_field_t<Hex8<2>>(f); } // for tb_patch_fused.hip, tb_ecg.hip
+int tabulate_diffusion_field_tet4(tb_form *f) { return tabulate_diffusion_field_t<Tet4<2>>(f); } // for tb_ecg.hip
 
 template <class E, int FORM>
 static int run_matrix_coef(tb_form *f, tb_pattern *p, int strategy, double t, double *d_nz)

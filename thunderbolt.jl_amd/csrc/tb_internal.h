@@ -211,6 +211,8 @@ struct tb_device {
     double *d_readback = nullptr;   // one 128-byte line: where a call that returns a scalar to the host has its kernel leave it (read_back); never the status block
     double *d_tslot = nullptr;      // {t, cos 2πt}: where time-dependent kernels read the time while a graph capture is open (tb_graph.hip)
     bool capturing = false, defer_before_capture = false, tslot_used = false; // tslot_used: a captured launch was handed the slot
+    double *d_ecg_ws = nullptr;     // [workgroup][output] partial sums of the ordered two-stage reductions of tb_ecg.hip; grows outside a graph capture only
+    size_t ecg_ws_doubles = 0;
     hipStream_t aux_stream = nullptr; // second queue of the chunked mechanics linearisation (gather of chunk k beside the integration of chunk k + 1)
     hipEvent_t aux_ev[2] = {nullptr, nullptr};
 };
@@ -371,6 +373,8 @@ int ensure_emap(tb_pattern *p);
 int ensure_cell_xyz(tb_mesh *m); // builds tb_mesh::d_cell_xyz on first use
 int launch_assemble_matrix(tb_form *f, tb_pattern *p, int strategy, double t, double *d_nz);
 int launch_assemble_vector(tb_form *f, int strategy, double t, double *d_b);
+int tabulate_diffusion_field(tb_form *f);      // first-order hexahedra: fills tb_form::d_dtab (8 points per cell) as the first assembly would
+int tabulate_diffusion_field_tet4(tb_form *f); // the same on linear tetrahedra (4 points per cell)
 // tb_mechanics.hip, tb_mech_tet.hip, tb_chamber.hip
 int launch_hyperelastic(tb_form *f, tb_pattern *p, int strategy, const double *d_u, double *d_nz, double *d_r);
 int host_material_eval_form(tb_form *form, const double *F9, double *psi, double *P, double *A);
