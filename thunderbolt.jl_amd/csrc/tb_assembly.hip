@@ -203,15 +203,37 @@ k_tabulate_isotropic(const double *__restrict__ field, int64_t n_cells, double s
     }
 }
 
+// The four source kinds, the kind known at compile time: the one definition of each closed form.  tv is the kind's time value — t for
+// norm_plus_t, cos(2πt) for cos_exp (source_time below), unused by the other two.
+template <int KIND>
+__device__ __forceinline__ double eval_source_k(const FormArgs &fa, double tv, const double (&xq)[3], int64_t cell, int q, int nq)
+{
+    static_assert(KIND == TB_SRC_CONST || KIND == TB_SRC_NORM_PLUS_T || KIND == TB_SRC_COS_EXP || KIND == TB_SRC_TABULATED, "unknown source kind");
+    if constexpr (KIND == TB_SRC_CONST) return fa.p0;
+    else if constexpr (KIND == TB_SRC_NORM_PLUS_T) return sqrt(xq[0] * xq[0] + xq[1] * xq[1] + xq[2] * xq[2]) + tv;
+    else if constexpr (KIND == TB_SRC_COS_EXP) // cos(2πt)·exp(−‖x‖²) (benchmarks-cuda-linear-form.jl:15-18); ct = cos(2πt) is uniform in space: evaluated once on the host.
+        // ‖x‖² is formed directly (the square of a square root differs from it by ≤ 2 ulp) and the exponential is the bounded-argument one.
+        return tv * exp_b(-(xq[0] * xq[0] + xq[1] * xq[1] + xq[2] * xq[2]));
+    else return fa.table[cell * nq + q];
+}
+
+// time value of a kind: from the device slot when replayed from a graph, else the launch's own scalars
+template <int KIND>
+__device__ __forceinline__ double source_time(const FormArgs &fa)
+{
+    if constexpr (KIND == TB_SRC_NORM_PLUS_T) return fa.tslot ? fa.tslot[0] : fa.t;
+    else if constexpr (KIND == TB_SRC_COS_EXP) return fa.tslot ? fa.tslot[1] : fa.ct;
+    else return 0.0;
+}
+
+// run-time kind: a switch over the compile-time forms (kernels that serve every kind with one instance)
 __device__ __forceinline__ double eval_source(const FormArgs &fa, const double (&xq)[3], int64_t cell, int q, int nq)
 {
     switch (fa.src_kind) {
-    case TB_SRC_CONST: return fa.p0;
-    case TB_SRC_NORM_PLUS_T: return sqrt(xq[0] * xq[0] + xq[1] * xq[1] + xq[2] * xq[2]) + (fa.tslot ? fa.tslot[0] : fa.t);
-    case TB_SRC_COS_EXP: // cos(2πt)·exp(−‖x‖²) (benchmarks-cuda-linear-form.jl:15-18); ct = cos(2πt) is uniform in space: evaluated once on the host.
-        // ‖x‖² is formed directly (the square of a square root differs from it by ≤ 2 ulp) and the exponential is the bounded-argument one.
-        return (fa.tslot ? fa.tslot[1] : fa.ct) * exp_b(-(xq[0] * xq[0] + xq[1] * xq[1] + xq[2] * xq[2]));
-    case TB_SRC_TABULATED: return fa.table[cell * nq + q];
+    case TB_SRC_CONST: return eval_source_k<TB_SRC_CONST>(fa, 0.0, xq, cell, q, nq);
+    case TB_SRC_NORM_PLUS_T: return eval_source_k<TB_SRC_NORM_PLUS_T>(fa, source_time<TB_SRC_NORM_PLUS_T>(fa), xq, cell, q, nq);
+    case TB_SRC_COS_EXP: return eval_source_k<TB_SRC_COS_EXP>(fa, source_time<TB_SRC_COS_EXP>(fa), xq, cell, q, nq);
+    case TB_SRC_TABULATED: return eval_source_k<TB_SRC_TABULATED>(fa, 0.0, xq, cell, q, nq);
     }
     return 0.0;
 }
@@ -503,64 +525,77 @@ struct VecPatchView {
     int max_nodes;
 };
 
-template <bool HALO>
-__global__ void __launch_bounds__(256, 3)
+// KIND: the source kind (TB_SRC_*) is a template parameter — one closed form per instance, no branch per Gauss point — and the kind's time value is
+// read once in front of the cell loop.  All eight instances fit four waves per SIMD (≤ 128 registers) without scratch memory: DESIGN.md §4.2.
+template <bool HALO, int KIND>
+__global__ void __launch_bounds__(256, 4)
 k_vector_hex8_patch(FormArgs fa, VecPatchView pv, double *__restrict__ b, Status *st)
 {
     extern __shared__ double lds[];
-    // every input of the patch is requested before anything waits: NI instances' node indices, NX coordinate values and ND dof ids per thread
-    // (8×8×8 tiles: ≤ 756 instances, ≤ 1043 nodes); larger patches fetch their surplus in place
-    constexpr int T = 256, NI = 2, NX = 13, ND = 3;
+    // the patch's coordinates are requested before anything waits: NX values per thread (8×8×8 tiles: ≤ 1043 nodes); larger patches fetch their
+    // surplus in place.  Nothing else is carried across the cell loop: an instance's node indices are read when its trip starts and again for its
+    // scatter (16 B from the cache), the dof ids at the flush — at four waves per SIMD (128 registers) the integration has none to spare for them.
+    constexpr int T = 256, NX = 13;
     const int tid = threadIdx.x;
     const uint4 h = pv.hdr[blockIdx.x];
     const int64_t e0 = h.x, n0 = h.y;
     const int nrows = (int)(h.z & 0xffff), nnodes = (int)(h.z >> 16), ne = (int)h.w;
     double *acc = lds;                 // one sum per patch node
     double *xs = lds + pv.max_nodes;   // 3 per patch node
-    uint4 lnv[NI];
-#pragma unroll
-    for (int k = 0; k < NI; ++k) lnv[k] = tid + k * T < ne ? ((const uint4 *)pv.elem_ln)[e0 + tid + k * T] : make_uint4(0, 0, 0, 0);
+    const uint4 *eln = (const uint4 *)pv.elem_ln + e0;
     const double *pc = pv.pcoord + 3 * n0;
     double xc[NX];
 #pragma unroll
     for (int j = 0; j < NX; ++j) xc[j] = tid + j * T < 3 * nnodes ? pc[tid + j * T] : 0.0;
     const int32_t *pd = pv.pdof + n0;
-    int32_t dofs[ND];
-#pragma unroll
-    for (int j = 0; j < ND; ++j) dofs[j] = tid + j * T < nrows ? pd[tid + j * T] : 0;
     for (int k = tid; k < nnodes; k += T) acc[k] = 0.0;
 #pragma unroll
     for (int j = 0; j < NX; ++j) if (tid + j * T < 3 * nnodes) xs[tid + j * T] = xc[j];
     for (int k = tid + NX * T; k < 3 * nnodes; k += T) xs[k] = pc[k];
+    const double tv = source_time<KIND>(fa);
     __syncthreads();
+    // HALO: every wave makes every trip (base < ne is uniform) and the waves add their cells' contributions in turn, a barrier between two turns: the
+    // sum of a node is then taken in one order — trip, wave, the LDS unit's own order inside one instruction — and two launches give the same bits.
+    // !HALO ends in global atomics, whose order is free anyway: its waves run unordered.
 #pragma unroll 1
-    for (int it = 0, ei = tid; ei < ne; ++it, ei += T) {
-        const uint4 l4 = it < NI ? lnv[0] : ((const uint4 *)pv.elem_ln)[e0 + ei];
-#pragma unroll
-        for (int k = 0; k + 1 < NI; ++k) lnv[k] = lnv[k + 1]; // rotate (static register indices: a run-time index would put the array in scratch memory)
-        const uint32_t ln[8] = {l4.x & 0xffffu, l4.x >> 16, l4.y & 0xffffu, l4.y >> 16, l4.z & 0xffffu, l4.z >> 16, l4.w & 0xffffu, l4.w >> 16};
-        double x[8][3];
-#pragma unroll
-        for (int a = 0; a < 8; ++a) {
-            const double *px = xs + 3 * ln[a];
-            x[a][0] = px[0]; x[a][1] = px[1]; x[a][2] = px[2];
-        }
-        int64_t cell = 0;
-        if (fa.src_kind == TB_SRC_TABULATED) cell = pv.elem_cell[e0 + ei];
+    for (int ei = tid; HALO ? ei - tid < ne : ei < ne; ei += T) {
+        const bool on = !HALO || ei < ne;
         double be[8];
-        if (!hex8_sf_source(x, [&](int q, const double(&xq)[3]) { return eval_source(fa, xq, cell, q, 8); }, be)) flag_neg_detj(st, pv.elem_cell[e0 + ei]);
+        if (on) {
+            const uint4 l4 = eln[ei];
+            const uint32_t ln[8] = {l4.x & 0xffffu, l4.x >> 16, l4.y & 0xffffu, l4.y >> 16, l4.z & 0xffffu, l4.z >> 16, l4.w & 0xffffu, l4.w >> 16};
+            double x[8][3];
 #pragma unroll
-        for (int a = 0; a < 8; ++a)
-            if (!HALO || ln[a] < (uint32_t)nrows) unsafeAtomicAdd(acc + ln[a], be[a]);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < ND; ++j)
-        if (tid + j * T < nrows) {
-            if (HALO) b[dofs[j]] = acc[tid + j * T];
-            else unsafeAtomicAdd(b + dofs[j], acc[tid + j * T]);
+            for (int a = 0; a < 8; ++a) {
+                const double *px = xs + 3 * ln[a];
+                x[a][0] = px[0]; x[a][1] = px[1]; x[a][2] = px[2];
+            }
+            int64_t cell = 0;
+            if constexpr (KIND == TB_SRC_TABULATED) cell = pv.elem_cell[e0 + ei];
+            if (!hex8_sf_source(x, [&](int q, const double(&xq)[3]) { return eval_source_k<KIND>(fa, tv, xq, cell, q, 8); }, be)) flag_neg_detj(st, pv.elem_cell[e0 + ei]);
         }
-    for (int k = tid + ND * T; k < nrows; k += T) {
+        auto scatter = [&]() {
+            // second read of the indices (the index is made opaque, or the compiler keeps the first read's four registers alive through the integration)
+            int es = ei;
+            asm volatile("" : "+v"(es));
+            const uint4 s4 = eln[es];
+            const uint32_t sn[8] = {s4.x & 0xffffu, s4.x >> 16, s4.y & 0xffffu, s4.y >> 16, s4.z & 0xffffu, s4.z >> 16, s4.w & 0xffffu, s4.w >> 16};
+#pragma unroll
+            for (int a = 0; a < 8; ++a)
+                if (!HALO || sn[a] < (uint32_t)nrows) unsafeAtomicAdd(acc + sn[a], be[a]);
+        };
+        if constexpr (HALO) {
+#pragma unroll 1
+            for (int w = 0; w < T / 64; ++w) {
+                if (on && (tid >> 6) == w) scatter();
+                __syncthreads();
+            }
+        } else {
+            scatter();
+        }
+    }
+    if constexpr (!HALO) __syncthreads(); // (HALO: the last turn ended with one)
+    for (int k = tid; k < nrows; k += T) {
         if (HALO) b[pd[k]] = acc[k];
         else unsafeAtomicAdd(b + pd[k], acc[k]);
     }
@@ -1628,6 +1663,21 @@ int launch_assemble_matrix(tb_form *f, tb_pattern *p, int strategy, double t, do
     return check_status(m->dev);
 }
 
+// One instance of the hexahedron source kernel per (HALO, kind).  Its dynamic LDS is 32 B per patch node, which the plan bounds by a third of a CU's
+// 160 KiB (ensure_vec_patch_plan) — below the 64 KiB a kernel may ask for without raising its limit, so no attribute call sits on the launch path.
+template <bool HALO, int KIND>
+static int launch_vector_hex8_patch_inst(int64_t n_patches, size_t lds, tb_device *dev, const FormArgs &fa, const VecPatchView &pv, double *d_b)
+{
+    hipLaunchKernelGGL((k_vector_hex8_patch<HALO, KIND>), dim3((unsigned)n_patches), dim3(256), lds, dev->stream, fa, pv, d_b, dev->d_status);
+    TB_HIP(hipGetLastError());
+    return TB_OK;
+}
+template <int KIND>
+static int launch_vector_hex8_patch(bool halo, int64_t n_patches, size_t lds, tb_device *dev, const FormArgs &fa, const VecPatchView &pv, double *d_b)
+{
+    return halo ? launch_vector_hex8_patch_inst<true, KIND>(n_patches, lds, dev, fa, pv, d_b) : launch_vector_hex8_patch_inst<false, KIND>(n_patches, lds, dev, fa, pv, d_b);
+}
+
 template <class E>
 static int run_vector(tb_form *f, int strategy, double t, double *d_b)
 {
@@ -1645,15 +1695,13 @@ static int run_vector(tb_form *f, int strategy, double t, double *d_b)
                 const VecPatchView pv{(const uint4 *)vp->d_hdr, vp->d_elem_ln, vp->d_elem_cell, vp->d_pcoord, vp->d_pdof, vp->max_nodes};
                 const size_t lds = (size_t)vp->max_nodes * 4 * sizeof(double);
                 if (!halo) TB_HIP(hipMemsetAsync(d_b, 0, (size_t)m->ndofs * sizeof(double), dev->stream));
-                if (halo) {
-                    TB_HIP(hipFuncSetAttribute((const void *)k_vector_hex8_patch<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    hipLaunchKernelGGL(k_vector_hex8_patch<true>, dim3((unsigned)vp->n_patches), dim3(256), lds, dev->stream, fa, pv, d_b, dev->d_status);
-                } else {
-                    TB_HIP(hipFuncSetAttribute((const void *)k_vector_hex8_patch<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    hipLaunchKernelGGL(k_vector_hex8_patch<false>, dim3((unsigned)vp->n_patches), dim3(256), lds, dev->stream, fa, pv, d_b, dev->d_status);
-                }
-                TB_HIP(hipGetLastError());
-                return TB_OK;
+                rc = fa.src_kind == TB_SRC_CONST         ? launch_vector_hex8_patch<TB_SRC_CONST>(halo, vp->n_patches, lds, dev, fa, pv, d_b)
+                     : fa.src_kind == TB_SRC_NORM_PLUS_T ? launch_vector_hex8_patch<TB_SRC_NORM_PLUS_T>(halo, vp->n_patches, lds, dev, fa, pv, d_b)
+                     : fa.src_kind == TB_SRC_COS_EXP     ? launch_vector_hex8_patch<TB_SRC_COS_EXP>(halo, vp->n_patches, lds, dev, fa, pv, d_b)
+                     : fa.src_kind == TB_SRC_TABULATED   ? launch_vector_hex8_patch<TB_SRC_TABULATED>(halo, vp->n_patches, lds, dev, fa, pv, d_b)
+                                                         : TB_ERR_BAD_ARG;
+                if (rc == TB_ERR_BAD_ARG) set_error("vector assembly: unknown source kind %d", fa.src_kind);
+                return rc;
             }
             if (rc != TB_ERR_UNSUPPORTED) return rc; // unsupported layouts: the general kernels below
         }
