@@ -27,6 +27,7 @@
  *   TB_PATCH_ISO = 0                              constant positive definite tensors through the DIAG / general instances instead of the ISO one
  *   TB_SPMV_KERNEL = rows                         CSR rows kernel also where the pattern compresses (what patterns without shared signatures run)
  *   TB_MECH_CHUNKS = n                            launches of the chunked Q2 linearisation (0 / 1: one)
+ *   TB_NEWMARK_STAGE = rows                       tb_newmark_stage runs its fused general CSR kernel on every pattern (read at a pattern's first stage call)
  *   TB_PLAN_VERBOSE = 1                           plan statistics on stderr;   TB_RCCL_LIBRARY = path   the RCCL to open
  * Tuning and comparison switches of earlier rounds exist in the profiling build only (make -C thunderbolt.jl_amd/csrc ablation).
  */
@@ -66,7 +67,11 @@ enum { TB_QUAD4 = 2 /* bilinear quadrilateral in the plane z = 0 (2-D problems; 
  * Quadrature of the mechanics path on tetrahedra: TB_TET4 displacement — the 4-point degree-2 rule (points (a,a,a,1−3a), a = 0.1381966…,
  * weights 1/24); TB_TET10 — Keast's 8-point degree-3 rule (Keast 1986; two orbits (a,a,a,1−3a), a = 0.328054696711427 and 0.106952273932930,
  * weights 0.138527966511862 and 0.111472033488138 of the volume: all positive, unlike the 5-point rule with its negative centroid weight).
- * Triangular facets: the 3-point degree-2 rule (interior points (1/6,1/6,2/3)) for TB_TET4, Dunavant's 6-point degree-4 rule for TB_TET10. */
+ * Triangular facets: the 3-point degree-2 rule (interior points (1/6,1/6,2/3)) for TB_TET4, Dunavant's 6-point degree-4 rule for TB_TET10.
+ * Quadrature of the vector mass (TB_FORM_MASS, ncomp = 3) on tetrahedra, exact for the integrand NᵢNⱼ of degree 2p: TB_TET4 — the 4-point degree-2 rule
+ * above; TB_TET10 — Keast's 11-point degree-4 rule (Keast 1986): the centroid with weight −74/5625, four points (a,a,a,1−3a), a = 1/14, weight 343/45000,
+ * six points (b,b,c,c), b, c = (1 ± √(5/14))/4, weight 56/2250 (weights as fractions of the unit cube: they sum to the reference volume 1/6).  The
+ * centroid weight is negative; the element mass matrix stays positive definite because the rule is exact for it. */
 
 /* assembly strategies — device analogues of the FerriteOperators strategies Thunderbolt re-exports
  * (src/Thunderbolt.jl:22-32; selected via FiniteElementDiscretization(; assembly_strategy), src/discretization/fem.jl:38-46) */
@@ -179,6 +184,8 @@ const char *tb_version(void);
  * 9: tb_chamber_form_create / tb_chamber_assemble (3D–0D chamber coupling).
  * 10: tb_locator_* (device point location and evaluation of a nodal field at the located points: nodal inter-grid interpolation).
  * Added under 10, purely additive (no existing entry changes what it reads or writes): tb_ecg_*, tb_scrub_scale (pseudo-ECG).
+ * Added under 10, purely additive: tb_newmark_predict / _stage / _correct, tb_hermite_interpolate (Newmark elastodynamics); tb_assemble_matrix accepts
+ * the mass form of a 3-component field, which it used to refuse (scalar calls are unchanged).
  * A host binding compares tb_abi_revision() with the
  * TB_ABI_REVISION it was written against and refuses to run on a mismatch (julia/ThunderboltHIPBackend.jl does, in __init__) */
 #define TB_ABI_REVISION 10
@@ -260,6 +267,14 @@ int tb_form_set_table(tb_form *form, const double *values, int64_t n);
  * update_operator!(op, t) for bilinear operators → fills op.A's nzval
  * (src/solver/time/euler.jl:172-176; canonical loop src/modeling/core/coordinate_systems.jl:145-171) */
 int tb_assemble_matrix(tb_form *form, tb_pattern *pat, int strategy, double t, double *d_nzval);
+/* Vector mass.  On a mesh with ncomp = 3 the TB_FORM_MASS form is Mₑ[(i,c),(j,d)] = ρ NᵢNⱼ δ_cd dΩ — mass.jl:28-43 with vector shape functions (Nᵢ ⋅ Nⱼ),
+ * the mass operator of setup_stage_operator (src/solver/time/newmark.jl:400-401).  Field kinds TB_HEX8, TB_HEX27, TB_TET4, TB_TET10; coefficients
+ * TB_COEF_CONST_SCALAR and TB_COEF_FIELD_SCALAR (first-order nodal density per cell, n_cells × 8 on hexahedra, n_cells × 4 on tetrahedra: a density per
+ * subdomain).  qorder on hexahedra as for the scalar forms (0 → max(2p−1, 2)); on tetrahedra the rule is the one named with the cell kinds, whatever
+ * qorder says.  Only the three same-component entries of a node pair are written, through the pattern's cell → nz map; every other entry of the
+ * pattern is exactly 0.0.  The dof table is the caller's (no dof = 3·node + c assumption).  TB_STRATEGY_ATOMIC: hardware atomics;
+ * TB_STRATEGY_PER_COLOR, TB_STRATEGY_ELEMENT and TB_STRATEGY_PATCH: colour by colour, an ordered sum (two assemblies give identical bits).  Cell sets
+ * and the diffusion form on 3-component fields: TB_ERR_UNSUPPORTED.  tb_last_kernel_name: "k_vector_mass<atomic>" / "k_vector_mass<colours>". */
 /* The heat stage's set-up assembles the mass and the diffusion operator of one DofHandler back to back on the shared
  * sparsity pattern (update_operator!(cache.M, t); update_operator!(cache.K, t), src/solver/time/euler.jl:172-176, pattern
  * sharing :110-116): one pass over the mesh fills both nzval arrays (geometry and scatter metadata read once).  Results are
@@ -716,6 +731,36 @@ int tb_meandiag(tb_pattern *pat, const double *d_nzval, double *result);
 /* signed maximum of a strided slice: exactly `maximum(@view dumat[:, φₘidx])` of get_reaction_tangent
  * (src/solver/time/rtc.jl:64-73 — no absolute value there).  n == 0 yields −∞. */
 int tb_max(tb_device *dev, int64_t n, const double *d_x, int64_t stride, double *result);
+
+/* ------------------------------------------------------------------ Newmark-β elastodynamics, M ü + f_int(u) = f_ext (src/solver/time/newmark.jl)
+ * The arithmetic of one fixed Newmark step in the structural numbering; the stage operator, the initial acceleration and the step itself are the host's
+ * (thunderbolt.jl_amd/dynamics.py).  All four entries only enqueue on the device's stream — no allocation, no wait, no read-back — and may be captured
+ * (tb_newmark_stage examines the pattern at its first call: make that call before a capture; inside one it runs the general kernel on a pattern it has
+ * not seen).  Vectors are n doubles on the device.
+ * tb_newmark_predict:  ũ = uₙ + Δt vₙ + (½−β)Δt² aₙ,  ṽ = vₙ + (1−γ)Δt aₙ (newmark.jl:580-581), one pass.
+ * tb_newmark_stage:    r += c·M(u−ũ) (newmark.jl:89-101) and Jnz += c·Mnz (:105-110) with c = 1/(βΔt²) > 0, in ONE pass over the rows of M; d_Jnz or d_r
+ *   may be NULL (only the other is computed; d_u and d_utilde may then be NULL with d_r).  A lane group per row, row sums by wave shuffles, no
+ *   floating-point atomics: two calls give identical bits.  Where the pattern is a CSR of 3×3 blocks AND the dof table numbers every field node's
+ *   components 3k, 3k + 1, 3k + 2 (both examined once, at the pattern's first stage call), the blocks of a vector mass as tb_assemble_matrix leaves it
+ *   are m·I₃ and the block kernel runs: it reads one entry of M per block and rewrites the three diagonal entries of the block in J.  d_Mnz must then
+ *   be such a mass.  Every other pattern runs the composition the stage was measured against, which assumes nothing of M: d = u − ũ into a workspace
+ *   of the pattern (allocated at that first call), r += c·M·d by the pattern's SpMV, J += c·M entry-wise — the fused general kernel (a lane group per
+ *   row, column index and both gathers per non-zero) was slower than it at one of four sizes and is kept behind TB_NEWMARK_STAGE=rows for measurement.
+ *   A pattern first seen inside an open capture runs that fused general kernel (it needs no workspace).
+ *   tb_last_kernel_name names the path: "k_newmark_stage_b3", "newmark stage composition: …" or "k_newmark_stage_csr".  Bad arguments (NULL pattern or mass, c ≤ 0 or not finite,
+ *   aliasing outputs): TB_ERR_BAD_ARG.
+ * tb_newmark_correct:  aₙ₊₁ = (u−ũ)/(βΔt²),  vₙ₊₁ = ṽ + γΔt aₙ₊₁ (newmark.jl:91-95, 171-180, 599-601), one pass.
+ * tb_hermite_interpolate:  out = the `derivative`-th time derivative (0, 1, 2) at θ = (t − tₙ₋₁)/Δt of the cubic through (u₀, v₀) and (u₁, v₁), weights of
+ *   _hermite_weights (newmark.jl:369-379): D = 0: (2θ³−3θ²+1, Δt(θ³−2θ²+θ), −2θ³+3θ², Δt(θ³−θ²)); D = 1: ((6θ²−6θ)/Δt, 3θ²−4θ+1, (−6θ²+6θ)/Δt, 3θ²−2θ);
+ *   D = 2: ((12θ−6)/Δt², (6θ−4)/Δt, (−12θ+6)/Δt², (6θ−2)/Δt).  At θ = 0 and 1 the D = 0 and D = 1 weights are exactly (1,0,0,0) / (0,1,0,0) and
+ *   (0,0,1,0) / (0,0,0,1): the end points are reproduced bit for bit. */
+int tb_newmark_predict(tb_device *dev, int64_t n, double dt, double beta, double gamma, const double *d_u, const double *d_v, const double *d_a,
+                       double *d_utilde, double *d_vtilde);
+int tb_newmark_stage(tb_pattern *pat, const double *d_Mnz, double c, const double *d_u, const double *d_utilde, double *d_Jnz, double *d_r);
+int tb_newmark_correct(tb_device *dev, int64_t n, double dt, double beta, double gamma, const double *d_u, const double *d_utilde, const double *d_vtilde,
+                       double *d_a, double *d_v);
+int tb_hermite_interpolate(tb_device *dev, int64_t n, double theta, double dt, int derivative, const double *d_u0, const double *d_v0, const double *d_u1,
+                           const double *d_v1, double *d_out);
 
 /* ------------------------------------------------------------------ Float32 value type
  * The reference types its device path by value_type(device) and its own GPU tests run Float32 (ext/CuThunderboltExt.jl:126-127,

@@ -798,6 +798,27 @@ evaluate_leads!(out::HIPVector{Float64}, Z::HIPVector{Float64}, nleads::Integer,
 # κ∇φₘ_t[isnan.(κ∇φₘ_t)] .= 0.0; κ∇φₘ_t .*= α (ecg.jl:345-347, 612) in one pass
 scrub_scale!(x::HIPVector{Float64}, α::Real) = check(ccall((:tb_scrub_scale, libtbhip), Cint, (Ptr{Cvoid}, Int64, Cdouble, Ptr{Float64}), x.dev.handle, x.n, α, x.ptr))
 
+# ---------------------------------------------------------------- Newmark-β elastodynamics (src/solver/time/newmark.jl)
+# The mass operator of the displacement field is an ordinary HIPBilinearOperator: tb_assemble_matrix accepts BilinearMassIntegrator on ncomp = 3.
+# ũ = uₙ + Δt vₙ + (½−β)Δt² aₙ, ṽ = vₙ + (1−γ)Δt aₙ (newmark.jl:580-581)
+newmark_predict!(ũ::HIPVector{Float64}, ṽ::HIPVector{Float64}, u::HIPVector{Float64}, v::HIPVector{Float64}, a::HIPVector{Float64}, Δt::Real, β::Real, γ::Real) =
+    check(ccall((:tb_newmark_predict, libtbhip), Cint, (Ptr{Cvoid}, Int64, Cdouble, Cdouble, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        u.dev.handle, u.n, Δt, β, γ, u.ptr, v.ptr, a.ptr, ũ.ptr, ṽ.ptr))
+# _add_inertia_residual! and _add_inertia_linearization! (newmark.jl:97-110) in one pass over M: residual += M(u−ũ)/(βΔt²), J += M/(βΔt²); either output may be `nothing`
+function newmark_stage!(J::Union{HIPSparseMatrixCSR{Float64}, Nothing}, residual::Union{HIPVector{Float64}, Nothing}, M::HIPSparseMatrixCSR{Float64}, u::HIPVector{Float64},
+                        ũ::HIPVector{Float64}, βΔt²::Real)
+    check(ccall((:tb_newmark_stage, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        M.ddh.pattern, M.nzval.ptr, inv(βΔt²), u.ptr, ũ.ptr, J === nothing ? C_NULL : J.nzval.ptr, residual === nothing ? C_NULL : residual.ptr))
+end
+# aₙ₊₁ = (u−ũ)/(βΔt²), vₙ₊₁ = ṽ + γΔt aₙ₊₁ (newmark.jl:91-95, 171-180)
+newmark_correct!(a::HIPVector{Float64}, v::HIPVector{Float64}, u::HIPVector{Float64}, ũ::HIPVector{Float64}, ṽ::HIPVector{Float64}, Δt::Real, β::Real, γ::Real) =
+    check(ccall((:tb_newmark_correct, libtbhip), Cint, (Ptr{Cvoid}, Int64, Cdouble, Cdouble, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        u.dev.handle, u.n, Δt, β, γ, u.ptr, ũ.ptr, ṽ.ptr, a.ptr, v.ptr))
+# _newmark_hermite! (newmark.jl:305-382) on the displacement block: D-th derivative of the cubic through (uprev, vprev), (u, v) at θ = (t − tprev)/Δt
+hermite_interpolate!(out::HIPVector{Float64}, θ::Real, Δt::Real, D::Integer, uprev::HIPVector{Float64}, vprev::HIPVector{Float64}, u::HIPVector{Float64}, v::HIPVector{Float64}) =
+    check(ccall((:tb_hermite_interpolate, libtbhip), Cint, (Ptr{Cvoid}, Int64, Cdouble, Cdouble, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        out.dev.handle, out.n, θ, Δt, D, uprev.ptr, vprev.ptr, u.ptr, v.ptr, out.ptr))
+
 # sarcomere models (RDQ20-MF …): explicit and implicit pointwise steps (src/modeling/solid/materials.jl:1403-1640 condenses them per quadrature point)
 function sarcomere_model_info(model::Integer)
     ns = Ref{Cint}(0); np = Ref{Cint}(0)

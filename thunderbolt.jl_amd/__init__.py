@@ -22,3 +22,5 @@ from .transfer import PointEvalHandler, evaluate_at_points, NodalIntergridInterp
 from . import ecg  # noqa: F401
 from .ecg import (Plonsey1964ECGGaussCache, PoissonECGReconstructionCache, Geselowitz1989ECGLeadCache, update_ecg, evaluate_ecg,  # noqa: F401
                   get_closest_vertex, cellset_coefficient, lead_right_hand_sides, vertex_dofs, scrub_scale)
+from . import dynamics  # noqa: F401
+from .dynamics import ElastodynamicsModel, NewmarkSolver, NewmarkStageOperator, NewmarkIntegrator, Dirichlet, LinearMaxwellMaterial  # noqa: F401

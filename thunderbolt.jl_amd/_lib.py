@@ -137,6 +137,10 @@ SIGNATURES = {
     "tb_ecg_evaluate": (C.c_int, [vp, C.c_int64, vp, C.c_double, vp]),
     "tb_ecg_leads": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int64, vp, C.c_double, vp]),
     "tb_scrub_scale": (C.c_int, [vp, C.c_int64, C.c_double, vp]),
+    "tb_newmark_predict": (C.c_int, [vp, C.c_int64, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp]),
+    "tb_newmark_stage": (C.c_int, [vp, vp, C.c_double, vp, vp, vp, vp]),
+    "tb_newmark_correct": (C.c_int, [vp, C.c_int64, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp]),
+    "tb_hermite_interpolate": (C.c_int, [vp, C.c_int64, C.c_double, C.c_double, C.c_int, vp, vp, vp, vp, vp]),
     "tb_host_material_eval": (C.c_int, [C.POINTER(tb_material), c_dp, c_dp, c_dp, c_dp]),
     "tb_reaction_step": (C.c_int, [vp, C.c_int, c_dp, C.c_int, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_double,
                                    C.c_double, C.c_int, C.c_double]),

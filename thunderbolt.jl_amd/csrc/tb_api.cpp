@@ -439,7 +439,7 @@ int tb_pattern_destroy(tb_pattern *p)
 {
     if (!p) return TB_OK;
     { std::lock_guard<std::mutex> lock(g_mirrored_mutex); g_mirrored.erase(std::remove(g_mirrored.begin(), g_mirrored.end(), p), g_mirrored.end()); }
-    hipFree(p->d_rowptr); hipFree(p->d_colidx); hipFree(p->d_blkrow); hipFree(p->d_blkrec); hipFree(p->d_rowsig); hipFree(p->d_sigoff); hipFree(p->d_wrunrec); for (double *q : p->d_mir) hipFree(q); hipFree(p->d_mir_base); hipFree(p->d_mir_off); hipFree(p->d_bcol); hipFree(p->d_diagpos); hipFree(p->d_emap); hipFree(p->d_blockpos); hipFree(p->d_krylov_ws); hipFree(p->d_q2pos); hipFree(p->d_q2pos_t); hipFree(p->d_kebuf); hipFree(p->d_qpbuf); hipFree(p->d_gnodes);
+    hipFree(p->d_rowptr); hipFree(p->d_colidx); hipFree(p->d_blkrow); hipFree(p->d_blkrec); hipFree(p->d_rowsig); hipFree(p->d_sigoff); hipFree(p->d_wrunrec); for (double *q : p->d_mir) hipFree(q); hipFree(p->d_mir_base); hipFree(p->d_mir_off); hipFree(p->d_bcol); hipFree(p->d_diagpos); hipFree(p->d_emap); hipFree(p->d_blockpos); hipFree(p->d_krylov_ws); hipFree(p->d_q2pos); hipFree(p->d_q2pos_t); hipFree(p->d_kebuf); hipFree(p->d_qpbuf); hipFree(p->d_gnodes); hipFree(p->d_stage_d);
     free_patch_mat_plan(p);
     free_patch_fused_plan(p);
     delete p;
@@ -461,8 +461,8 @@ int tb_form_create(tb_mesh *mesh, int form_kind, int qorder, const tb_coef *coef
     auto f = std::make_unique<tb_form>();
     f->mesh = mesh; f->kind = form_kind; f->qorder = qorder; f->coef = *coef; f->coef.field = nullptr;
     // field coefficients are first-order nodal data per cell (coefficients.jl:85-99): the cell's own basis for first-order fields, the
-    // eight geometry nodes for the quadratic field
-    const int nb = mesh->field_kind == TB_HEX27 ? 8 : mesh->nb;
+    // geometry nodes (eight / four) for the quadratic fields
+    const int nb = mesh->field_kind == TB_HEX27 ? 8 : mesh->field_kind == TB_TET10 ? 4 : mesh->nb;
     int64_t need_field = 0;
     if (form_kind == TB_FORM_MASS) {
         TB_REQUIRE(coef->kind == TB_COEF_CONST_SCALAR || coef->kind == TB_COEF_FIELD_SCALAR, "mass form: coefficient kind %d", coef->kind);
@@ -539,7 +539,6 @@ int tb_assemble_matrix(tb_form *form, tb_pattern *pat, int strategy, double t, d
     TB_REQUIRE(form && pat && (d_nzval || pat->nnz == 0), "tb_assemble_matrix: NULL argument");
     TB_REQUIRE(form->mesh == pat->mesh, "tb_assemble_matrix: form and pattern belong to different meshes");
     TB_REQUIRE(form->kind == TB_FORM_MASS || form->kind == TB_FORM_DIFFUSION, "tb_assemble_matrix: form is not bilinear");
-    TB_REQUIRE(form->mesh->ncomp == 1, "tb_assemble_matrix: scalar fields only");
     TB_REQUIRE(strategy >= TB_STRATEGY_ATOMIC && strategy <= TB_STRATEGY_PATCH, "tb_assemble_matrix: unknown strategy %d", strategy);
     TB_HIP(hipSetDevice(form->mesh->dev->id));
     mirror_drop(pat, d_nzval);
@@ -547,6 +546,7 @@ int tb_assemble_matrix(tb_form *form, tb_pattern *pat, int strategy, double t, d
         if (pat->nnz) TB_HIP(hipMemsetAsync(d_nzval, 0, sizeof(double) * (size_t)pat->nnz, form->mesh->dev->stream));
         return TB_OK;
     }
+    if (form->mesh->ncomp == 3) return launch_assemble_vector_mass(form, pat, strategy, d_nzval); // the mass of the displacement field (tb_newmark.hip)
     return launch_assemble_matrix(form, pat, strategy, t, d_nzval);
 }
 

@@ -258,6 +258,9 @@ struct tb_pattern {
     double last_tol = 0.0;          // atol + rtol·‖r₀‖ of the latest Krylov solve on this pattern (tb_solver_last_tolerance)
     int32_t *d_bcol = nullptr;      // block SpMV of 3-dof-per-node patterns: one column (node) index per 3×3 block
     int b3 = 0, b3_lanes = 16;      // b3: 0 = not examined, 1 = CSR of 3×3 blocks, −1 = not
+    int stage_path = 0;             // tb_newmark_stage: 0 = not examined, 1 = block kernel (3×3 blocks AND every node's dofs 3k, 3k+1, 3k+2 in component order),
+                                    // 2 = fused general kernel (TB_NEWMARK_STAGE=rows), 3 = composition (vector kernel, SpMV, axpy) with d_stage_d
+    double *d_stage_d = nullptr;    // u − ũ of the composition path (n_rows doubles)
     int64_t *d_diagpos = nullptr;   // nz index of each row's diagonal entry (−1 if absent), built at the first Jacobi-preconditioned solve
     int32_t *d_blkrow = nullptr;    // stream SpMV: first row of each workgroup's run of rows (n_blk + 1 entries)
     uint32_t *d_blkrec = nullptr;   // the same runs as 16-byte records {first row, rows | entries << 16, first nz low, high} (k_spmv_stream_rec)
@@ -384,6 +387,8 @@ int ensure_blockpos(tb_pattern *p);
 int launch_hyperelastic_tet(tb_form *f, tb_pattern *p, int strategy, const double *d_u, double *d_nz, double *d_r);
 int launch_facets_tet(tb_form *f, tb_pattern *p, const double *d_u, double *d_nz, double *d_r);
 int launch_chamber(tb_form *f, tb_pattern *p, const double *d_u, double pressure, double *d_nz, double *d_r, double *d_col, double *d_row, double *d_volume);
+// tb_newmark.hip
+int launch_assemble_vector_mass(tb_form *f, tb_pattern *p, int strategy, double *d_nz); // TB_FORM_MASS on a 3-component field
 // tb_reaction.hip
 int launch_reaction(tb_device *dev, int model, const double *params, int n_params, double *d_u, double *d_du,
                     int64_t n_points, int layout, double t, double dt, int substeps, double thr, double *rmax /*nullable, host*/,

@@ -653,6 +653,7 @@ def update_linearization(op, u, t=0.0, residual=None):
     """update_linearization!(op, residual, u, p) / update_linearization!(op, u, p) (newton_raphson.jl:238): volume terms of every
     subdomain, then the surface terms, all accumulated into the same J / residual."""
     _sync_active_tension(op, t)
+    op.J_includes_inertia = False     # J is rewritten: a stage operator that adds M/(βΔt²) to it afterwards (dynamics.py) sets this again
     for form, _ in op.forms:
         check(lib().tb_linearize(form, op.pattern.h, op.strategy.code, _ptr(u), float(t), op.J.ptr, _ptr(residual)))
     for h in op.facet_forms:
