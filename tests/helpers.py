@@ -11,6 +11,48 @@ def rel_err(got, ref):
     return max(np.linalg.norm(d) / scale2, d.max() / scalem)
 
 
+def per_state_err(got, ref, nstates, n, layout):
+    """One figure per state of a pointwise ODE array: max over the points of |got − ref| of that state, relative to max over the points of |ref| of that
+    state.  `layout` is "SOA" (u[k·n + i]) or "AOS" (u[i·nstates + k]).  A state whose reference is zero at every point has no scale: it has to be exactly
+    zero in `got` (figure 0), anything else is reported as inf.  A NaN in `got` gives a NaN figure, which fails every `<` it is asserted with."""
+    got, ref = np.asarray(got, dtype=np.float64).ravel(), np.asarray(ref, dtype=np.float64).ravel()
+    assert got.size == ref.size
+    return per_state_ratio(np.abs(got - ref), ref, nstates, n, layout)
+
+
+def per_state_ratio(dev, ref, nstates, n, layout):
+    """per_state_err for a deviation given entry by entry (`dev` ≥ 0): max over the points of dev, by max over the points of |ref|, for every state"""
+    assert layout in ("SOA", "AOS")
+    dev, ref = np.asarray(dev, dtype=np.float64).ravel(), np.asarray(ref, dtype=np.float64).ravel()
+    assert dev.size == ref.size == nstates * n
+    d, r = (dev.reshape(nstates, n), ref.reshape(nstates, n)) if layout == "SOA" else (dev.reshape(n, nstates).T, ref.reshape(n, nstates).T)
+    out = np.empty(nstates)
+    for k in range(nstates):
+        dmax = np.nan if np.isnan(d[k]).any() else (d[k].max() if n else 0.0)      # (ndarray.max propagates a NaN as well; spelt out because the tests rely on it)
+        scale = np.abs(r[k]).max() if n else 0.0
+        out[k] = dmax / scale if scale > 0.0 else (0.0 if dmax == 0.0 else dmax * np.inf)
+    return out
+
+
+# The protocols of the reaction parity tests (tests/test_gpu_parity.py), by number of states: forward-Euler Δt, adaptive sub-stepper Δt and threshold,
+# and the Rush–Larsen Δt of the models that have a gate decomposition (PCG2019 7 states, TT06 19, O'Hara–Rudy 41)
+FE_DT = {2: 0.1, 7: 0.01, 19: 0.001, 41: 0.002}
+ADAPTIVE_DT = {2: 0.05, 7: 0.05, 19: 0.007, 41: 0.007}
+ADAPTIVE_THRESHOLD = {2: 0.05, 7: 1.0, 19: 20.0, 41: 20.0}
+RL_DT = {7: 0.05, 19: 0.02, 41: 0.01}
+
+
+def phi_rates(oracle, oid, params, u, nstates, n, layout, phi, xs=None):
+    """dφₘ/dt of every point of the flat state array `u` (left unchanged), from the oracle's cell_rhs: what the adaptive sub-stepper compares with its threshold.
+    With coordinates (`xs`) the rate is the one the oracle's forward-Euler step reports for a copy of `u`: cell_rhs takes no coordinate."""
+    u = np.asarray(u, dtype=np.float64)
+    if xs is not None:
+        du = oracle.reaction_step_x(oid, params, u.copy(), n, xs, getattr(oracle, "LAYOUT_" + layout), t=0.0, dt=0.0, substeps=1, threshold=0.0)
+        return (du.reshape(nstates, n)[phi] if layout == "SOA" else du.reshape(n, nstates)[:, phi]).copy()
+    pts = u.reshape(nstates, n).T if layout == "SOA" else u.reshape(n, nstates)
+    return np.array([oracle.cell_rhs(oid, params, np.ascontiguousarray(p))[phi] for p in pts])
+
+
 def hex_to_tets(xyz, conn):
     """Split every hexahedron into 6 positively oriented tetrahedra around the 0–6 diagonal."""
     T = [(0, 1, 2, 6), (0, 2, 3, 6), (0, 3, 7, 6), (0, 7, 4, 6), (0, 4, 5, 6), (0, 5, 1, 6)]

@@ -1,5 +1,5 @@
-// Host build of thunderbolt.jl_amd/csrc/tb_math.hpp for tests/test_tt06_derived_constants.py: largest error, in units of the last place of the
-// exact result, of exp_b and rsqrt_b against long double (64-bit significand: the truth is good to 2⁻¹¹ of a double's last place), next to the
+// Host build of thunderbolt.jl_amd/csrc/tb_math.hpp for tests/test_tt06_derived_constants.py: the values of all five functions (eval_*), and the largest
+// error, in units of the last place of the exact result, of exp_b and rsqrt_b against long double (64-bit significand: the truth is good to 2⁻¹¹ of a double's last place), next to the
 // same figure of the forms they replace, measured in the same run on the same arguments.
 #include <cmath>
 
@@ -48,5 +48,10 @@ double max_ulps_exp_b(const double *x, long n) { return max_ulps(x, n, [](double
 double max_ulps_exp_b_before(const double *x, long n) { return max_ulps(x, n, [](double v) { return before::exp_b(v); }, [](double v) { return expl((long double)v); }); }
 double max_ulps_rsqrt_b(const double *x, long n) { return max_ulps(x, n, [](double v) { return tb::rsqrt_b(v); }, [](double v) { return 1.0L / sqrtl((long double)v); }); }
 double max_ulps_rsqrt_before(const double *x, long n) { return max_ulps(x, n, [](double v) { return before::rsqrt(v); }, [](double v) { return 1.0L / sqrtl((long double)v); }); }
+// y[i] = f(x[i]): the values themselves, for the comparison with the device build (tests/tb_math_device.hip) and for errors measured by the caller
 void eval_exp_b(const double *x, long n, double *y) { for (long i = 0; i < n; ++i) y[i] = tb::exp_b(x[i]); }
+void eval_rcp_b(const double *x, long n, double *y) { for (long i = 0; i < n; ++i) y[i] = tb::rcp_b(x[i]); }
+void eval_rsqrt_b(const double *x, long n, double *y) { for (long i = 0; i < n; ++i) y[i] = tb::rsqrt_b(x[i]); }
+void eval_log_b(const double *x, long n, double *y) { for (long i = 0; i < n; ++i) y[i] = tb::log_b(x[i]); }
+void eval_expm1_b(const double *x, long n, double *y) { for (long i = 0; i < n; ++i) y[i] = tb::expm1_b(x[i]); }
 }

@@ -3,7 +3,9 @@ lower-degree exp_b (tb_math.hpp).
 
 GPU cases: every kernel form that reads the derived block against the CPU oracle at the suite's per-step tolerance (1e-12 of the largest
 reference entry, tests/test_gpu_parity.py: TOL / rel_err), on point counts at the wave and workgroup edges of the grid-stride loop.
-Host case: exp_b and rsqrt_b compiled for the host and measured against long double next to the forms they replace."""
+Host case: exp_b and rsqrt_b compiled for the host and measured against long double next to the forms they replace.
+Device math: exp_b, rcp_b, rsqrt_b, log_b and expm1_b evaluated by a kernel each (tests/tb_math_device.hip, built with the library's flags) against the host
+build and long double: the hardware seeds of rcp_b and rsqrt_b exist on the device only, the host build stands in for them."""
 import ctypes as C
 import os
 import subprocess
@@ -213,3 +215,136 @@ def test_exp_b_and_rsqrt_b_are_no_less_accurate_than_what_they_replace(tmp_path)
     new, old = fns["max_ulps_rsqrt_b"](y), fns["max_ulps_rsqrt_before"](y)
     print("rsqrt_b: %.4f ulp, 1/sqrt %.4f ulp (%d arguments)" % (new, old, len(y)))
     assert new <= old and new <= 2.0
+
+
+# ------------------------------------------------------------------------------------------- the math functions on the device
+LD = np.longdouble
+NARG = 2 ** 18
+HALF_SQRT2 = 0.70710678118654752                    # the cut of log_b's mantissa range [√½, √2)
+FUNCTIONS = ("exp_b", "rcp_b", "rsqrt_b", "log_b", "expm1_b")      # in the order of the enum of tests/tb_math_device.hip
+
+
+def _spread_ulps(rng, centre, count, width):
+    """`centre` moved by a whole number of units in the last place, −width … width"""
+    return centre * (1.0 + rng.integers(-width, width + 1, count) * 2.0 ** -52)
+
+
+@pytest.fixture(scope="module")
+def math_args():
+    """2¹⁸ arguments per function, fixed seed, only where the function is defined (tb_math.hpp)"""
+    rng = np.random.default_rng(20261)
+    ln2 = float(np.log(2.0))
+    sign = lambda m: np.where(rng.integers(0, 2, m) == 1, 1.0, -1.0)      # noqa: E731
+    a = {}
+    # the set of the host test below, scaled to 2¹⁸: uniform in ±700 and ±100, and the reduction boundaries (k + ½)·ln2 from a few ulp to 10⁻³·ln2 away
+    k1, k2 = rng.integers(-1009, 1010, 57344), rng.integers(-1009, 1010, 57344)
+    a["exp_b"] = np.concatenate([rng.uniform(-700, 700, 98304), rng.uniform(-100, 100, 49152), (k1 + 0.5) * ln2 + rng.uniform(-1e-3, 1e-3, 57344) * ln2,
+                                 (k2 + 0.5) * ln2 * (1 + rng.integers(-4, 5, 57344) * 2.2e-16)])
+    a["rcp_b"] = np.concatenate([sign(2 ** 17) * 10.0 ** rng.uniform(-12, 12, 2 ** 17), rng.uniform(1, 2, 2 ** 17 - 4), [1.0, np.nextafter(1.0, 2.0), np.nextafter(2.0, 1.0), 2.0]])
+    a["rsqrt_b"] = np.concatenate([rng.uniform(1, 4, 2 ** 17), 10.0 ** rng.uniform(-6, 6, 2 ** 17)])
+    cuts = HALF_SQRT2 * 2.0 ** rng.integers(-22, 11, 2 ** 15)                        # √½·2ᵉ inside 10⁻⁷ … 10³: where frexp's mantissa crosses the cut
+    a["log_b"] = np.concatenate([10.0 ** rng.uniform(-7, 3, 2 ** 17), rng.uniform(0.7, 1.3, 2 ** 16 + 2 ** 15), _spread_ulps(rng, cuts, 2 ** 15, 64)])
+    edge = np.concatenate([_spread_ulps(rng, s * np.full(32, 0.3), 32, 8) for s in (1.0, -1.0)])      # both sides of the switch between series and exp_b − 1
+    a["expm1_b"] = np.concatenate([rng.uniform(-0.3, 0.3, 2 ** 16), sign(2 ** 16) * 10.0 ** rng.uniform(-12, -3, 2 ** 16),
+                                   sign(2 ** 17 - 64) * rng.uniform(0.3, 50.0, 2 ** 17 - 64), edge])
+    for name, x in a.items():
+        assert len(x) == NARG and np.isfinite(x).all(), name
+        a[name] = np.ascontiguousarray(x, dtype=np.float64)
+    assert np.abs(a["exp_b"]).max() <= 700.0
+    assert 1e-12 <= np.abs(a["rcp_b"]).min() and np.abs(a["rcp_b"]).max() <= 1e12
+    assert 1e-6 <= a["rsqrt_b"].min() and a["rsqrt_b"].max() <= 1e6
+    assert 1e-7 <= a["log_b"].min() and a["log_b"].max() <= 1e3 and (a["log_b"] < HALF_SQRT2).any()
+    assert np.abs(a["expm1_b"]).max() <= 50.0 and (np.abs(edge) < 0.3).any() and (np.abs(edge) >= 0.3).any()
+    return a
+
+
+@pytest.fixture(scope="module")
+def math_truth(math_args):
+    """the exact values to 2⁻¹¹ of a double's last place: numpy.longdouble where it has a 64-bit significand (x87), skipped elsewhere"""
+    if np.finfo(LD).nmant < 63:
+        pytest.skip("numpy.longdouble has no 64-bit significand here")
+    x = {k: v.astype(LD) for k, v in math_args.items()}
+    return {"exp_b": np.exp(x["exp_b"]), "rcp_b": LD(1) / x["rcp_b"], "rsqrt_b": LD(1) / np.sqrt(x["rsqrt_b"]), "log_b": np.log(x["log_b"]),
+            "expm1_b": np.expm1(x["expm1_b"])}
+
+
+def max_ulps(got, truth):
+    """largest |got − truth| in units of the last place of a double at the truth's magnitude (2^(ilogb(truth) − 52), as tests/tb_math_host.cpp counts)"""
+    _, e = np.frexp(truth)                                         # |truth| = m·2ᵉ, m in [½, 1): ilogb = e − 1
+    err = np.abs(got.astype(LD) - truth) / np.ldexp(LD(1), e - 53)
+    return float(err.max()) if np.isfinite(got).all() else float("nan")
+
+
+@pytest.fixture(scope="module")
+def host_math(tmp_path_factory, math_args):
+    """the five functions of the host build of tb_math.hpp (tests/tb_math_host.cpp) on math_args"""
+    rocm = os.environ.get("ROCM", os.environ.get("ROCM_PATH", "/opt/rocm"))
+    so = str(tmp_path_factory.mktemp("tbmathhost") / "libtbmathhost.so")
+    subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__",
+                           "-I" + os.path.join(rocm, "include"), "-I" + os.path.join(ROOT, "thunderbolt.jl_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "tb_math_host.cpp"), "-o", so])
+    L = C.CDLL(so)
+    out = {}
+    for name in FUNCTIONS:
+        fn = getattr(L, "eval_" + name)
+        fn.restype, fn.argtypes = None, [C.c_void_p, C.c_long, C.c_void_p]
+        y = np.full(NARG, np.nan)
+        fn(math_args[name].ctypes.data, NARG, y.ctypes.data)
+        out[name] = y
+    return out
+
+
+def test_log_b_and_expm1_b_of_the_host_build_against_long_double(math_args, math_truth, host_math):
+    """The two functions tb_math.hpp gave no figure for.  Measured on 3·10⁶ arguments each of the same ranges: log_b 2.38 ulp on 10⁻⁷ … 10³ and 2.42 ulp on
+    [0.7, 1.3], expm1_b 1.48 ulp for |z| < 0.3 and 3.31 ulp for 0.3 ≤ |z| ≤ 50 (libm: log 0.52 ulp, exp(z) − 1 2.01 ulp).  The bounds are those figures
+    rounded up to the next integer: a later change of coefficients cannot slide past them."""
+    e_log, e_expm1 = max_ulps(host_math["log_b"], math_truth["log_b"]), max_ulps(host_math["expm1_b"], math_truth["expm1_b"])
+    z = math_args["expm1_b"]
+    small = np.abs(z) < 0.3
+    e_small = max_ulps(host_math["expm1_b"][small], math_truth["expm1_b"][small])
+    print("host build: log_b %.4f ulp; expm1_b %.4f ulp (|z| < 0.3: %.4f ulp); %d arguments each" % (e_log, e_expm1, e_small, NARG))
+    assert e_log <= 3.0
+    assert e_expm1 <= 4.0
+
+
+@pytest.mark.gpu
+def test_math_functions_on_the_device(tmp_path, math_args, math_truth, host_math):
+    """exp_b, rcp_b, rsqrt_b, log_b and expm1_b as the kernels get them: tests/tb_math_device.hip built with the library's flags (-O3 -ffp-contract=fast for
+    gfx950), one kernel per function, on math_args.
+      exp_b, expm1_b  no hardware seed and every fused multiply-add written out: bit for bit the host build's values, which pins the device to the host
+                      measurement against long double (0.862 ulp for exp_b);
+      rcp_b           ≤ 2 ulp (the header's claim for v_rcp_f64 and two Newton steps);
+      rsqrt_b         ≤ 2 ulp, and no more than 1.0 / sqrt(y) evaluated in the same kernel (the host assertion above, on the device);
+      log_b           ≤ the host build's error on the same arguments + 3 ulp: the one seed dependence is rcp_b(m + 1), allowed 2 ulp on the device against
+                      the stand-in's 0.5; log m = 2f(1 + …) carries f's relative error one to one, and a relative error is worth up to twice as many units in
+                      the last place on the far side of a binade.
+    Every figure is printed before it is asserted."""
+    import shutil
+    hipcc = shutil.which("hipcc") or os.path.join(os.environ.get("ROCM", os.environ.get("ROCM_PATH", "/opt/rocm")), "bin", "hipcc")
+    so = str(tmp_path / "libtbmathdevice.so")
+    b = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast", "-shared", "-fPIC",
+                        "-I" + os.path.join(ROOT, "thunderbolt.jl_amd", "csrc"), os.path.join(ROOT, "tests", "tb_math_device.hip"), "-o", so],
+                       capture_output=True, text=True, timeout=600)
+    assert b.returncode == 0, b.stderr[-2000:]
+    fn = C.CDLL(so).tb_math_device_eval
+    fn.restype, fn.argtypes = C.c_int, [C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p]
+    dev, plain_rsqrt = {}, np.full(NARG, np.nan)
+    for which, name in enumerate(FUNCTIONS):
+        y = np.full(NARG, np.nan)
+        rc = fn(which, math_args[name].ctypes.data, NARG, y.ctypes.data, plain_rsqrt.ctypes.data if name == "rsqrt_b" else None)
+        assert rc == 0, "%s: HIP status %d" % (name, rc)
+        dev[name] = y
+    e_dev = {name: max_ulps(dev[name], math_truth[name]) for name in FUNCTIONS}
+    e_host = {name: max_ulps(host_math[name], math_truth[name]) for name in FUNCTIONS}
+    e_plain = max_ulps(plain_rsqrt, math_truth["rsqrt_b"])
+    for name in FUNCTIONS:
+        differ = np.flatnonzero(dev[name].view(np.uint64) != host_math[name].view(np.uint64))
+        print("%-8s device %.4f ulp, host build %.4f ulp, %d of %d values differ from the host build%s" % (
+            name, e_dev[name], e_host[name], len(differ), NARG, "".join(" [x = %r: device %r, host %r]" % (
+                float(math_args[name][i]), float(dev[name][i]), float(host_math[name][i])) for i in differ[:3]) if name in ("exp_b", "expm1_b") else ""))
+    print("1.0 / sqrt(y) in the rsqrt_b kernel: %.4f ulp" % e_plain)
+    np.testing.assert_array_equal(dev["exp_b"].view(np.uint64), host_math["exp_b"].view(np.uint64))
+    np.testing.assert_array_equal(dev["expm1_b"].view(np.uint64), host_math["expm1_b"].view(np.uint64))
+    assert e_dev["rcp_b"] <= 2.0
+    assert e_dev["rsqrt_b"] <= 2.0 and e_dev["rsqrt_b"] <= e_plain
+    assert e_dev["log_b"] <= e_host["log_b"] + 3.0

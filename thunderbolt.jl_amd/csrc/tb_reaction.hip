@@ -321,6 +321,7 @@ template <> struct CellModel<TB_CELL_ORD11> {
         const double EKs = RTF * (log(ko + 0.01833 * nao) - log(ki + 0.01833 * nai));
         const double vg = fabs(v) < 1e-7 ? 1e-7 : v; // the constant-field fluxes divide by e^{zVF/RT} − 1: V = 0 exactly is moved by 10⁻⁷ mV (as in the oracle)
         const double vfrt = vg * FRT, vffrt = vfrt * F;
+        const double vfrt0 = v * FRT; // V itself for the exchanger and the pump, which have no singularity at V = 0: the moved voltage is for the constant-field fluxes alone (as in the oracle)
         // INa
         constexpr double Ahf = 0.99, Ahs = 1.0 - Ahf;
         const double h = Ahf * hf + Ahs * hs;
@@ -368,7 +369,7 @@ template <> struct CellModel<TB_CELL_ORD11> {
         // INaCa: the same six-state cycle in the myoplasm (80 %) and in the subspace (20 %)
         constexpr double kna1 = 15.0, kna2 = 5.0, kna3 = 88.12, kasymm = 12.5, wna = 6.0e4, wca = 6.0e4, wnaca = 5.0e3, kcaon = 1.5e6, kcaoff = 5.0e3,
                          qna = 0.5224, qca = 0.1670, KmCaAct = 150.0e-6;
-        const double hca = exp_b(qca * vfrt), hna = exp_b(qna * vfrt), ihna = rcp_b(hna);
+        const double hca = exp_b(qca * vfrt0), hna = exp_b(qna * vfrt0), ihna = rcp_b(hna);
         const double Gncx = 0.0008 * p[7] * (celltype == 1 ? 1.1 : celltype == 2 ? 1.4 : 1.0);
         const double h7 = 1.0 + nao * (1.0 / kna3) * (1.0 + ihna), h8 = nao * ihna * rcp_b(kna3 * h7), h9 = rcp_b(h7);
         const double h10 = kasymm + 1.0 + nao * (1.0 / kna1) * (1.0 + nao * (1.0 / kna2)), h11 = nao * nao / (h10 * kna1 * kna2), h12 = 1.0 / h10;
@@ -392,7 +393,7 @@ template <> struct CellModel<TB_CELL_ORD11> {
         constexpr double k1p = 949.5, k1m = 182.4, k2p = 687.2, k2m = 39.4, k3p_ = 1899.0, k3m = 79300.0, k4p_ = 639.0, k4m = 40.0, Knai0 = 9.073,
                          Knao0 = 27.78, delta = -0.1550, Kki = 0.5, Kko = 0.3582, MgADP = 0.05, MgATP = 9.8, Kmgatp = 1.698e-7, H = 1.0e-7, eP = 4.2,
                          Khp = 1.698e-7, Knap = 224.0, Kxkur = 292.0;
-        const double Knai = Knai0 * exp_b(delta * vfrt * (1.0 / 3.0)), Knao = Knao0 * exp_b((1.0 - delta) * vfrt * (1.0 / 3.0));
+        const double Knai = Knai0 * exp_b(delta * vfrt0 * (1.0 / 3.0)), Knao = Knao0 * exp_b((1.0 - delta) * vfrt0 * (1.0 / 3.0));
         const double Pp = eP * rcp_b(1.0 + H / Khp + nai * (1.0 / Knap) + ki * (1.0 / Kxkur));
         const double rni = nai * rcp_b(Knai), rno = nao * rcp_b(Knao), rki = ki * (1.0 / Kki), rko = ko * (1.0 / Kko);
         const double c3 = [](double x) { return x * x * x; }(1.0 + rni), c3o = [](double x) { return x * x * x; }(1.0 + rno);
@@ -571,21 +572,6 @@ k_reaction(CellParams P, CellDerived<MODEL> D, TS *__restrict__ u, TS *__restric
             atomicMax(rmax_key, (b >> 63) ? ~b : (b | 0x8000000000000000ull)); // order-preserving key, see tb_algebra.hip
         }
     }
-}
-
-// expm1 for the Rush–Larsen factor: series for small arguments (no cancellation), exp − 1 otherwise
-__device__ __forceinline__ double expm1_b(double z)
-{
-    if (fabs(z) < 0.3) {
-        double q = 1.6059043836821613e-10;
-        const double c[11] = {2.08767569878681e-09, 2.505210838544172e-08, 2.755731922398589e-07, 2.7557319223985893e-06, 2.48015873015873e-05,
-                              0.0001984126984126984, 0.001388888888888889, 0.008333333333333333, 0.041666666666666664, 0.16666666666666666, 0.5};
-#pragma unroll
-        for (int i = 0; i < 11; ++i) q = fma(q, z, c[i]);
-        q = fma(q, z, 1.0);
-        return q * z;
-    }
-    return exp_b(z) - 1.0;
 }
 
 // Rush–Larsen step (the splitting SURVEY §8 f4 names; the reference only carries the reaction_rhs!/state_rhs! hooks for it,
