@@ -47,7 +47,7 @@ static int sarcomere_and_materials()
     for (int i = 0; i < 9; ++i) e.G[i] = G[i];
     const double F[9] = {1.05, 0.02, -0.01, 0.03, 0.97, 0.04, -0.02, 0.01, 1.02}, f0[3] = {1, 0, 0}, s0[3] = {0, 1, 0}, n0[3] = {0, 0, 1};
     double acc = 0.0;
-    for (int pr = 0; pr < 45; ++pr) { int mm, nn; tbk::pair_components(pr, mm, nn); acc += tbk::energy_pair(e, F, mm, nn, f0, s0, n0).ab; }
+    for (int pr = 0; pr < 45; ++pr) { int mm, nn; tbk::pair_components(pr, mm, nn); acc += tbk::energy_pair(e, F, mm, nn, f0, s0, n0, e.Ta).ab; }
     if (!(acc == acc)) return 23;
     // oracle: condensed assembly (rate-coupled) on a tiny mesh, Hill framework, prestress
     return 0;

@@ -3550,6 +3550,27 @@ def test_sums_through_reduction_slots_accumulate_into_the_callers_scalar(tb, dev
         device.set_stream(None)
 
 
+def test_refused_vector_plan_inside_a_capture_takes_the_general_kernel(tb, oracle, device):
+    """A field whose dofs and vertices are not one-to-one (vertex 6 of cell 0 carries the dof of a far vertex) is refused by the vector patch planner,
+    every call anew, and the atomic strategy then runs the general kernel.  The planner touches no device, so the same happens while a graph capture is
+    open: the refusal stays TB_ERR_UNSUPPORTED (not "cannot run while a capture is open"), the general kernel is captured and the replay gives the
+    oracle's vector."""
+    g = tb.generate_mesh(tb.Hexahedron, (6, 5, 4), (0, 0, 0), (1.0, 0.9, 0.8), perturb=0.2)
+    cd, nd = oracle.close_dofs(oracle.HEX8, 1, g.conn, g.n_nodes)
+    cd[0, 6] = cd[-1, 6]
+    dh = tb.DofHandler(g, cell_dofs=cd, ndofs=nd)
+    om = oracle.Mesh(oracle.HEX8, 2, g.xyz, g.conn, dh.cell_dofs)
+    src = tb.setup_operator(tb.AtomicAssemblyStrategy(device), tb.LinearIntegrator(tb.AnalyticalCoefficient("cos_exp")), dh)
+    ref = oracle.assemble_source(om, oracle.SRC_COS_EXP, t=0.3)
+    assert rel_err(tb.update_operator(src, 0.3).b.to_host(), ref) < TOL       # outside a capture: the general kernel
+    gr = device.capture(lambda: tb.update_operator(src, 123.0))
+    src.b.copy_from_host(np.full(dh.ndofs, np.nan))
+    gr.launch(0.3)
+    device.poll_status()
+    assert rel_err(src.b.to_host(), ref) < TOL
+    gr.close()
+
+
 def test_bisection_patcher_on_a_curved_thin_wall(tb, oracle, device):
     """The tile plan of per-axis buckets fills the 256-lane sweeps of the idealised ventricle to about a half; ensure_patch_fused then bisects the cells into
     equal leaves (round 5) if that needs clearly fewer patches.  The matrices of the new plan are the oracle's, the plan has fewer instances per patch

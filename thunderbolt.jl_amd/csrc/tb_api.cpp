@@ -70,6 +70,18 @@ static int read_status(tb_device *dev)
 
 int read_status_public(tb_device *dev) { return read_status(dev); }
 
+// second queue and two events of the chunked element assemblies, created on first use (released by tb_device_destroy)
+int ensure_aux_stream(tb_device *dev)
+{
+    if (dev->aux_stream) return TB_OK;
+    static const bool hi = [] { const char *e = tune_env("TB_MECH_CHUNK_PRIO"); return e && atoi(e); }();
+    int lo_p = 0, hi_p = 0;
+    TB_HIP(hipDeviceGetStreamPriorityRange(&lo_p, &hi_p));
+    TB_HIP(hipStreamCreateWithPriority(&dev->aux_stream, hipStreamNonBlocking, hi ? hi_p : lo_p));
+    for (hipEvent_t &e : dev->aux_ev) TB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return TB_OK;
+}
+
 template <class T>
 static void copy_rebased(std::vector<T> &dst, const T *src, size_t n, int base)
 {

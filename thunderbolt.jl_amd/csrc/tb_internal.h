@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "tbhip.h"
+#include "tb_planners.hpp"
 
 namespace tb {
 
@@ -70,17 +71,10 @@ const char *last_kernel();
         if (rc__) return rc__;            \
     } while (0)
 
-// TB_PLAN_VERBOSE=1: wall time of the host-side plan builders, stage by stage, on stderr (what `setup_s.first_step_incl_plan_build` of bench.py is made of)
-struct PlanTimer {
-    const char *name;
-    double t0;
-    bool on;
-    static double now() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
-    explicit PlanTimer(const char *n) : name(n), t0(0.0), on(getenv("TB_PLAN_VERBOSE") != nullptr) { if (on) t0 = now(); }
-    void lap(const char *what) { if (on) { const double t = now(); fprintf(stderr, "[tbhip] plan time: %-28s %-34s %8.3f s\n", name, what, t - t0); t0 = t; } }
-    ~PlanTimer() { lap("(rest)"); }
+// TB_PLAN_VERBOSE=1: wall time of the host-side plan builders, stage by stage, on stderr (StageTimer, tb_planners.hpp)
+struct PlanTimer : StageTimer {
+    explicit PlanTimer(const char *n) : StageTimer(n, getenv("TB_PLAN_VERBOSE") != nullptr) {}
 };
-
 
 // status word written by kernels (device) and read back after each launch group
 struct Status {
@@ -111,15 +105,9 @@ struct EAPlan {                // dof → contributing (cell, local) slots, cell
                                  // value reaches c are complete once cells [0, c) are integrated (chunked element assembly: gather behind the integration front)
 };
 
-// Patch plan: cells in Morton order are cut into patches; every dof (row) is owned by exactly one
-// patch, which (re)computes all cells touching its rows, accumulates in LDS and stores once.
-struct PatchPlan {
-    int cells_per_patch = 0;
-    int version = 0;   // bumped when the plan is rebuilt (LDS-fit retry); matrix extensions remember theirs
-    int shrink = 0;    // tile reductions applied so far
-    int64_t n_patches = 0;
-    int max_elems = 0, max_rows = 0, threads = 256; // threads: workgroup size used by the patch kernels
-    int64_t total_elems = 0, total_rows = 0;
+// Patch plan (plan::PatchHost, whose host arrays the matrix extensions read) with its device copies
+struct PatchPlan : plan::PatchHost {
+    int version = 0;   // moves on when the plan is replaced (LDS-fit retry); an extension is valid only for the version it was built for
     // per patch
     int64_t *d_elem_ptr = nullptr; // n_patches+1 → element instances
     int64_t *d_row_ptr = nullptr;  // n_patches+1 → owned rows
@@ -128,16 +116,6 @@ struct PatchPlan {
     uint16_t *d_elem_lrow = nullptr; // ndpc local-row slots per instance (0xFFFF = row not owned here)
     // per owned row
     int32_t *d_row_dof = nullptr;   // global dof id
-    // matrix extension (needs a pattern)
-    std::vector<int64_t> h_elem_ptr, h_row_ptr;
-    std::vector<int32_t> h_elem_cell, h_row_dof;
-    std::vector<uint16_t> h_elem_lrow;
-};
-
-struct RowDesc {      // one owned row of a patch
-    int64_t nz0;      // first nz of the row in the global CSR arrays
-    uint32_t off;     // offset of its accumulators in the patch's LDS block (in entries)
-    uint32_t len;     // row length
 };
 
 struct PatchMatPlan {
@@ -236,9 +214,7 @@ struct tb_mesh {
     std::unique_ptr<tb::ColorPlan> colors;
     std::unique_ptr<tb::EAPlan> ea;
     std::unique_ptr<tb::PatchPlan> patches;
-    int patch_rcb = 0;            // > 0: the matrix patch plan bisects the cells into leaves of this many cells instead of tiling per-axis buckets (tb_plans.cpp)
-    bool patch_rcb_tried = false; // the bisection was compared with the tiles once
-    int patch_tile_shrink = 0;    // tile reductions the LDS-fit loop applied to the tile plan (restored when the bisection loses)
+    tb::plan::FitState fit;       // what the fits of the patch plan remember (bisection instead of tiles, tile reductions)
     std::unique_ptr<tb::VecPatchPlan> vpatches[2]; // [halo]
 };
 
@@ -347,15 +323,12 @@ struct tb_form {
 
 namespace tb {
 
-// ---- plan builders (tb_plans.cpp) ----
-void dof_slots(const tb_mesh *m, std::vector<int64_t> &ptr, std::vector<int32_t> &src); // dof → (cell·ndpc + local) slots, cell-ordered
+// ---- plan caches and uploads (tb_plans.cpp; the planners themselves are in tb_planners.hpp) ----
 int build_color_plan(tb_mesh *m);
 int build_color_plan_subset(tb_mesh *m, const std::vector<int32_t> &cells, std::unique_ptr<ColorPlan> &out);
 int build_ea_plan(tb_mesh *m);
 int ensure_ea_ell(tb_mesh *m);
 int ensure_ea_ell_q2t(tb_mesh *m);
-int build_patch_plan(tb_mesh *m, int cells_per_patch);
-int build_patch_mat_plan(tb_pattern *p);
 int ensure_patch_records(tb_pattern *p); // one-trip records of the fused plan (after ensure_patch_fused); TB_ERR_UNSUPPORTED when the patches do not fit the form
 int ensure_patch_plans(tb_mesh *m, tb_pattern *p); // builds / refits both so the LDS block allows two workgroups per CU
 void free_patch_plan(tb_mesh *m);
@@ -368,7 +341,7 @@ int launch_assemble_hex8_patch(tb_form *fK, tb_form *fM, tb_pattern *p, double t
 bool hex8_patch_applicable(const tb_form *f, const tb_pattern *p);
 int launch_assemble_tet4_patch(tb_form *fK, tb_form *fM, tb_pattern *p, double t, double *d_nzK, double *d_nzM); // linear tetrahedra; either form may be NULL
 bool tet4_patch_applicable(const tb_form *f, const tb_pattern *p);
-int ensure_aux_stream(tb_device *dev); // second queue + two events of the chunked element assemblies (tb_mechanics.hip, scalar Q2 forms)
+int ensure_aux_stream(tb_device *dev); // tb_api.cpp: second queue + two events of the chunked element assemblies (tb_mechanics.hip, scalar Q2 forms)
 
 // ---- kernel launchers, by the file that defines them ----
 // tb_assembly.hip
@@ -489,6 +462,15 @@ int upload(tb_device *dev, const std::vector<T> &h, T **d)
     TB_HIP(hipMemcpyAsync(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, dev->stream));
     TB_SYNC_STREAM(dev);
     return TB_OK;
+}
+
+// several host vectors in a row; the first failure ends it (what was uploaded before stays with the caller, who frees the plan)
+inline int upload_all(tb_device *) { return TB_OK; }
+template <class T, class... Rest>
+int upload_all(tb_device *dev, const std::vector<T> &h, T **d, Rest &&...rest)
+{
+    TB_TRY(upload(dev, h, d));
+    return upload_all(dev, rest...);
 }
 
 } // namespace tb
