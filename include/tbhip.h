@@ -513,7 +513,8 @@ int tb_host_sarcomere_local_solve(int model, const double *params, int n_params,
  * ext/CuThunderboltExt.jl:103-124).  substeps <= 1: ForwardEulerCellSolver (:80-99); substeps > 1:
  * AdaptiveForwardEulerSubstepper with reaction_threshold (:196-234).  d_du (dumat) may be NULL when the
  * caller does not need the rates (the RTC controller does: src/solver/time/rtc.jl:64-73).
- * Returns TB_OK (the reference kernels always return true; NaNs are the host's business). */
+ * Returns TB_OK (the reference kernels always return true; NaNs are the host's business: a non-finite state of one point stays in that point, in
+ * `d_u` and `d_du`, and reaches the host through tb_max / tb_absmax or the `rmax` of tb_reaction_step_rtc, all of which keep a NaN). */
 int tb_reaction_step(tb_device *dev, int model, const double *params, int n_params, double *d_u, double *d_du,
                      int64_t n_points, int n_states, int layout, double t, double dt, int substeps,
                      double threshold);
@@ -526,7 +527,8 @@ int tb_reaction_step_x(tb_device *dev, int model, const double *params, int n_pa
                        double threshold);
 /* Same step with the reaction tangent fused in: *rmax receives max over points of the φₘ component of the last right-hand
  * side evaluated at each point — what ReactionTangentController reads from `dumat` after the step (src/solver/time/rtc.jl:55-73)
- * — without `du` having to be written (d_du may be NULL): 16 instead of 24 bytes per DoF-update. */
+ * — without `du` having to be written (d_du may be NULL): 16 instead of 24 bytes per DoF-update.  Like Julia's `maximum`, and like tb_max on the
+ * same slice, *rmax is NaN as soon as the φₘ rate of one point is NaN (of any sign or payload); n_points == 0 yields −∞. */
 int tb_reaction_step_rtc(tb_device *dev, int model, const double *params, int n_params, double *d_u, double *d_du,
                          int64_t n_points, int n_states, int layout, double t, double dt, int substeps, double threshold,
                          double *rmax);
@@ -554,7 +556,9 @@ int tb_spmv_csr(tb_pattern *pat, const double *d_nzval, const double *d_x, doubl
 enum { TB_JACOBI_REUSE = 2 };
 /* the stopping threshold atol + rtol·‖r₀‖₂ of the latest tb_cg_solve / tb_cg_solve_from_residual / tb_pcg_solve / tb_gmres_solve on this pattern:
  * a solve has converged iff its reported resnorm ≤ this value (the reference fails a step whose linear solve ran into MaxIters,
- * src/solver/nonlinear/newton_raphson.jl: `solve_succeeded || return false`) */
+ * src/solver/nonlinear/newton_raphson.jl: `solve_succeeded || return false`).  Non-finite data never converges: when ‖r₀‖ is NaN or ∞ (a NaN or
+ * ±∞ in A, b or x₀) the threshold is NaN and the solve returns at once with that ‖r₀‖ as resnorm; a NaN met later ends the solve with a NaN
+ * resnorm or with TB_ERR_BAD_ARG (pᵀAp not positive, non-finite Arnoldi vector).  Nothing of it outlives the call. */
 int tb_solver_last_tolerance(const tb_pattern *pat, double *tol);
 int tb_cg_solve(tb_pattern *pat, const double *d_Anz, const double *d_b, double *d_x, double rtol, double atol, int maxiter,
                 int jacobi, int *iters, double *resnorm);
@@ -581,7 +585,8 @@ int tb_l1gs_apply(tb_pattern *pat, const double *d_Anz, int partsize, int sweep,
 int tb_gmres_solve(tb_pattern *pattern, const double *d_Anz, const double *d_b, double *d_x, double rtol, double atol, int maxiter, int restart,
                    int jacobi, int *iters, double *resnorm);
 /* y += x (add!(b, source), src/solver/time/euler.jl:90) and max |x[i]| over a strided slice
- * (RTC reads max(dumat[:,φₘidx]), src/solver/time/rtc.jl:64-73) */
+ * (RTC reads max(dumat[:,φₘidx]), src/solver/time/rtc.jl:64-73).  tb_absmax follows `maximum(abs, …)`: any NaN among the n addressed elements
+ * makes the result NaN, ±∞ without a NaN gives +∞, n == 0 gives 0; elements between the strides are not read. */
 int tb_axpy(tb_device *dev, int64_t n, double a, const double *d_x, double *d_y);
 int tb_absmax(tb_device *dev, int64_t n, const double *d_x, int64_t stride, double *result);
 /* x·y (norms of residuals / increments in the Newton loop, src/solver/nonlinear/newton_raphson.jl:246-290) */
@@ -729,7 +734,8 @@ int tb_apply_zero_csr(tb_pattern *pat, double *d_nzval, double *d_f, const uint8
 /* mean |diagonal| (Ferrite.meandiag) */
 int tb_meandiag(tb_pattern *pat, const double *d_nzval, double *result);
 /* signed maximum of a strided slice: exactly `maximum(@view dumat[:, φₘidx])` of get_reaction_tangent
- * (src/solver/time/rtc.jl:64-73 — no absolute value there).  n == 0 yields −∞. */
+ * (src/solver/time/rtc.jl:64-73 — no absolute value there), NaN included: any NaN among the n addressed elements, of either sign and any payload,
+ * makes the result NaN; +∞ without a NaN gives +∞; a slice of −∞ gives −∞.  n == 0 yields −∞. */
 int tb_max(tb_device *dev, int64_t n, const double *d_x, int64_t stride, double *result);
 
 /* ------------------------------------------------------------------ Newmark-β elastodynamics, M ü + f_int(u) = f_ext (src/solver/time/newmark.jl)

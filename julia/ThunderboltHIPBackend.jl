@@ -351,7 +351,8 @@ function _pointwise_step_outer_kernel!(f::AbstractPointwiseFunction, t::Real, Δ
     return rc == 0
 end
 
-# reaction tangent of the RTC controller: `maximum(@view cache.dumat[:, φₘidx])` (src/solver/time/rtc.jl:64-73) on the device
+# reaction tangent of the RTC controller: `maximum(@view cache.dumat[:, φₘidx])` (src/solver/time/rtc.jl:64-73) on the device, NaN included:
+# any NaN in the slice makes the result NaN, as `maximum` does
 function reaction_tangent(dev::MI355XDevice, dumat_phi::Ptr{Float64}, npoints::Integer, stride::Integer = 1)
     R = Ref{Float64}()
     check(ccall((:tb_max, libtbhip), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ref{Float64}), dev.handle, npoints, dumat_phi, stride, R))

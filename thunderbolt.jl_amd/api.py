@@ -1213,11 +1213,24 @@ class ReactionTangentController:
         return ok, self.stepsize(self.R)
 
     def solve(self, t0, t1, dt):
-        """Advance from t0 to t1 (the last step is clipped to land on t1); returns the list of accepted (t, dt)."""
+        """Advance from t0 to t1 (the last step is clipped to land on t1); returns the list of accepted (t, dt).
+
+        Stated deviation from the reference: a step whose reaction tangent R is not finite (a point of the pointwise problem has blown up — the fused
+        reduction keeps its NaN) raises RuntimeError naming the time and R.  The reference accepts the step and goes on with Δt = σ(NaN) = NaN
+        (rtc.jl:104-120); this loop would leave silently instead, `min(nan, …)` and `t < t1` being what they are in Python.  A heat step that fails
+        because φₘ itself is not finite (max |φₘ| read with tb_absmax, nothing is written) is reported the same way, with R = NaN: no reaction step
+        of that call ran to form a tangent, and the tangent of such a state is NaN."""
         t, hist = float(t0), []
         while t < t1 - 1e-14 * max(1.0, abs(t1)):
             h = min(dt, t1 - t)
             ok, dt_next = self.step(t, h)
+            if not ok and self.ltg.f.npoints > 0:
+                top = C.c_double()
+                check(lib().tb_absmax(self.ltg.phi.dev.h, self.ltg.phi.n, self.ltg.phi.ptr, 1, C.byref(top)))
+                if not np.isfinite(top.value):
+                    self.R = float("nan")
+            if not np.isfinite(self.R) and self.ltg.f.npoints > 0:                  # (no points: R = −∞, the empty maximum)
+                raise RuntimeError("RTC: non-finite reaction tangent R = %r in the step at t = %g (Δt = %g): the pointwise problem has blown up" % (self.R, t, h))
             if not ok:
                 raise RuntimeError("RTC: inner step failed at t = %g" % t)
             hist.append((t, h))

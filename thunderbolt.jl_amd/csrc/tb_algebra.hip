@@ -37,29 +37,24 @@ __global__ void __launch_bounds__(256) k_axpy(int64_t n, double a, const double 
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) y[i] += a * x[i];
 }
 
+// Both maxima keep a NaN (max_nan, tb_reduce.hpp): any NaN in the addressed slice makes the result NaN, as Julia's `maximum` does.
 __global__ void __launch_bounds__(256)
 k_absmax(int64_t n, const double *__restrict__ x, int64_t stride_x, unsigned long long *__restrict__ out)
 {
     double m = 0.0;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) m = fmax(m, fabs(x[i * stride_x]));
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) m = max_nan(m, fabs(x[i * stride_x]));
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+    for (int o = 32; o > 0; o >>= 1) m = max_nan(m, __shfl_xor(m, o, 64));
     __shared__ double sm[4];
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) {
-        m = fmax(fmax(sm[0], sm[1]), fmax(sm[2], sm[3]));
-        // non-negative doubles order like their bit patterns
+        m = max_nan(max_nan(sm[0], sm[1]), max_nan(sm[2], sm[3]));
+        // non-negative doubles order like their bit patterns, and a NaN of positive sign lies above +∞ in that order: it wins the atomicMax
+        // (m is +0 or an operand that went through fabs above, so its sign bit is clear)
         atomicMax(out, (unsigned long long)__double_as_longlong(m));
     }
-}
-
-// order-preserving map double → uint64 (total order of finite values and ±∞), so atomicMax works on signed values
-__device__ __forceinline__ unsigned long long ordered_key(double v)
-{
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 
 __global__ void __launch_bounds__(256)
@@ -67,10 +62,10 @@ k_max(int64_t n, const double *__restrict__ x, int64_t stride_x, unsigned long l
 {
     double m = -__builtin_huge_val();
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) m = fmax(m, x[i * stride_x]);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) m = max_nan(m, x[i * stride_x]);
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
-    if ((threadIdx.x & 63) == 0) atomicMax(out, ordered_key(m));
+    for (int o = 32; o > 0; o >>= 1) m = max_nan(m, __shfl_xor(m, o, 64));
+    if ((threadIdx.x & 63) == 0) atomicMax(out, ordered_key(m)); // (NaN: the largest key)
 }
 
 int launch_heat_matrix(tb_device *dev, int64_t nnz, const double *M, const double *K, double dt, double *A)
@@ -99,6 +94,7 @@ int launch_absmax(tb_device *dev, int64_t n, const double *x, int64_t stride, do
 
 double decode_ordered_key(unsigned long long k)
 {
+    if (k == ~0ull) return __builtin_nan(""); // the key of every NaN (ordered_key, tb_reduce.hpp)
     const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
     double v;
     memcpy(&v, &b, sizeof v);

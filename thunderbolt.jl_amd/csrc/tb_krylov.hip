@@ -30,6 +30,14 @@ double *krylov_ws(tb_pattern *pat, size_t doubles)
     return pat->d_krylov_ws;
 }
 
+// Stopping tolerance atol + rtol·‖r₀‖ of every solver here (tb_solver_last_tolerance).  A non-finite ‖r₀‖ — a NaN or ±∞ in A, b or x₀ — gives NaN, which
+// no residual compares ≤ to: with atol + rtol·∞ = ∞ a solve on such data would return ‖r‖ = ∞ ≤ ∞ at once, "converged".  The loops below are
+// `while (rnorm > tol …)`, so they are not entered either: the call returns TB_OK with zero iterations and the residual norm it found.
+static inline double stopping_tolerance(double atol, double rtol, double rnorm0)
+{
+    return std::isfinite(rnorm0) ? atol + rtol * rnorm0 : __builtin_nan("");
+}
+
 } // namespace tb
 
 // ------------------------------------------------------------------------------------------------
@@ -157,7 +165,7 @@ int launch_cg(tb_pattern *pat, const double *A, const double *b, double *x, doub
     TB_HIP(hipMemsetAsync(g_pap, 0, 5 * RED_GROUP * sizeof(double), dev->stream));
     TB_HIP(hipMemcpyAsync(g_rz(0), scal, sizeof(double), hipMemcpyDeviceToDevice, dev->stream)); // r·z of the start: slot 0 of the current group
     double rnorm = std::sqrt(h[1]);
-    const double tol = atol + rtol * rnorm;
+    const double tol = stopping_tolerance(atol, rtol, rnorm);
     pat->last_tol = tol;
     // The host looks at (‖r‖², flag) once per `check` iterations: small systems are bound by the host round trip, not by the kernels, so they
     // run a few iterations between looks (at most check − 1 iterations past the tolerance); large ones look every iteration.
@@ -272,7 +280,7 @@ int launch_gmres(tb_pattern *pat, const double *A, const double *b, double *x, d
         hipLaunchKernelGGL(k_residual, dim3(g), dim3(256), 0, dev->stream, n, b, z, w, h1);
         TB_TRY(read_back(dev, hh.data(), h1, 1));
         rnorm = std::sqrt(hh[0]);
-        if (first) { tol = atol + rtol * rnorm; pat->last_tol = tol; first = false; }
+        if (first) { tol = stopping_tolerance(atol, rtol, rnorm); pat->last_tol = tol; first = false; }
         if (!(rnorm > tol) || it >= maxiter) break;
         hipLaunchKernelGGL(k_scale_diag, dim3(g), dim3(256), 0, dev->stream, n, 1.0 / rnorm, (const double *)nullptr, w, V);
         std::fill(gvec.begin(), gvec.end(), 0.0);
@@ -429,7 +437,7 @@ int launch_pcg_l1gs(tb_pattern *pat, const double *A, const double *b, double *x
     hipLaunchKernelGGL(k_residual, dim3(g), dim3(256), 0, dev->stream, n, b, Ap, r, scal);
     TB_TRY(read_back(dev, h, scal, 1));
     double rnorm = std::sqrt(h[0]);
-    const double tol = atol + rtol * rnorm;
+    const double tol = stopping_tolerance(atol, rtol, rnorm);
     pat->last_tol = tol;
     int it = 0;
     double rz = 0.0;
@@ -662,7 +670,7 @@ int launch_pcg_chebyshev(tb_pattern *pat, const double *A, const double *b, doub
     hipLaunchKernelGGL(k_residual, dim3(g), dim3(256), 0, dev->stream, n, b, Ap, r, S + 3);
     TB_TRY(read_back(dev, h, S + 3, 1));
     double rnorm = std::sqrt(h[0]);
-    const double tol = atol + rtol * rnorm;
+    const double tol = stopping_tolerance(atol, rtol, rnorm);
     pat->last_tol = tol;
     int it = 0;
     while (rnorm > tol && it < maxiter) {

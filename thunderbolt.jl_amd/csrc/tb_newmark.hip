@@ -155,7 +155,8 @@ k_vector_mass(VMassArgs a, const MapT *__restrict__ emap, const int32_t *__restr
         }
         // the sign of detJ·w is the sign of detJ except at the centroid of the degree-4 rule (negative weight)
         const bool neg_w = !hex && a.ng == 4 && q == 0;
-        if (neg_w ? dOmega >= 0.0 : dOmega <= 0.0) { st->neg_detj = 1; st->cell = cell; }
+        // (negated comparisons: a NaN or ±∞ coordinate gives a NaN detJ, which flags the cell like every other assembly kernel's !(det > 0))
+        if (neg_w ? !(dOmega < 0.0) : !(dOmega > 0.0)) { st->neg_detj = 1; st->cell = cell; }
         sW[q] = rho * dOmega;
     }
     __syncthreads();

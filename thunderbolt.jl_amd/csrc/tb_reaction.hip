@@ -15,6 +15,7 @@
 
 #include "tb_internal.h"
 #include "tb_math.hpp"
+#include "tb_reduce.hpp"
 
 namespace tb {
 
@@ -562,15 +563,12 @@ k_reaction(CellParams P, CellDerived<MODEL> D, TS *__restrict__ u, TS *__restric
             u[k] = (TS)ul[j];
             if (WRITE_DU) du_out[k] = (TS)dul[j];
         }
-        rm = fmax(rm, dul[M::PHI]);
+        rm = max_nan(rm, dul[M::PHI]); // a NaN rate stays (tb_reduce.hpp): R is all the controller reads of a step
     }
     if (rmax_key) {
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) rm = fmax(rm, __shfl_xor(rm, o, 64));
-        if ((threadIdx.x & 63) == 0) {
-            const unsigned long long b = (unsigned long long)__double_as_longlong(rm);
-            atomicMax(rmax_key, (b >> 63) ? ~b : (b | 0x8000000000000000ull)); // order-preserving key, see tb_algebra.hip
-        }
+        for (int o = 32; o > 0; o >>= 1) rm = max_nan(rm, __shfl_xor(rm, o, 64));
+        if ((threadIdx.x & 63) == 0) atomicMax(rmax_key, ordered_key(rm)); // order-preserving key, NaN on top (tb_reduce.hpp)
     }
 }
 

@@ -1,5 +1,6 @@
-// tb_reduce.hpp — sums over the workgroups of a launch, shared by the units that end a kernel in one (tb_spmv.hip, tb_krylov.hip, tb_algebra.hip):
-// the workgroup sums (device, inline), the slot groups they leave through, and the grids of the kernels that use them (host, inline).
+// tb_reduce.hpp — sums and maxima over the workgroups of a launch, shared by the units that end a kernel in one (tb_spmv.hip, tb_krylov.hip, tb_algebra.hip,
+// tb_reaction.hip): the workgroup sums (device, inline), the slot groups they leave through, the NaN-keeping maximum and its atomicMax key, and the grids
+// of the kernels that use them (host, inline).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,6 +21,19 @@ static inline unsigned grid_for(tb_device *dev, int64_t n, int bs)
     int64_t nb = (n + bs - 1) / bs;
     const int64_t cap = (int64_t)dev->n_cu * 8;
     return (unsigned)(nb > cap ? cap : nb);
+}
+
+// ---- one maximum ----
+// max(a, b) that keeps a NaN of either operand (fmax returns the other one): the `max` of Julia's `maximum`, which the reaction-tangent controller
+// reads (src/solver/time/rtc.jl:57-73) — a point that has blown up has to reach the host.  One compare more than fmax.
+__device__ __forceinline__ double max_nan(double a, double b) { return (b > a || b != b) ? b : a; }
+// Order-preserving map double → uint64, so atomicMax works on signed values: a total order of the finite values and ±∞ with key(−∞) > 0 (0 = "no
+// element yet").  EVERY NaN, whatever its sign or payload, maps to the largest key, above key(+∞): by its bits alone a negative-sign NaN (0xfff8…, what
+// x86 produces for 0/0) would sort below −∞ and lose.  decode_ordered_key (tb_algebra.hip) turns that key back into a quiet NaN.
+__device__ __forceinline__ unsigned long long ordered_key(double v)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return v != v ? ~0ull : (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 
 // ---- one scalar ----
