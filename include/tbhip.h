@@ -25,6 +25,8 @@
  *                                                 field coefficients and oversize patches run — the switch lets a test put them on any mesh)
  *   TB_PATCH_CUT = full, TB_PATCH_TILE = "x,y,z"  tile cut / tile shape of the patch plan
  *   TB_PATCH_ISO = 0                              constant positive definite tensors through the DIAG / general instances instead of the ISO one
+ *   TB_PATCH_CANON = 0 | 1                        record kernel: 0 = canonical patches (lexicographic lattice rows) through the general instance too, 1 = through
+ *                                                 the CANON instance at any size (default: from 64 canonical patches per CU on)
  *   TB_SPMV_KERNEL = rows                         CSR rows kernel also where the pattern compresses (what patterns without shared signatures run)
  *   TB_MECH_CHUNKS = n                            launches of the chunked Q2 linearisation (0 / 1: one)
  *   TB_NEWMARK_STAGE = rows                       tb_newmark_stage runs its fused general CSR kernel on every pattern (read at a pattern's first stage call)

@@ -149,6 +149,9 @@ struct PatchFusedPlan {
     //   rec_rm × 16 B row descriptors · rec_nm × 24 B vertex coordinates; zero padding behind the patch's own counts.  Built on first use.
     uint8_t *d_rec = nullptr;
     int rec_stride = 0, rec_rm = 0, rec_nm = 0, rec_ne = 0; // rec_ne: instance slots per record (≥ 256, multiple of 64); rec_stride = −1: the patches do not fit the record form (a patch with more than 256 instances)
+    // the records stand in two classes (plan::classify_records): rec_general general patches first, rec_canonical canonical ones behind them — the CANON
+    // instances of the record kernel take the second class with compile-time scatter offsets
+    int64_t rec_general = 0, rec_canonical = 0;
 };
 
 // Patch plan of the linear-form (vector) kernels on trilinear hexahedra (tb_assembly.hip: k_vector_hex8_patch).  Row accumulators of a vector

@@ -47,7 +47,22 @@ struct FusedView {
 // in the accumulator block or 0xFFFFFFFF when the patch does not own it.
 // meta(cp, ro) delivers the scatter metadata when the scatter starts (the streaming kernel reads them from LDS only then: held from the start, they
 // cost 24 registers through the contraction).
-template <bool WK, bool WM, bool FK, bool FM, bool DIAG = false, bool ISO = false, class Meta>
+//
+// CANON (canonical patches, plan::classify_records): every owned row has 27 entries with column dof(j) at 13 + Δx + 3Δy + 9Δz, a constant of the pair
+// (i, j).  ro[i] is then the BYTE address of row i's stiffness accumulators in LDS (0xFFFFFFFF: not owned) and every add is
+// `ds_add_f64 v_row_i, value offset:8·pos(i, j)` — the mass block MOFF entries further on in the same immediate.  No signature words, no address
+// arithmetic between an entry's last FP64 instruction and its add; masks, values and target addresses are those of the general path.
+using lds_f64 = __attribute__((address_space(3))) double;
+__device__ constexpr int canon_pos(int i, int j)
+{
+    return 13 + (SF::bit(j, 0) - SF::bit(i, 0)) + 3 * (SF::bit(j, 1) - SF::bit(i, 1)) + 9 * (SF::bit(j, 2) - SF::bit(i, 2));
+}
+__device__ __forceinline__ void lds_add(uint32_t row, int entry, double v)
+{
+    (void)__hip_atomic_fetch_add((lds_f64 *)(uintptr_t)row + entry, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+template <bool WK, bool WM, bool FK, bool FM, bool DIAG = false, bool ISO = false, bool CANON = false, int MOFF = 0, class Meta>
 __device__ __forceinline__ void hex8_instance(const double (&x)[8][3], Meta &&meta, int64_t cell, const FormArgs &faK,
                                               const FormArgs &faM, double *accK, double *accM, Status *st, const int32_t *elem_cell, int64_t e)
 {
@@ -99,8 +114,13 @@ __device__ __forceinline__ void hex8_instance(const double (&x)[8][3], Meta &&me
 #pragma unroll
             for (int j = i; j < 8; ++j) {
                 const double v = hex8_sf_entry(c, i, j);
-                if (own[i]) unsafeAtomicAdd(accK + (ro[i] + pos(i, j)), v);
-                if (j > i && own[j]) unsafeAtomicAdd(accK + (ro[j] + pos(j, i)), v);
+                if constexpr (CANON) {
+                    if (own[i]) lds_add(ro[i], canon_pos(i, j), v);
+                    if (j > i && own[j]) lds_add(ro[j], canon_pos(j, i), v);
+                } else {
+                    if (own[i]) unsafeAtomicAdd(accK + (ro[i] + pos(i, j)), v);
+                    if (j > i && own[j]) unsafeAtomicAdd(accK + (ro[j] + pos(j, i)), v);
+                }
             }
     }
     if constexpr (WM) {
@@ -125,7 +145,11 @@ __device__ __forceinline__ void hex8_instance(const double (&x)[8][3], Meta &&me
         for (int i = 0; i < 8; ++i)
             if (own[i]) {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) unsafeAtomicAdd(accM + (ro[i] + pos(i, j)), Z[SF::ty(i, j, 0)][SF::ty(i, j, 1)][SF::ty(i, j, 2)]);
+                for (int j = 0; j < 8; ++j) {
+                    const double v = Z[SF::ty(i, j, 0)][SF::ty(i, j, 1)][SF::ty(i, j, 2)];
+                    if constexpr (CANON) lds_add(ro[i], MOFF + canon_pos(i, j), v);
+                    else unsafeAtomicAdd(accM + (ro[i] + pos(i, j)), v);
+                }
             }
     }
 }
@@ -365,7 +389,9 @@ k_patch_hex8_staged(FormArgs faK, FormArgs faM, FusedView pv, const uint4 *__res
 // Write-out: a half-wave reads ALL its row descriptors, then ALL its accumulators, then stores (one dependent LDS round instead of five).
 // KOFF > 0: the mass block sits KOFF entries behind the stiffness block (compile-time: the second add of a pair reuses the first one's address register with
 // an immediate offset); KOFF = 0: `kcap` entries behind it (patches with more than KOFF accumulator entries)
-template <bool WK, bool WM, bool DIAG, bool ISO, int RPH, int KOFF = 0, bool WQ = true>
+// CANON: the instance of the canonical patches (see hex8_instance) — no signature ids, no signature words, row addresses in bytes; single-matrix instances and
+// the fixed-KOFF pair only (a pair with KOFF = 0 keeps its mass block at a run-time distance, which an immediate cannot carry)
+template <bool WK, bool WM, bool DIAG, bool ISO, int RPH, int KOFF = 0, bool WQ = true, bool CANON = false>
 __global__ void __launch_bounds__(256, 2)
 k_patch_hex8_record(FormArgs faK, FormArgs faM, const uint8_t *__restrict__ rec, int stride, int nem, int rm, int nm, int kcap, const uint8_t *__restrict__ sigtab, const int32_t *__restrict__ elem_cell, int pf, int prio, int stagger,
                     double *__restrict__ nzK, double *__restrict__ nzM, Status *st
@@ -402,7 +428,9 @@ k_patch_hex8_record(FormArgs faK, FormArgs faM, const uint8_t *__restrict__ rec,
     const uint32_t hw = h4.x;
     (void)pf; // (look-ahead touch of the record pf patches ahead: measured slower, its keep-alive cost the kernel two registers — removed)
     uint4 lnv = ((const uint4 *)(r + 16))[tid];
-    const uint32_t sig = ((const uint32_t *)(r + 16 + (size_t)nem * 16))[tid];
+    static_assert(!CANON || !(WK && WM) || KOFF > 0, "the canonical pair needs the mass block at a compile-time distance");
+    uint32_t sig = 0;
+    if constexpr (!CANON) sig = ((const uint32_t *)(r + 16 + (size_t)nem * 16))[tid];
     const uint8_t *rdp = r + 16 + (size_t)nem * 20;
     const double *pc = (const double *)(rdp + (size_t)rm * 16);
     constexpr int NX = ISO ? 6 : 5;
@@ -443,7 +471,7 @@ k_patch_hex8_record(FormArgs faK, FormArgs faM, const uint8_t *__restrict__ rec,
         for (int k = tid + NX * T; k < 3 * nm; k += T) xs[k] = pc[k]; // more than 426 nodes per patch
     }
     uint4 cp[4];
-    {
+    if constexpr (!CANON) {
         const uint4 *cpp = (const uint4 *)(sigtab + (size_t)sig * 64); // padding lanes carry signature 0: a valid read
 #pragma unroll
         for (int k = 0; k < 4; ++k) cp[k] = cpp[k];
@@ -457,9 +485,11 @@ k_patch_hex8_record(FormArgs faK, FormArgs faM, const uint8_t *__restrict__ rec,
     for (int ei = tid; ei < ne; ei += T) { // one pass for all but the domain-boundary patches (they own the extra boundary layers: up to ≈ 280 instances)
         if (ei >= T) {
             lnv = ((const uint4 *)(r + 16))[ei];
-            const uint4 *cpp = (const uint4 *)(sigtab + (size_t)((const uint32_t *)(r + 16 + (size_t)nem * 16))[ei] * 64);
+            if constexpr (!CANON) {
+                const uint4 *cpp = (const uint4 *)(sigtab + (size_t)((const uint32_t *)(r + 16 + (size_t)nem * 16))[ei] * 64);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) cp[k] = cpp[k];
+                for (int k = 0; k < 4; ++k) cp[k] = cpp[k];
+            }
         }
         const uint32_t ln[8] = {lnv.x & 0xffffu, lnv.x >> 16, lnv.y & 0xffffu, lnv.y >> 16, lnv.z & 0xffffu, lnv.z >> 16, lnv.w & 0xffffu, lnv.w >> 16};
         double x[8][3];
@@ -471,8 +501,16 @@ k_patch_hex8_record(FormArgs faK, FormArgs faM, const uint8_t *__restrict__ rec,
         uint32_t ro[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) ro[i] = ln[i] < (uint32_t)nrows ? desc[ln[i]].off : 0xFFFFFFFFu;
-        hex8_instance<WK, WM, false, false, DIAG, ISO>(x, [&](uint4(&c4)[4], uint32_t(&r8)[8]) { for (int k = 0; k < 4; ++k) c4[k] = cp[k]; for (int k = 0; k < 8; ++k) r8[k] = ro[k]; }, 0, faK, faM, accK, accM, st,
-                                                  elem_cell, (int64_t)h4.y + ei);
+        if constexpr (CANON) {
+            const uint32_t base = (uint32_t)(uintptr_t)(lds_f64 *)lds; // byte address of the stiffness block (of the only block for a single matrix)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) if (ro[i] != 0xFFFFFFFFu) ro[i] = base + 8u * ro[i];
+            hex8_instance<WK, WM, false, false, DIAG, ISO, true, (WK && WM) ? KOFF : 0>(x, [&](uint4(&)[4], uint32_t(&r8)[8]) { for (int k = 0; k < 8; ++k) r8[k] = ro[k]; }, 0, faK, faM, accK, accM, st,
+                                                                                       elem_cell, (int64_t)h4.y + ei);
+        } else {
+            hex8_instance<WK, WM, false, false, DIAG, ISO>(x, [&](uint4(&c4)[4], uint32_t(&r8)[8]) { for (int k = 0; k < 4; ++k) c4[k] = cp[k]; for (int k = 0; k < 8; ++k) r8[k] = ro[k]; }, 0, faK, faM, accK, accM, st,
+                                                           elem_cell, (int64_t)h4.y + ei);
+        }
     }
     TB_ST(3);
     __syncthreads();
@@ -691,25 +729,46 @@ int launch_assemble_hex8_patch(tb_form *fK, tb_form *fM, tb_pattern *p, double t
             }
             static const size_t lds_pad = tune_env("TB_PATCH_LDS_PAD") ? (size_t)atol(tune_env("TB_PATCH_LDS_PAD")) : 0; // profiling build: > 80 KB leaves one workgroup per CU
             const size_t ldsr_ = ldsr;
-            auto launch_rec = [&](auto k) -> int {
+            // two launches of the same grid family: the general instance over the first class of records, the CANON instance over the second (a class
+            // without patches is not launched).  The second launch starts when the first has drained, and that boundary has a price: measured on the
+            // 27-layer slab (9 680 patches, 5 292 of them canonical) 0.006 ms — more than the canonical scatter gains there (≈ 0.9 ns per canonical patch:
+            // 0.050 ms on the 61 740 of 216³).  So the classes are split where the gain is clearly the larger: from 32 generations of canonical workgroups
+            // on (two residents per CU; 16 384 patches on 256 CUs, ≈ 0.015 ms of gain).  A mixed kernel — one launch, a branch on blockIdx between the two
+            // scatter forms — has no boundary but spills (156 B of scratch: the general path alone fills the 256 registers), so it was not kept.
+            // TB_PATCH_CANON=0 sends both classes through the general instance (A/B runs), TB_PATCH_CANON=1 splits at any size (the parity test's boxes).
+            static const int canon_mode = getenv("TB_PATCH_CANON") ? atoi(getenv("TB_PATCH_CANON")) : -1;
+            const bool canon = canon_mode != 0 && pr->rec_canonical > 0 && !(fK && fM && !fixm) && (canon_mode > 0 || pr->rec_canonical >= (int64_t)64 * dev->n_cu);
+            const int64_t n_gen = canon ? pr->rec_general : pp->n_patches, n_can = pp->n_patches - n_gen;
+            auto launch_one = [&](auto k, int64_t first, int64_t count) -> int {
                 const size_t ldsr = std::max(ldsr_, lds_pad);
+                const uint8_t *rec0 = (const uint8_t *)pr->d_rec + (size_t)first * (size_t)pr->rec_stride;
                 TB_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsr));
 #ifdef TB_ABLATION
-                hipLaunchKernelGGL(k, dim3((unsigned)pp->n_patches), dim3(256), ldsr, dev->stream, aK, aMi, (const uint8_t *)pr->d_rec, pr->rec_stride, pr->rec_ne, pr->rec_rm, pr->rec_nm, pv.kcap,
+                hipLaunchKernelGGL(k, dim3((unsigned)count), dim3(256), ldsr, dev->stream, aK, aMi, rec0, pr->rec_stride, pr->rec_ne, pr->rec_rm, pr->rec_nm, pv.kcap,
                                    (const uint8_t *)pf->d_sigtab, pp->d_elem_cell, pf_ahead, wave_prio, stagger, d_nzK, d_nzM, dev->d_status, d_prof);
 #else
-                hipLaunchKernelGGL(k, dim3((unsigned)pp->n_patches), dim3(256), ldsr, dev->stream, aK, aMi, (const uint8_t *)pr->d_rec, pr->rec_stride, pr->rec_ne, pr->rec_rm, pr->rec_nm, pv.kcap,
+                hipLaunchKernelGGL(k, dim3((unsigned)count), dim3(256), ldsr, dev->stream, aK, aMi, rec0, pr->rec_stride, pr->rec_ne, pr->rec_rm, pr->rec_nm, pv.kcap,
                                    (const uint8_t *)pf->d_sigtab, pp->d_elem_cell, pf_ahead, wave_prio, stagger, d_nzK, d_nzM, dev->d_status);
 #endif
                 return TB_OK;
             };
-            set_last_kernel("k_patch_hex8_record<%s,%s,RPH%d%s>", fK && fM ? "K+M" : fK ? "K" : "M", !fK ? "-" : iso ? "ISO" : diag ? "DIAG" : "GEN", RPH, fK && fM && fixm ? ",KOFF4096" : "");
+            auto launch_rec = [&](auto kg, auto kc) -> int {
+                if (n_gen > 0) TB_TRY(launch_one(kg, 0, n_gen));
+                if (n_can > 0) TB_TRY(launch_one(kc, n_gen, n_can));
+                return TB_OK;
+            };
+            set_last_kernel("k_patch_hex8_record<%s,%s,RPH%d%s%s>", fK && fM ? "K+M" : fK ? "K" : "M", !fK ? "-" : iso ? "ISO" : diag ? "DIAG" : "GEN", RPH, fK && fM && fixm ? ",KOFF4096" : "",
+                            n_can > 0 ? ",CANON" : "");
             static const bool wq_off = tune_env("TB_PATCH_WQ") && atoi(tune_env("TB_PATCH_WQ")) == 0; // profiling build: the half-wave write-out of rounds 2-5 (bench instance only)
-            if (fK && fM && fixm && iso && wq_off) rc = launch_rec(k_patch_hex8_record<true, true, false, true, RPH, KOFF, false>);
-            else if (fK && fM && fixm) rc = iso ? launch_rec(k_patch_hex8_record<true, true, false, true, RPH, KOFF>) : diag ? launch_rec(k_patch_hex8_record<true, true, true, false, RPH, KOFF>) : launch_rec(k_patch_hex8_record<true, true, false, false, RPH, KOFF>);
-            else if (fK && fM) rc = iso ? launch_rec(k_patch_hex8_record<true, true, false, true, RPH>) : diag ? launch_rec(k_patch_hex8_record<true, true, true, false, RPH>) : launch_rec(k_patch_hex8_record<true, true, false, false, RPH>);
-            else if (fK) rc = iso ? launch_rec(k_patch_hex8_record<true, false, false, true, RPH>) : diag ? launch_rec(k_patch_hex8_record<true, false, true, false, RPH>) : launch_rec(k_patch_hex8_record<true, false, false, false, RPH>);
-            else rc = launch_rec(k_patch_hex8_record<false, true, false, false, RPH>);
+#define TB_REC(wk, wm, dg, is, koff) launch_rec(k_patch_hex8_record<wk, wm, dg, is, RPH, koff>, k_patch_hex8_record<wk, wm, dg, is, RPH, koff, true, true>)
+#define TB_REC0(wk, wm, dg, is) launch_rec(k_patch_hex8_record<wk, wm, dg, is, RPH>, k_patch_hex8_record<wk, wm, dg, is, RPH>) /* pair with a run-time block distance: no CANON instance */
+            if (fK && fM && fixm && iso && wq_off) rc = launch_rec(k_patch_hex8_record<true, true, false, true, RPH, KOFF, false>, k_patch_hex8_record<true, true, false, true, RPH, KOFF, false, true>);
+            else if (fK && fM && fixm) rc = iso ? TB_REC(true, true, false, true, KOFF) : diag ? TB_REC(true, true, true, false, KOFF) : TB_REC(true, true, false, false, KOFF);
+            else if (fK && fM) rc = iso ? TB_REC0(true, true, false, true) : diag ? TB_REC0(true, true, true, false) : TB_REC0(true, true, false, false);
+            else if (fK) rc = iso ? TB_REC(true, false, false, true, 0) : diag ? TB_REC(true, false, true, false, 0) : TB_REC(true, false, false, false, 0);
+            else rc = TB_REC(false, true, false, false, 0);
+#undef TB_REC
+#undef TB_REC0
             if (rc) return rc;
             TB_HIP(hipGetLastError());
             goto done;

@@ -601,13 +601,50 @@ Records record_layout(const PatchHost &pp, int max_nodes)
     return rec;
 }
 
-void pack_records(Records &rec, int64_t np, const uint32_t *hdr, const uint16_t *ln, const uint32_t *sig, const RowDesc *desc, const double *xyz)
+// Position of column dof(j) in row dof(i) on a lattice whose rows hold their 27 columns in ascending lexicographic order: 13 + Δx + 3Δy + 9Δz, with the
+// vertex bits of Ferrite's hexahedron (-,-,-),(+,-,-),(+,+,-),(-,+,-),(-,-,+),… — the table tb_patch_fused.hip compiles into its CANON instances
+static inline int canonical_pos(int i, int j)
+{
+    static const int bit[3][8] = {{0, 1, 1, 0, 0, 1, 1, 0}, {0, 0, 1, 1, 0, 0, 1, 1}, {0, 0, 0, 0, 1, 1, 1, 1}};
+    return 13 + (bit[0][j] - bit[0][i]) + 3 * (bit[1][j] - bit[1][i]) + 9 * (bit[2][j] - bit[2][i]);
+}
+
+// Reads the plan's own arrays only (headers, local node indices, signature ids and table, row descriptors): nothing about how the mesh was generated.
+RecordClasses classify_records(int64_t np, const uint32_t *hdr, const uint16_t *ln, const uint32_t *sig, const RowDesc *desc, const uint8_t *sigtab)
+{
+    std::vector<uint8_t> canon((size_t)np, 0);
+#pragma omp parallel for schedule(static)
+    for (int64_t q = 0; q < np; ++q) {
+        const uint32_t e0 = hdr[4 * q], r0 = hdr[4 * q + 1], w = hdr[4 * q + 3];
+        const uint32_t nr = w & 0x3ff, ne = w >> 21;
+        bool ok = ne <= 256;
+        for (uint32_t k = 0; k < nr && ok; ++k) ok = desc[(size_t)r0 + k].len == 27;
+        for (uint32_t e = 0; e < ne && ok; ++e) {
+            const uint8_t *sg = sigtab + (size_t)sig[(size_t)e0 + e] * 64;
+            for (int i = 0; i < 8 && ok; ++i) {
+                if (ln[((size_t)e0 + e) * 8 + i] >= nr) continue; // a row of another patch: this instance adds nothing to it
+                for (int j = 0; j < 8; ++j) ok = ok && sg[i * 8 + j] == canonical_pos(i, j);
+            }
+        }
+        canon[q] = ok;
+    }
+    RecordClasses rc;
+    rc.order.reserve((size_t)np);
+    for (int64_t q = 0; q < np; ++q) if (!canon[q]) rc.order.push_back(q);
+    rc.n_general = (int64_t)rc.order.size();
+    for (int64_t q = 0; q < np; ++q) if (canon[q]) rc.order.push_back(q);
+    rc.n_canonical = np - rc.n_general;
+    return rc;
+}
+
+void pack_records(Records &rec, int64_t np, const uint32_t *hdr, const uint16_t *ln, const uint32_t *sig, const RowDesc *desc, const double *xyz, const int64_t *order)
 {
     const size_t stride = (size_t)rec.stride, o_ln = 16, o_sig = o_ln + (size_t)rec.ne * 16, o_desc = o_sig + (size_t)rec.ne * 4, o_xyz = o_desc + (size_t)rec.rm * 16;
     rec.bytes.assign(stride * (size_t)np, 0);
 #pragma omp parallel for schedule(static)
-    for (int64_t q = 0; q < np; ++q) {
-        uint8_t *r = &rec.bytes[stride * (size_t)q];
+    for (int64_t s = 0; s < np; ++s) {
+        const int64_t q = order ? order[s] : s;
+        uint8_t *r = &rec.bytes[stride * (size_t)s];
         const uint32_t e0 = hdr[4 * q], r0 = hdr[4 * q + 1], n0 = hdr[4 * q + 2], w = hdr[4 * q + 3];
         const uint32_t nr = w & 0x3ff, nn = (w >> 10) & 0x7ff, ne = w >> 21;
         const uint32_t h4[4] = {w, e0, 0, 0}; // e0: first instance of the patch in the plan's instance arrays (the kernel names the offending cell through it)

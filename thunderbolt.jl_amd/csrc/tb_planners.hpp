@@ -90,6 +90,11 @@ struct FusedHost {
     std::vector<double> pcoord;
 };
 struct Records { int stride = -1, rm = 0, nm = 0, ne = 0; std::vector<uint8_t> bytes; }; // stride −1: the patches do not take the record form
+// The two classes of hexahedron patches (classify_records).  A patch is CANONICAL when it has at most 256 instances and, for every instance and every local
+// node i the patch owns, the row has exactly 27 entries and the signature places column dof(j) at 13 + Δx + 3Δy + 9Δz of the row (Δ: vertex bits of j
+// minus those of i in Ferrite's vertex order) — the interior rows of a lattice whose columns ascend lexicographically, under whatever numbering gives that
+// order.  order[s] is the patch whose record sits in slot s: general patches first, canonical ones behind them, plan order within each class.
+struct RecordClasses { int64_t n_general = 0, n_canonical = 0; std::vector<int64_t> order; };
 struct VecHost {
     bool halo = false;
     int64_t n_patches = 0, total_elems = 0, total_nodes = 0;
@@ -111,7 +116,9 @@ std::vector<RowDesc> row_descs(const PatchHost &pp, const PatternView &p, int64_
 Outcome mat_extension(const MeshView &m, const PatternView &p, const PatchHost &pp, const Options &o, MatHost &out);
 Outcome fused_extension(const MeshView &m, const PatternView &p, const PatchHost &pp, const Options &o, int nregions, FusedHost &out);
 Records record_layout(const PatchHost &pp, int max_nodes);
-void pack_records(Records &rec, int64_t np, const uint32_t *hdr, const uint16_t *ln, const uint32_t *sig, const RowDesc *desc, const double *xyz);
+RecordClasses classify_records(int64_t np, const uint32_t *hdr, const uint16_t *ln, const uint32_t *sig, const RowDesc *desc, const uint8_t *sigtab);
+// order (np entries, a permutation) puts patch order[s] into record slot s; nullptr keeps the plan's order
+void pack_records(Records &rec, int64_t np, const uint32_t *hdr, const uint16_t *ln, const uint32_t *sig, const RowDesc *desc, const double *xyz, const int64_t *order = nullptr);
 int vec_patch_plan(const MeshView &m, const Options &o, bool halo, VecHost &out);
 // The fit policies.  `cur` is the mesh's patch plan, or empty where it has none yet; a fit that has to change the patch shape builds the new plan in place and sets
 // `replaced` — the caller then owes the device a new copy.  After a failed patch planner `cur` is empty.

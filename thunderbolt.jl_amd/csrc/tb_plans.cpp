@@ -231,12 +231,17 @@ static int ensure_patch_records_impl(tb_pattern *p)
     for (int64_t q = 0; q < np; ++q) total_nodes = std::max<int64_t>(total_nodes, (int64_t)hdr[4 * q + 2] + ((hdr[4 * q + 3] >> 10) & 0x7ff));
     std::vector<double> xyz((size_t)total_nodes * 3);
     TB_HIP(hipMemcpy(xyz.data(), f->d_pcoord, xyz.size() * 8, hipMemcpyDeviceToHost));
-    pack_records(rec, np, hdr.data(), ln.data(), sig.data(), desc.data(), xyz.data());
+    std::vector<uint8_t> sigtab((size_t)f->nsig * 64);
+    TB_HIP(hipMemcpy(sigtab.data(), f->d_sigtab, sigtab.size(), hipMemcpyDeviceToHost));
+    const RecordClasses cls = classify_records(np, hdr.data(), ln.data(), sig.data(), desc.data(), sigtab.data());
+    pack_records(rec, np, hdr.data(), ln.data(), sig.data(), desc.data(), xyz.data(), cls.order.data());
     TB_HIP(hipMalloc((void **)&f->d_rec, rec.bytes.size()));
     TB_HIP(hipMemcpy(f->d_rec, rec.bytes.data(), rec.bytes.size(), hipMemcpyHostToDevice));
     f->rec_stride = rec.stride; f->rec_rm = rec.rm; f->rec_nm = rec.nm; f->rec_ne = rec.ne;
+    f->rec_general = cls.n_general; f->rec_canonical = cls.n_canonical;
     if (getenv("TB_PLAN_VERBOSE"))
-        fprintf(stderr, "[tbhip] one-trip patch records: %lld patches x %zu B (rows <= %d, nodes <= %d), %.2f GB\n", (long long)np, (size_t)rec.stride, rec.rm, rec.nm, (double)rec.bytes.size() / 1e9);
+        fprintf(stderr, "[tbhip] one-trip patch records: %lld patches x %zu B (rows <= %d, nodes <= %d), %.2f GB; %lld general, %lld canonical\n", (long long)np, (size_t)rec.stride, rec.rm, rec.nm,
+                (double)rec.bytes.size() / 1e9, (long long)cls.n_general, (long long)cls.n_canonical);
     return TB_OK;
 }
 
