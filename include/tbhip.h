@@ -790,6 +790,48 @@ int tb_heat_matrix_f32(tb_device *dev, int64_t nnz, const float *d_Mnz, const fl
 int tb_axpy_f32(tb_device *dev, int64_t n, double a, const float *d_x, float *d_y);
 int tb_cg_solve_f32(tb_pattern *pat, const float *d_Anz, const float *d_b, float *d_x, double rtol, double atol, int maxiter, int jacobi, int *iters, double *resnorm);
 
+/* ------------------------------------------------------------------ geometric multigrid preconditioner (h-levels, first-order hexahedra)
+ * GMGPrecon of the reference (src/solver/linear/multigrid.jl, ext/ThunderboltFerriteMultigridExt.jl, docs/src/literate-howto/multigrid.jl) on the
+ * nested grids of uniform refinement: Galerkin coarse operators A_c = PᵀA_fP rebuilt from every new matrix, one V(degree, degree) cycle with the
+ * Chebyshev–Jacobi smoother of multigrid.jl:28-33 on [λmax/interval_ratio, λmax] of D⁻¹A, an explicit inverse on the coarsest level.  A symmetric
+ * positive-definite operator, so plain PCG applies.  Out of scope and refused: p-levels (PMGPrecon / ChainedMGPrecon), second-order fields,
+ * tetrahedra, W- and F-cycles, other smoothers, GMRES, several ranks.
+ *   tb_mg_create        an empty hierarchy of n_levels ≥ 2 levels; level 0 is the coarsest, level n_levels − 1 the one the solve runs on
+ *   tb_mg_set_level     the pattern of a level: the allocate_matrix pattern of a first-order field (1 or 3 components) on that level's grid; the
+ *                       pattern (and its mesh) must outlive the hierarchy
+ *   tb_mg_set_transfer  the parent nodes of every node of level fine_level in level fine_level − 1 (host arrays, 0-based, parent_ptr of n_fine_nodes + 1
+ *                       entries): 1 parent for a kept node — itself: the coarse nodes are a prefix of the fine ones —, 2 for an edge centre, 4 for
+ *                       a face centre, 8 for a cell centre.  A fine dof interpolates the same component of its parents with weight 1/#parents.  Both
+ *                       levels must be set; a parent list that does not fit them is TB_ERR_BAD_ARG.
+ *   tb_mg_set_prescribed  flags of the Dirichlet dofs of the finest level (device, one byte per dof, as tb_apply_zero_csr takes them; NULL: none).  A
+ *                       coarse dof is prescribed iff the fine dof it coincides with is; rows of P at prescribed fine dofs and columns at prescribed
+ *                       coarse dofs are dropped — elimination on the free dofs, for matrices as tb_apply_zero_csr leaves them.  Copies the flags.
+ *   tb_mg_setup         the numeric phase a Newton iteration repeats (multigrid.jl: the coarse operators follow every new Jacobian): plans on first
+ *                       use (P row-wise, Pᵀ row-wise and the gather plan of the product, so no kernel needs an atomic and every sum has one recorded
+ *                       order: two setups give the same bits), then the Galerkin chain from fine to coarse, D⁻¹, λmax(D⁻¹A) per level (the estimate
+ *                       of TB_PRECOND_CHEBYSHEV) and the inverse of the coarsest operator (n ≤ 1024 dofs, else TB_ERR_UNSUPPORTED: add a level).
+ *                       Prescribed coarse rows and columns are empty, their diagonal the mean |diagonal| of the level's free dofs.  d_Anz_fine is
+ *                       read by tb_mg_apply as well: it must stay as it is until the next setup.  Reads scalars back: not inside a graph capture.
+ *   tb_mg_apply         z = M⁻¹ r, one V cycle from z = 0; enqueues only (fits inside tb_graph_begin / tb_graph_end); z = 0 at prescribed dofs
+ *   tb_mg_level_matrix / tb_mg_level_lambda_max / tb_mg_prolong (x_f = P x_c) / tb_mg_restrict (r_c = Pᵀ r_f): what the cycle is made of, for tests
+ *                       and callers that inspect levels; prolong and restrict need the plans, i.e. one tb_mg_setup
+ *   tb_pcg_solve_mg     tb_pcg_solve with z = M⁻¹ r by tb_mg_apply (KrylovMGSolver with CG): same stopping rule, tb_solver_last_tolerance and
+ *                       non-finite behaviour; pat and d_Anz are the finest level's and the array of the latest tb_mg_setup */
+typedef struct tb_mg tb_mg;
+int tb_mg_create(tb_device *dev, int n_levels, tb_mg **out);
+int tb_mg_set_level(tb_mg *mg, int level, tb_pattern *pat);
+int tb_mg_set_transfer(tb_mg *mg, int fine_level, int64_t n_fine_nodes, const int64_t *parent_ptr, const int32_t *parent_idx);
+int tb_mg_set_prescribed(tb_mg *mg, const uint8_t *d_prescribed_fine);
+int tb_mg_setup(tb_mg *mg, const double *d_Anz_fine, int degree, double interval_ratio);
+int tb_mg_apply(tb_mg *mg, const double *d_r, double *d_z);
+int tb_mg_level_matrix(tb_mg *mg, int level, const double **d_nzval);
+int tb_mg_level_lambda_max(tb_mg *mg, int level, double *lmax);
+int tb_mg_prolong(tb_mg *mg, int fine_level, const double *d_xc, double *d_xf);
+int tb_mg_restrict(tb_mg *mg, int fine_level, const double *d_rf, double *d_rc);
+int tb_mg_destroy(tb_mg *mg);
+int tb_pcg_solve_mg(tb_pattern *pat, const double *d_Anz, const double *d_b, double *d_x, double rtol, double atol, int maxiter, tb_mg *mg, int *iters,
+                    double *resnorm);
+
 /* ------------------------------------------------------------------ host-side generators (no GPU needed)
  * Ferrite-convention synthetic inputs for benchmarks and tests: generate_grid (src/mesh/generators.jl:942),
  * close!(dh) numbering, allocate_matrix pattern.  Conventions are documented in DESIGN.md (UNPINNED

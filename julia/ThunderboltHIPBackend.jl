@@ -697,6 +697,56 @@ function gmres!(x::HIPVector{Float64}, A::HIPSparseMatrixCSR{Float64}, b::HIPVec
 end
 l1gs_apply!(z::HIPVector{Float64}, A::HIPSparseMatrixCSR{Float64}, r::HIPVector{Float64}; partsize = 64, sweep = 0) =
     check(ccall((:tb_l1gs_apply, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint, Cint, Ptr{Float64}, Ptr{Float64}), A.ddh.pattern, A.nzval.ptr, partsize, sweep, r.ptr, z.ptr))
+# Geometric multigrid (src/solver/linear/multigrid.jl, ext/ThunderboltFerriteMultigridExt.jl: GMGPrecon over a grid hierarchy, KrylovMGSolver with CG).
+# `patterns`: the tb_pattern handles of the levels, coarsest first (DeviceDofHandlers of the hierarchy's grids with the fine handler's field); `parents`:
+# per refinement (parent_ptr::Vector{Int64}, parent_idx::Vector{Int32}), 0-based, of the fine nodes in the next coarser grid; `prescribed`: the flag
+# vector tb_apply_zero_csr takes (device pointer, or C_NULL).  `setup!` is the numeric phase of every new Jacobian.
+mutable struct HIPGMGPrecon
+    handle::Ptr{Cvoid}
+    degree::Int
+    interval_ratio::Float64
+end
+function HIPGMGPrecon(dev::MI355XDevice, patterns::Vector{Ptr{Cvoid}}, n_nodes::Vector{Int64}, parents::Vector{Tuple{Vector{Int64},Vector{Int32}}};
+                      prescribed::Ptr{UInt8} = Ptr{UInt8}(C_NULL), degree = 2, interval_ratio = 4.0)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:tb_mg_create, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ref{Ptr{Cvoid}}), dev.handle, length(patterns), h))
+    for (l, p) in enumerate(patterns)
+        check(ccall((:tb_mg_set_level, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), h[], l - 1, p))
+    end
+    for (l, (pptr, pidx)) in enumerate(parents)
+        check(ccall((:tb_mg_set_transfer, libtbhip), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Int64}, Ptr{Int32}), h[], l, n_nodes[l + 1], pptr, pidx))
+    end
+    check(ccall((:tb_mg_set_prescribed, libtbhip), Cint, (Ptr{Cvoid}, Ptr{UInt8}), h[], prescribed))
+    mg = HIPGMGPrecon(h[], degree, interval_ratio)
+    finalizer(m -> ccall((:tb_mg_destroy, libtbhip), Cint, (Ptr{Cvoid},), m.handle), mg)
+    return mg
+end
+setup!(mg::HIPGMGPrecon, A::HIPSparseMatrixCSR{Float64}) =
+    check(ccall((:tb_mg_setup, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint, Cdouble), mg.handle, A.nzval.ptr, mg.degree, mg.interval_ratio))
+mg_apply!(z::HIPVector{Float64}, mg::HIPGMGPrecon, r::HIPVector{Float64}) =
+    check(ccall((:tb_mg_apply, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), mg.handle, r.ptr, z.ptr))
+mg_prolong!(xf::HIPVector{Float64}, mg::HIPGMGPrecon, fine_level::Integer, xc::HIPVector{Float64}) =
+    check(ccall((:tb_mg_prolong, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}), mg.handle, fine_level, xc.ptr, xf.ptr))
+mg_restrict!(rc::HIPVector{Float64}, mg::HIPGMGPrecon, fine_level::Integer, rf::HIPVector{Float64}) =
+    check(ccall((:tb_mg_restrict, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}), mg.handle, fine_level, rf.ptr, rc.ptr))
+function mg_level_matrix(mg::HIPGMGPrecon, level::Integer)
+    p = Ref{Ptr{Float64}}(C_NULL)
+    check(ccall((:tb_mg_level_matrix, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ref{Ptr{Float64}}), mg.handle, level, p))
+    return p[]
+end
+function mg_lambda_max(mg::HIPGMGPrecon, level::Integer)
+    r = Ref{Cdouble}(0)
+    check(ccall((:tb_mg_level_lambda_max, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ref{Cdouble}), mg.handle, level, r))
+    return r[]
+end
+# KrylovMGSolver(CG, mg): rebuild the numeric phase from the matrix, then CG with one cycle per iteration
+function pcg_mg!(x::HIPVector{Float64}, A::HIPSparseMatrixCSR{Float64}, b::HIPVector{Float64}, mg::HIPGMGPrecon; rtol = 1e-5, atol = 1e-6, maxiter = 1000, setup = true)
+    setup && setup!(mg, A)
+    it = Ref{Cint}(0); res = Ref{Cdouble}(0)
+    check(ccall((:tb_pcg_solve_mg, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Cint, Ptr{Cvoid}, Ref{Cint}, Ref{Cdouble}),
+        A.ddh.pattern, A.nzval.ptr, b.ptr, x.ptr, rtol, atol, maxiter, mg.handle, it, res))
+    return Int(it[]), res[]
+end
 function absmax(v::HIPVector{Float64}; stride = 1)
     r = Ref{Cdouble}(0)
     check(ccall((:tb_absmax, libtbhip), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ref{Cdouble}), v.dev.handle, v.n ÷ stride, v.ptr, stride, r))

@@ -12,6 +12,9 @@ from .coordinates import (compute_lv_coordinate_system, compute_midmyocardial_se
                           create_lumped_microstructure_model, ODB25LTMicrostructureParameters, evaluate_coordinate_axes, evaluate_coordinate,
                           wrap_rotational, apicobasal_from_laplace)
 from .meshgen import generate_ring_mesh, generate_open_ring_mesh, generate_ideal_lv_mesh_hex, ideal_lv_microstructure, uniform_refinement  # noqa: F401
+from .meshgen import uniform_refinement_with_maps, GridHierarchy  # noqa: F401
+from . import multigrid  # noqa: F401
+from .multigrid import GMGPrecon, PMGPrecon, ChainedMGPrecon, KrylovMGSolver, MultigridHierarchy  # noqa: F401
 from . import chamber  # noqa: F401
 from .chamber import (RSAFDQ2022SurrogateVolume, Hirschvogel2017SurrogateVolume, ConstantChamberVolume, ChamberVolumeCoupling,  # noqa: F401
                       LumpedFluidSolidCoupler, ChamberForm, ChamberTying, compute_chamber_volume, SchurComplementLinearSolver, BlockedChamberSystem,

@@ -205,6 +205,18 @@ SIGNATURES = {
     "tb_apply_zero_csr": (C.c_int, [vp, vp, vp, vp, C.c_double]),
     "tb_meandiag": (C.c_int, [vp, vp, C.POINTER(C.c_double)]),
     "tb_max": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.POINTER(C.c_double)]),
+    "tb_mg_create": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
+    "tb_mg_set_level": (C.c_int, [vp, C.c_int, vp]),
+    "tb_mg_set_transfer": (C.c_int, [vp, C.c_int, C.c_int64, c_i64p, c_i32p]),
+    "tb_mg_set_prescribed": (C.c_int, [vp, vp]),
+    "tb_mg_setup": (C.c_int, [vp, vp, C.c_int, C.c_double]),
+    "tb_mg_apply": (C.c_int, [vp, vp, vp]),
+    "tb_mg_level_matrix": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
+    "tb_mg_level_lambda_max": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double)]),
+    "tb_mg_prolong": (C.c_int, [vp, C.c_int, vp, vp]),
+    "tb_mg_restrict": (C.c_int, [vp, C.c_int, vp, vp]),
+    "tb_mg_destroy": (C.c_int, [vp]),
+    "tb_pcg_solve_mg": (C.c_int, [vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "tb_host_generate_grid_hex": (C.c_int, [C.c_int, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_i32p]),
     "tb_host_generate_grid_tet": (C.c_int, [C.c_int, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_i32p]),
     "tb_host_generate_grid_quad": (C.c_int, [C.c_int, C.c_int, c_dp, c_dp, c_dp, c_i32p]),

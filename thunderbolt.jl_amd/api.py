@@ -1100,7 +1100,12 @@ class ChebyshevPrecBuilder:
 
 
 def pcg_solve(pattern, A, b, x, rtol=1e-5, atol=1e-6, maxiter=1000, precond="jacobi"):
-    """CG with precond = None | "jacobi" | L1GSPrecBuilder(partsize) | ChebyshevPrecBuilder(degree)"""
+    """CG with precond = None | "jacobi" | L1GSPrecBuilder(partsize) | ChebyshevPrecBuilder(degree) | GMGPrecon(gh) or its materialised hierarchy
+    (multigrid.py: the numeric phase is rebuilt from `A`, then tb_pcg_solve_mg; Dirichlet dofs need the hierarchy materialised with their handler)"""
+    if hasattr(precond, "materialize"):
+        precond = precond.materialize(pattern)
+    if hasattr(precond, "tb_mg_solve"):
+        return precond.tb_mg_solve(pattern, A, b, x, rtol, atol, maxiter)
     if isinstance(precond, ChebyshevPrecBuilder):
         kind, ps = L.TB_PRECOND_CHEBYSHEV, precond.degree
     else:

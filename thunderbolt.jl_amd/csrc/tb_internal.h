@@ -420,6 +420,10 @@ int launch_l1gs_setup(tb_pattern *pat, const double *A, int ps, double *d_dtilde
 int launch_l1gs_apply(tb_pattern *pat, const double *A, const double *d_dtilde, int ps, int symmetric, const double *r, double *z);
 int launch_pcg_l1gs(tb_pattern *pat, const double *A, const double *b, double *x, double rtol, double atol, int maxiter, int ps, int *iters, double *resnorm);
 int launch_pcg_chebyshev(tb_pattern *pat, const double *A, const double *b, double *x, double rtol, double atol, int maxiter, int degree, int *iters, double *resnorm);
+int estimate_lambda_max(tb_pattern *pat, const double *A, const double *dinv, double *w, double *v, double *vp, double *t, double *sq, double *S2,
+                        double *lmax_out); // Lanczos + Gershgorin estimate of λmax(D⁻¹A): five scratch vectors, two device scalars; reads back
+int launch_pcg_apply(tb_pattern *pat, const double *A, const double *b, double *x, double rtol, double atol, int maxiter,
+                     int (*apply)(void *ctx, const double *r, double *z), void *ctx, const char *what, int *iters, double *resnorm);
 int launch_cgd_dot(tb_device *dev, int64_t n, const double *w, const double *a, const double *b, double *d_out);
 int launch_cgd_update(tb_device *dev, int64_t n, const double *w, const double *dinv, const double *p, const double *Ap, double *x, double *r,
                       const double *d_rz, const double *d_pAp, double *d_out3);

@@ -579,18 +579,15 @@ k_pcg_update_dev(int64_t n, const double *__restrict__ rz_new, const double *__r
     block_sum_to(c, rr);
 }
 
-int launch_pcg_chebyshev(tb_pattern *pat, const double *A, const double *b, double *x, double rtol, double atol, int maxiter, int degree, int *iters, double *resnorm)
+// λmax(D⁻¹A) of the Chebyshev preconditioner and of the multigrid smoother (tb_multigrid.hip).  w, v, vp, t, sq: five scratch vectors of n doubles,
+// S2: two device scalars; dinv may hold zeros (dofs the caller has masked out: they drop out of the spectrum).  Reads scalars back.
+int estimate_lambda_max(tb_pattern *pat, const double *A, const double *dinv, double *w, double *v, double *vp, double *t, double *sq, double *S2, double *lmax_out)
 {
     tb_device *dev = pat->mesh->dev;
-    TB_NO_CAPTURE(dev); // reads scalars back (convergence looks)
+    TB_NO_CAPTURE(dev); // reads scalars back
     const int64_t n = pat->n_rows;
-    double *r = krylov_ws(pat, 7 * (size_t)n + 16); // r, z, p, Ap, D⁻¹, d, w, scalars
-    if (!r) return TB_ERR_HIP;
-    pat->cg_dinv_of = nullptr; // the workspace no longer holds launch_cg's D⁻¹
-    double *z = r + n, *p = z + n, *Ap = p + n, *dinv = Ap + n, *d = dinv + n, *w = d + n, *S = w + n; // S: rz | rz_new | pAp | rr | flag | power sums
     const unsigned g = grid_for(dev, n, 256);
-    int rc = launch_extract_inverse_diagonal(pat, A, dinv);
-    if (rc) return rc;
+    int rc;
     // λmax(D⁻¹A) = λmax(D^-½ A D^-½): Gershgorin bound (safe, loose), sharpened by the largest Ritz value of 24 Lanczos steps (converges from
     // below, within a per cent after a few tens of steps) inflated by 5 % — an interval that misses the top of the spectrum would make the
     // polynomial indefinite there
@@ -602,11 +599,10 @@ int launch_pcg_chebyshev(tb_pattern *pat, const double *A, const double *b, doub
     {
         constexpr int KL = 24;
         double al[KL], be[KL + 1], h[2];
-        double *v = z, *vp = p, *t = Ap, *sq = d; // scratch: the solver's vectors are not in use yet
         hipLaunchKernelGGL(k_lanczos_init, dim3(g), dim3(256), 0, dev->stream, n, dinv, w, sq, v, vp);
-        TB_HIP(hipMemsetAsync(S + 8, 0, 2 * sizeof(double), dev->stream));
-        enqueue_dot(dev, n, v, v, S + 8);
-        TB_TRY(read_back(dev, h, S + 8, 1));
+        TB_HIP(hipMemsetAsync(S2, 0, 2 * sizeof(double), dev->stream));
+        enqueue_dot(dev, n, v, v, S2);
+        TB_TRY(read_back(dev, h, S2, 1));
         int kdone = 0;
         if (h[0] > 0.0) {
             hipLaunchKernelGGL(k_scale_to, dim3(g), dim3(256), 0, dev->stream, n, 1.0 / std::sqrt(h[0]), v, v);
@@ -615,12 +611,12 @@ int launch_pcg_chebyshev(tb_pattern *pat, const double *A, const double *b, doub
                 hipLaunchKernelGGL(k_mul_to, dim3(g), dim3(256), 0, dev->stream, n, sq, v, t);            // t = D^-½ v
                 rc = launch_spmv(pat, A, t, 1.0, 0.0, w);                                                    // w = A t
                 if (rc) return rc;
-                TB_HIP(hipMemsetAsync(S + 8, 0, 2 * sizeof(double), dev->stream));
-                hipLaunchKernelGGL(k_lanczos_a, dim3(grid_red(dev, n)), dim3(1024), 0, dev->stream, n, sq, be[k], vp, v, w, S + 8); // w = D^-½ w − β v₋₁; α = w·v
-                TB_TRY(read_back(dev, h, S + 8, 1));
+                TB_HIP(hipMemsetAsync(S2, 0, 2 * sizeof(double), dev->stream));
+                hipLaunchKernelGGL(k_lanczos_a, dim3(grid_red(dev, n)), dim3(1024), 0, dev->stream, n, sq, be[k], vp, v, w, S2); // w = D^-½ w − β v₋₁; α = w·v
+                TB_TRY(read_back(dev, h, S2, 1));
                 al[k] = h[0];
-                hipLaunchKernelGGL(k_lanczos_b, dim3(grid_red(dev, n)), dim3(1024), 0, dev->stream, n, al[k], v, w, S + 9);  // w −= α v; ‖w‖²
-                TB_TRY(read_back(dev, h, S + 9, 1));
+                hipLaunchKernelGGL(k_lanczos_b, dim3(grid_red(dev, n)), dim3(1024), 0, dev->stream, n, al[k], v, w, S2 + 1);  // w −= α v; ‖w‖²
+                TB_TRY(read_back(dev, h, S2 + 1, 1));
                 kdone = k + 1;
                 be[k + 1] = std::sqrt(h[0]);
                 if (!(be[k + 1] > 1e-12 * std::fabs(al[k]))) break;                                           // invariant subspace: the Ritz values are exact
@@ -647,23 +643,21 @@ int launch_pcg_chebyshev(tb_pattern *pat, const double *A, const double *b, doub
             lmax = std::min(gersh, 1.05 * hi);
         }
     }
-    static const double ratio_env = tune_env("TB_CHEB_RATIO") ? atof(tune_env("TB_CHEB_RATIO")) : 0.0;
-    const int m = degree < 1 ? 1 : degree;
-    const double lmin = lmax / (ratio_env > 1.0 ? ratio_env : std::max(4.0, 1.8 * m * m));
-    const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sigma1 = theta / delta;
-    auto precondition = [&]() -> int { // z = p_m(D⁻¹A) D⁻¹ r  (Saad, Iterative Methods, Alg. 12.1, started from zero)
-        double rho = 1.0 / sigma1;
-        hipLaunchKernelGGL(k_cheb_step, dim3(g), dim3(256), 0, dev->stream, n, 0.0, 1.0 / theta, dinv, r, (const double *)nullptr, d, z);
-        for (int k = 1; k < m; ++k) {
-            int rc2 = launch_spmv(pat, A, z, 1.0, 0.0, w);
-            if (rc2) return rc2;
-            const double rho_new = 1.0 / (2.0 * sigma1 - rho);
-            hipLaunchKernelGGL(k_cheb_step, dim3(g), dim3(256), 0, dev->stream, n, rho_new * rho, 2.0 * rho_new / delta, dinv, r, w, d, z);
-            rho = rho_new;
-        }
-        return TB_OK;
-    };
-    rc = launch_spmv(pat, A, x, 1.0, 0.0, Ap);
+    *lmax_out = lmax;
+    return TB_OK;
+}
+
+// The device-scalar PCG loop of the preconditioners that are applied by launches alone (Chebyshev polynomial, multigrid cycle): precondition()
+// leaves z = M⁻¹ r.  r, z, p, Ap: n doubles each; S: rz | rz_new | pAp | rr | flag (8 doubles).  `what` names the operator in the
+// not-positive-definite message.
+template <class Precondition>
+static int pcg_loop(tb_pattern *pat, const double *A, const double *b, double *x, double rtol, double atol, int maxiter, double *r, double *z, double *p,
+                    double *Ap, double *S, Precondition precondition, const char *what, int *iters, double *resnorm)
+{
+    tb_device *dev = pat->mesh->dev;
+    const int64_t n = pat->n_rows;
+    const unsigned g = grid_for(dev, n, 256);
+    int rc = launch_spmv(pat, A, x, 1.0, 0.0, Ap);
     if (rc) return rc;
     double h[3];
     TB_HIP(hipMemsetAsync(S, 0, 8 * sizeof(double), dev->stream));
@@ -689,13 +683,62 @@ int launch_pcg_chebyshev(tb_pattern *pat, const double *A, const double *b, doub
             hipLaunchKernelGGL(k_pcg_update_dev, dim3(grid_red(dev, n)), dim3(1024), 0, dev->stream, n, S + 1, S + 2, p, Ap, x, r, S + 3, S + 4);
         }
         TB_TRY(read_back(dev, h, S + 3, 2));
-        if (h[1] != 0.0) { set_error("tb_pcg_solve: matrix or Chebyshev preconditioner is not positive definite (pᵀAp = %g)", h[1] == -1e-300 ? 0.0 : h[1]); return TB_ERR_BAD_ARG; }
+        if (h[1] != 0.0) { set_error("tb_pcg_solve: matrix or %s is not positive definite (pᵀAp = %g)", what, h[1] == -1e-300 ? 0.0 : h[1]); return TB_ERR_BAD_ARG; }
         rnorm = std::sqrt(h[0]);
     }
     TB_HIP(hipGetLastError());
     if (iters) *iters = it;
     if (resnorm) *resnorm = rnorm;
     return TB_OK;
+}
+
+// PCG with z = M⁻¹ r supplied by the caller as enqueue-only launches (tb_pcg_solve_mg: one multigrid cycle)
+int launch_pcg_apply(tb_pattern *pat, const double *A, const double *b, double *x, double rtol, double atol, int maxiter,
+                     int (*apply)(void *ctx, const double *r, double *z), void *ctx, const char *what, int *iters, double *resnorm)
+{
+    tb_device *dev = pat->mesh->dev;
+    TB_NO_CAPTURE(dev); // reads scalars back (convergence looks)
+    const int64_t n = pat->n_rows;
+    double *r = krylov_ws(pat, 4 * (size_t)n + 8); // r, z, p, Ap, scalars
+    if (!r) return TB_ERR_HIP;
+    pat->cg_dinv_of = nullptr; // the workspace no longer holds launch_cg's D⁻¹
+    double *z = r + n, *p = z + n, *Ap = p + n, *S = Ap + n;
+    TB_HIP(hipMemsetAsync(p, 0, sizeof(double) * n, dev->stream)); // the first direction is p = z + 0·p: whatever a fresh workspace holds (a NaN pattern) must not enter it
+    return pcg_loop(pat, A, b, x, rtol, atol, maxiter, r, z, p, Ap, S, [&]() -> int { return apply(ctx, r, z); }, what, iters, resnorm);
+}
+
+int launch_pcg_chebyshev(tb_pattern *pat, const double *A, const double *b, double *x, double rtol, double atol, int maxiter, int degree, int *iters, double *resnorm)
+{
+    tb_device *dev = pat->mesh->dev;
+    TB_NO_CAPTURE(dev); // reads scalars back (convergence looks)
+    const int64_t n = pat->n_rows;
+    double *r = krylov_ws(pat, 7 * (size_t)n + 16); // r, z, p, Ap, D⁻¹, d, w, scalars
+    if (!r) return TB_ERR_HIP;
+    pat->cg_dinv_of = nullptr; // the workspace no longer holds launch_cg's D⁻¹
+    double *z = r + n, *p = z + n, *Ap = p + n, *dinv = Ap + n, *d = dinv + n, *w = d + n, *S = w + n; // S: rz | rz_new | pAp | rr | flag | power sums
+    const unsigned g = grid_for(dev, n, 256);
+    int rc = launch_extract_inverse_diagonal(pat, A, dinv);
+    if (rc) return rc;
+    double lmax = 0.0;
+    rc = estimate_lambda_max(pat, A, dinv, w, z, p, Ap, d, S + 8, &lmax); // scratch: the solver's vectors are not in use yet
+    if (rc) return rc;
+    static const double ratio_env = tune_env("TB_CHEB_RATIO") ? atof(tune_env("TB_CHEB_RATIO")) : 0.0;
+    const int m = degree < 1 ? 1 : degree;
+    const double lmin = lmax / (ratio_env > 1.0 ? ratio_env : std::max(4.0, 1.8 * m * m));
+    const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sigma1 = theta / delta;
+    auto precondition = [&]() -> int { // z = p_m(D⁻¹A) D⁻¹ r  (Saad, Iterative Methods, Alg. 12.1, started from zero)
+        double rho = 1.0 / sigma1;
+        hipLaunchKernelGGL(k_cheb_step, dim3(g), dim3(256), 0, dev->stream, n, 0.0, 1.0 / theta, dinv, r, (const double *)nullptr, d, z);
+        for (int k = 1; k < m; ++k) {
+            int rc2 = launch_spmv(pat, A, z, 1.0, 0.0, w);
+            if (rc2) return rc2;
+            const double rho_new = 1.0 / (2.0 * sigma1 - rho);
+            hipLaunchKernelGGL(k_cheb_step, dim3(g), dim3(256), 0, dev->stream, n, rho_new * rho, 2.0 * rho_new / delta, dinv, r, w, d, z);
+            rho = rho_new;
+        }
+        return TB_OK;
+    };
+    return pcg_loop(pat, A, b, x, rtol, atol, maxiter, r, z, p, Ap, S, precondition, "Chebyshev preconditioner", iters, resnorm);
 }
 
 // ---- sub-structured CG over several devices: weighted sums (a dof held by k ranks counts 1/k), every scalar in caller-owned device memory ----

@@ -1,0 +1,512 @@
+// tb_multigrid.hip — geometric multigrid preconditioner on nested first-order hexahedral grids (GMGPrecon of the reference: src/solver/linear/multigrid.jl,
+// ext/ThunderboltFerriteMultigridExt.jl).  The plans come from tb_mg_planners.cpp (P row-wise, Pᵀ row-wise, the gather plan of PᵀAP); this file holds
+// the hierarchy object, the numeric Galerkin kernel, the transfers, the Chebyshev–Jacobi smoother step, the coarsest inverse and the V-cycle driver.
+// Every sum has one recorded order and no kernel uses an atomic: two setups, and two applications, give the same bits.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+
+#include "tb_internal.h"
+#include "tb_mg_planners.hpp"
+#include "tb_reduce.hpp"
+
+namespace tb {
+
+static_assert(mgplan::ERR_BAD_ARG == TB_ERR_BAD_ARG && mgplan::ERR_PATTERN == TB_ERR_PATTERN && mgplan::ERR_UNSUPPORTED == TB_ERR_UNSUPPORTED, "planner codes");
+
+constexpr int MG_COARSEST_MAX = 1024; // dofs of the coarsest level: its inverse is dense
+
+struct MgLevel {
+    tb_pattern *pat = nullptr;
+    int64_t n = 0, nnz = 0;
+    double *d_A = nullptr;          // the level's operator: owned below the finest level
+    const double *A = nullptr;      // what the cycle reads (finest: the caller's array of the latest setup)
+    double *d_vec = nullptr;        // dinv | d | w | x | r (x, r: below the finest level) and, during setup, the Lanczos scratch
+    double *dinv = nullptr, *d = nullptr, *w = nullptr, *x = nullptr, *r = nullptr;
+    uint8_t *d_presc = nullptr;     // flags of the level's prescribed dofs (NULL: none)
+    std::vector<uint8_t> h_presc;
+    double lmax = 0.0;
+    // to the level below (levels ≥ 1)
+    std::vector<int64_t> parent_ptr;
+    std::vector<int32_t> parent_idx;
+    bool has_transfer = false;
+    int64_t *d_pptr = nullptr, *d_rptr = nullptr, *d_gptr = nullptr, *d_cdiag = nullptr;
+    int32_t *d_pcol = nullptr, *d_rcol = nullptr;
+    uint8_t *d_pexp = nullptr, *d_rexp = nullptr;
+    uint32_t *d_gterms = nullptr;
+    int64_t n_terms = 0;
+};
+
+} // namespace tb
+
+struct tb_mg {
+    tb_device *dev = nullptr;
+    std::vector<tb::MgLevel> lv;
+    bool planned = false, ready = false;
+    int degree = 2;
+    double ratio = 4.0;
+    double *d_cinv = nullptr; // dense inverse of the coarsest operator
+    double *d_scal = nullptr; // two scalars of the λmax estimate
+};
+
+namespace tb {
+
+// 2^−e for e in 0…7 without a table: the exponent field of 1.0 lowered by e
+__device__ __forceinline__ double pow2_neg(unsigned e) { return __longlong_as_double((long long)(1023u - e) << 52); }
+
+// A_c[k] = Σ over the recorded terms of 2^−e · A_f[fine nz]: 16 lanes share a coarse non-zero (≈ 90 terms each on a scalar field: the term words
+// are read as 64-byte runs), lane sums in term order, then a fixed butterfly over the 16 lanes.
+__global__ void __launch_bounds__(256)
+k_mg_galerkin(int64_t cnnz, const int64_t *__restrict__ gptr, const uint32_t *__restrict__ terms, const double *__restrict__ Af, double *__restrict__ Ac)
+{
+    const int64_t k = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    if (k >= cnnz) return; // (the 16 lanes of a group leave together)
+    const int sub = threadIdx.x & 15;
+    const int64_t lo = gptr[k], hi = gptr[k + 1];
+    double s = 0.0;
+    for (int64_t q = lo + sub; q < hi; q += 16) {
+        const uint32_t t = terms[q];
+        s += pow2_neg(t >> mgplan::TERM_BITS) * Af[t & ((1u << mgplan::TERM_BITS) - 1u)];
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 16);
+    if (sub == 0) Ac[k] = s;
+}
+
+// one workgroup: the diagonal of every prescribed dof of a coarse level becomes the mean |diagonal| of its free dofs (fixed order: strided lane sums, LDS tree)
+__global__ void __launch_bounds__(1024)
+k_mg_fill_diag(int64_t n, const int64_t *__restrict__ diagpos, const uint8_t *__restrict__ presc, double *__restrict__ A)
+{
+    __shared__ double ssum[1024];
+    __shared__ double scnt[1024];
+    double s = 0.0, c = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += 1024)
+        if (!presc[i]) { s += fabs(A[diagpos[i]]); c += 1.0; }
+    ssum[threadIdx.x] = s; scnt[threadIdx.x] = c;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) { ssum[threadIdx.x] += ssum[threadIdx.x + o]; scnt[threadIdx.x] += scnt[threadIdx.x + o]; }
+        __syncthreads();
+    }
+    const double fill = scnt[0] > 0.0 ? ssum[0] / scnt[0] : 1.0;
+    for (int64_t i = threadIdx.x; i < n; i += 1024)
+        if (presc[i]) A[diagpos[i]] = fill;
+}
+
+__global__ void __launch_bounds__(256) k_mg_mask(int64_t n, const uint8_t *__restrict__ presc, double *__restrict__ dinv)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        if (presc[i]) dinv[i] = 0.0;
+}
+
+// One step of the Chebyshev iteration on D⁻¹A (Saad, Iterative Methods, Alg. 12.1).  MODE 0: first step from x = 0 (d = c2·D⁻¹r, x = d, no product
+// needed); MODE 1: first step from a given x (w = A x; d = c2·D⁻¹(r − w), x += d); MODE 2: d = c1·d + c2·D⁻¹(r − w), x += d.
+template <int MODE>
+__global__ void __launch_bounds__(256)
+k_mg_cheb(int64_t n, double c1, double c2, const double *__restrict__ dinv, const double *__restrict__ r, const double *__restrict__ w, double *__restrict__ d,
+          double *__restrict__ x)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        if (MODE == 0) {
+            const double di = c2 * dinv[i] * r[i];
+            d[i] = di; x[i] = di;
+        } else {
+            const double g = c2 * dinv[i] * (r[i] - w[i]);
+            const double di = MODE == 1 ? g : c1 * d[i] + g;
+            d[i] = di; x[i] += di;
+        }
+    }
+}
+
+// r_c = Pᵀ(r − w) (w NULL: Pᵀ r): one thread per coarse dof gathers its fine dofs (at most 27 per component)
+__global__ void __launch_bounds__(256)
+k_mg_restrict(int64_t nc, const int64_t *__restrict__ rptr, const int32_t *__restrict__ rcol, const uint8_t *__restrict__ rexp, const double *__restrict__ r,
+              const double *__restrict__ w, double *__restrict__ rc)
+{
+    const int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (I >= nc) return;
+    double s = 0.0;
+    for (int64_t q = rptr[I]; q < rptr[I + 1]; ++q) {
+        const int32_t i = rcol[q];
+        s += pow2_neg(rexp[q]) * (w ? r[i] - w[i] : r[i]);
+    }
+    rc[I] = s;
+}
+
+// x_f (+)= P x_c: one thread per fine dof gathers its at most 8 parents
+template <bool ADD>
+__global__ void __launch_bounds__(256)
+k_mg_prolong(int64_t nf, const int64_t *__restrict__ pptr, const int32_t *__restrict__ pcol, const uint8_t *__restrict__ pexp, const double *__restrict__ xc,
+             double *__restrict__ xf)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nf) return;
+    double s = 0.0;
+    for (int64_t q = pptr[i]; q < pptr[i + 1]; ++q) s += pow2_neg(pexp[q]) * xc[pcol[q]];
+    if (ADD) xf[i] += s; else xf[i] = s;
+}
+
+// One workgroup: C = A⁻¹ of the coarsest operator (n ≤ 1024), dense, by Gauss–Jordan elimination in place without pivoting (the operator is symmetric
+// positive definite; a prescribed dof is a row of the identity scaled by its diagonal), symmetrised at the end.  Rows go to the 16 waves, columns to
+// the lanes; the workgroup's barriers order the global-memory phases.
+__global__ void __launch_bounds__(1024)
+k_mg_dense_inverse(int n, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, const double *__restrict__ nz, double *__restrict__ C)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    for (int i = wv; i < n; i += nw)
+        for (int j = lane; j < n; j += 64) C[(size_t)i * n + j] = 0.0;
+    __syncthreads();
+    for (int i = wv; i < n; i += nw)
+        for (int64_t k = rowptr[i] + lane; k < rowptr[i + 1]; k += 64) C[(size_t)i * n + colidx[k]] = nz[k];
+    __syncthreads();
+    for (int k = 0; k < n; ++k) {
+        const double piv = 1.0 / C[(size_t)k * n + k];
+        for (int i = wv; i < n; i += nw) {
+            if (i == k) continue;
+            const double f = C[(size_t)i * n + k] * piv;
+            for (int j = lane; j < n; j += 64)
+                if (j != k) C[(size_t)i * n + j] -= f * C[(size_t)k * n + j];
+        }
+        __syncthreads();
+        for (int j = threadIdx.x; j < n; j += blockDim.x)
+            if (j != k) { C[(size_t)k * n + j] *= piv; C[(size_t)j * n + k] *= -piv; }
+        if (threadIdx.x == 0) C[(size_t)k * n + k] = piv;
+        __syncthreads();
+    }
+    for (int i = wv; i < n; i += nw)
+        for (int j = i + 1 + lane; j < n; j += 64) {
+            const double s = 0.5 * (C[(size_t)i * n + j] + C[(size_t)j * n + i]);
+            C[(size_t)i * n + j] = s; C[(size_t)j * n + i] = s;
+        }
+}
+
+// x = C r, dense: one wavefront per row
+__global__ void __launch_bounds__(256)
+k_mg_dense_apply(int n, const double *__restrict__ C, const double *__restrict__ r, double *__restrict__ x)
+{
+    const int lane = threadIdx.x & 63;
+    const int i = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    if (i >= n) return;
+    double s = 0.0;
+    for (int j = lane; j < n; j += 64) s += C[(size_t)i * n + j] * r[j];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) x[i] = s;
+}
+
+static inline unsigned blocks_of(int64_t n, int bs) { return (unsigned)std::max<int64_t>(1, (n + bs - 1) / bs); }
+
+static void free_plans(tb_mg *mg)
+{
+    for (MgLevel &L : mg->lv) {
+        void *ptrs[] = {L.d_A, L.d_vec, L.d_presc, L.d_pptr, L.d_rptr, L.d_gptr, L.d_cdiag, L.d_pcol, L.d_rcol, L.d_pexp, L.d_rexp, L.d_gterms};
+        for (void *p : ptrs) if (p) (void)hipFree(p);
+        L.d_A = nullptr; L.d_vec = nullptr; L.d_presc = nullptr; L.d_pptr = L.d_rptr = L.d_gptr = L.d_cdiag = nullptr;
+        L.d_pcol = L.d_rcol = nullptr; L.d_pexp = L.d_rexp = nullptr; L.d_gterms = nullptr;
+        L.A = nullptr;
+    }
+    if (mg->d_cinv) (void)hipFree(mg->d_cinv);
+    mg->d_cinv = nullptr;
+    mg->planned = mg->ready = false;
+}
+
+static mgplan::LevelView view_of(const tb_pattern *p)
+{
+    const tb_mesh *m = p->mesh;
+    return mgplan::LevelView{m->n_nodes, m->n_cells, m->ndofs, m->nverts, m->ncomp, m->h_conn.data(), m->h_cell_dofs.data(), p->h_rowptr.data(), p->h_colidx.data()};
+}
+
+// symbolic phase: transfers, Galerkin plans, level storage, the SpMV plan of every level
+static int build_plans(tb_mg *mg)
+{
+    tb_device *dev = mg->dev;
+    TB_NO_CAPTURE(dev);
+    const int nl = (int)mg->lv.size();
+    for (int l = 0; l < nl; ++l) {
+        TB_REQUIRE(mg->lv[l].pat, "tb_mg_setup: level %d has no pattern (tb_mg_set_level)", l);
+        TB_REQUIRE(l == 0 || mg->lv[l].has_transfer, "tb_mg_setup: level %d has no transfer to level %d (tb_mg_set_transfer)", l, l - 1);
+    }
+    if (mg->lv[0].pat->n_rows > MG_COARSEST_MAX) {
+        set_error("tb_mg_setup: the coarsest level has %lld dofs; its dense inverse takes at most %d - add a level", (long long)mg->lv[0].pat->n_rows, MG_COARSEST_MAX);
+        return TB_ERR_UNSUPPORTED;
+    }
+    PlanTimer timer("multigrid");
+    for (int l = nl - 1; l >= 0; --l) {
+        MgLevel &L = mg->lv[l];
+        L.n = L.pat->n_rows;
+        L.nnz = L.pat->nnz;
+        if (l > 0) {
+            MgLevel &Cl = mg->lv[l - 1];
+            const mgplan::LevelView fv = view_of(L.pat), cv = view_of(Cl.pat);
+            TB_REQUIRE((int64_t)L.parent_ptr.size() == fv.n_nodes + 1, "tb_mg_setup: the transfer of level %d lists %lld nodes, its pattern's grid has %lld", l,
+                       (long long)L.parent_ptr.size() - 1, (long long)fv.n_nodes);
+            const uint8_t *flags = L.h_presc.empty() ? nullptr : L.h_presc.data();
+            mgplan::Transfer t;
+            mgplan::Galerkin g;
+            TB_TRY(mgplan::build_transfer(fv, cv, L.parent_ptr.data(), L.parent_idx.data(), flags, t));
+            timer.lap("transfer");
+            TB_TRY(mgplan::build_galerkin(fv, cv, t, flags, g));
+            timer.lap("galerkin plan");
+            if (flags) Cl.h_presc = t.coarse_prescribed; else Cl.h_presc.clear();
+            L.n_terms = (int64_t)g.terms.size();
+            TB_TRY(upload_all(dev, t.p_ptr, &L.d_pptr, t.p_col, &L.d_pcol, t.p_exp, &L.d_pexp, t.r_ptr, &L.d_rptr, t.r_col, &L.d_rcol, t.r_exp, &L.d_rexp,
+                              g.ptr, &L.d_gptr, g.terms, &L.d_gterms, g.diag_pos, &L.d_cdiag));
+        }
+        if (!L.h_presc.empty() && l < nl - 1) TB_TRY(upload(dev, L.h_presc, &L.d_presc));
+        // dinv | d | w | x | r; the λmax estimate of setup borrows d, w, x, r and one more vector
+        TB_HIP(hipMalloc((void **)&L.d_vec, sizeof(double) * 6 * (size_t)std::max<int64_t>(L.n, 1)));
+        L.dinv = L.d_vec; L.d = L.dinv + L.n; L.w = L.d + L.n; L.x = L.w + L.n; L.r = L.x + L.n;
+        if (l < nl - 1) TB_HIP(hipMalloc((void **)&L.d_A, sizeof(double) * (size_t)std::max<int64_t>(L.nnz, 1)));
+        TB_TRY(spmv_plans(L.pat));
+    }
+    TB_HIP(hipMalloc((void **)&mg->d_cinv, sizeof(double) * (size_t)mg->lv[0].n * (size_t)mg->lv[0].n));
+    if (!mg->d_scal) TB_HIP(hipMalloc((void **)&mg->d_scal, 16 * sizeof(double)));
+    mg->planned = true;
+    return TB_OK;
+}
+
+static int smooth(tb_mg *mg, int l, const double *r, double *x, bool from_zero)
+{
+    MgLevel &L = mg->lv[l];
+    tb_device *dev = mg->dev;
+    const unsigned g = grid_for(dev, L.n, 256);
+    const double lmax = L.lmax, lmin = lmax / mg->ratio;
+    const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sigma1 = theta / delta;
+    double rho = 1.0 / sigma1;
+    if (from_zero) hipLaunchKernelGGL(k_mg_cheb<0>, dim3(g), dim3(256), 0, dev->stream, L.n, 0.0, 1.0 / theta, L.dinv, r, (const double *)nullptr, L.d, x);
+    else {
+        TB_TRY(launch_spmv(L.pat, L.A, x, 1.0, 0.0, L.w));
+        hipLaunchKernelGGL(k_mg_cheb<1>, dim3(g), dim3(256), 0, dev->stream, L.n, 0.0, 1.0 / theta, L.dinv, r, L.w, L.d, x);
+    }
+    for (int k = 1; k < mg->degree; ++k) {
+        TB_TRY(launch_spmv(L.pat, L.A, x, 1.0, 0.0, L.w));
+        const double rho_new = 1.0 / (2.0 * sigma1 - rho);
+        hipLaunchKernelGGL(k_mg_cheb<2>, dim3(g), dim3(256), 0, dev->stream, L.n, rho_new * rho, 2.0 * rho_new / delta, L.dinv, r, L.w, L.d, x);
+        rho = rho_new;
+    }
+    return TB_OK;
+}
+
+// x = M_l⁻¹ r: V(degree, degree) from x = 0; enqueues only
+static int cycle(tb_mg *mg, int l, const double *r, double *x)
+{
+    tb_device *dev = mg->dev;
+    MgLevel &L = mg->lv[l];
+    if (l == 0) {
+        hipLaunchKernelGGL(k_mg_dense_apply, dim3(blocks_of(L.n * 64, 256)), dim3(256), 0, dev->stream, (int)L.n, mg->d_cinv, r, x);
+        return TB_OK;
+    }
+    MgLevel &Cl = mg->lv[l - 1];
+    TB_TRY(smooth(mg, l, r, x, true));
+    TB_TRY(launch_spmv(L.pat, L.A, x, 1.0, 0.0, L.w));
+    hipLaunchKernelGGL(k_mg_restrict, dim3(blocks_of(Cl.n, 256)), dim3(256), 0, dev->stream, Cl.n, L.d_rptr, L.d_rcol, L.d_rexp, r, (const double *)L.w, Cl.r);
+    TB_TRY(cycle(mg, l - 1, Cl.r, Cl.x));
+    hipLaunchKernelGGL(k_mg_prolong<true>, dim3(blocks_of(L.n, 256)), dim3(256), 0, dev->stream, L.n, L.d_pptr, L.d_pcol, L.d_pexp, (const double *)Cl.x, x);
+    TB_TRY(smooth(mg, l, r, x, false));
+    return TB_OK;
+}
+
+static int mg_apply_cb(void *ctx, const double *r, double *z)
+{
+    tb_mg *mg = (tb_mg *)ctx;
+    const int rc = cycle(mg, (int)mg->lv.size() - 1, r, z);
+    if (rc) return rc;
+    TB_HIP(hipGetLastError());
+    return TB_OK;
+}
+
+} // namespace tb
+
+using namespace tb;
+
+int tb_mg_create(tb_device *dev, int n_levels, tb_mg **out)
+{
+    TB_REQUIRE(dev && out, "tb_mg_create: NULL argument");
+    *out = nullptr;
+    TB_REQUIRE(n_levels >= 2 && n_levels <= 32, "tb_mg_create: n_levels must be in 2..32 (got %d)", n_levels);
+    tb_mg *mg = new tb_mg;
+    mg->dev = dev;
+    mg->lv.resize((size_t)n_levels);
+    *out = mg;
+    return TB_OK;
+}
+
+int tb_mg_destroy(tb_mg *mg)
+{
+    if (!mg) return TB_OK;
+    (void)hipSetDevice(mg->dev->id);
+    free_plans(mg);
+    if (mg->d_scal) (void)hipFree(mg->d_scal);
+    delete mg;
+    return TB_OK;
+}
+
+int tb_mg_set_level(tb_mg *mg, int level, tb_pattern *pat)
+{
+    TB_REQUIRE(mg && pat, "tb_mg_set_level: NULL argument");
+    TB_REQUIRE(level >= 0 && level < (int)mg->lv.size(), "tb_mg_set_level: level %d of %d", level, (int)mg->lv.size());
+    TB_REQUIRE(pat->mesh && pat->mesh->dev == mg->dev, "tb_mg_set_level: the pattern lives on another device");
+    if (pat->mesh->geom_kind != TB_HEX8 || pat->mesh->field_kind != TB_HEX8) {
+        set_error("tb_mg_set_level: the multigrid covers first-order fields on hexahedra only (no p-levels, no second-order fields, no tetrahedra)");
+        return TB_ERR_UNSUPPORTED;
+    }
+    TB_HIP(hipSetDevice(mg->dev->id));
+    free_plans(mg);
+    mg->lv[level].pat = pat;
+    return TB_OK;
+}
+
+int tb_mg_set_transfer(tb_mg *mg, int fine_level, int64_t n_fine_nodes, const int64_t *parent_ptr, const int32_t *parent_idx)
+{
+    TB_REQUIRE(mg && parent_ptr && parent_idx, "tb_mg_set_transfer: NULL argument");
+    TB_REQUIRE(fine_level >= 1 && fine_level < (int)mg->lv.size(), "tb_mg_set_transfer: fine_level %d of 1..%d", fine_level, (int)mg->lv.size() - 1);
+    MgLevel &L = mg->lv[fine_level], &Cl = mg->lv[fine_level - 1];
+    TB_REQUIRE(L.pat && Cl.pat, "tb_mg_set_transfer: set the patterns of levels %d and %d first (tb_mg_set_level)", fine_level, fine_level - 1);
+    TB_REQUIRE(L.pat->mesh->ncomp == Cl.pat->mesh->ncomp, "tb_mg_set_transfer: the levels carry %d and %d components", L.pat->mesh->ncomp, Cl.pat->mesh->ncomp);
+    TB_REQUIRE(n_fine_nodes == L.pat->mesh->n_nodes, "tb_mg_set_transfer: %lld fine nodes, but the grid of level %d has %lld: the pattern does not match the transfer",
+               (long long)n_fine_nodes, fine_level, (long long)L.pat->mesh->n_nodes);
+    TB_REQUIRE(parent_ptr[0] == 0, "tb_mg_set_transfer: parent_ptr does not start at 0");
+    const int64_t ncn = Cl.pat->mesh->n_nodes;
+    TB_REQUIRE(ncn <= n_fine_nodes, "tb_mg_set_transfer: level %d has more nodes than level %d", fine_level - 1, fine_level);
+    for (int64_t v = 0; v < n_fine_nodes; ++v) {
+        const int64_t np = parent_ptr[v + 1] - parent_ptr[v];
+        TB_REQUIRE(np == 1 || np == 2 || np == 4 || np == 8, "tb_mg_set_transfer: node %lld has %lld parents (1, 2, 4 or 8)", (long long)v, (long long)np);
+        for (int64_t q = parent_ptr[v]; q < parent_ptr[v + 1]; ++q)
+            TB_REQUIRE(parent_idx[q] >= 0 && parent_idx[q] < ncn, "tb_mg_set_transfer: parent %d of node %lld is not a node of level %d (%lld nodes): the pattern does not match the transfer",
+                       parent_idx[q], (long long)v, fine_level - 1, (long long)ncn);
+        TB_REQUIRE(v >= ncn || (np == 1 && parent_idx[parent_ptr[v]] == v), "tb_mg_set_transfer: coarse node %lld is not its own parent (coarse nodes must be a prefix of the fine nodes)", (long long)v);
+    }
+    TB_HIP(hipSetDevice(mg->dev->id));
+    free_plans(mg);
+    L.parent_ptr.assign(parent_ptr, parent_ptr + n_fine_nodes + 1);
+    L.parent_idx.assign(parent_idx, parent_idx + parent_ptr[n_fine_nodes]);
+    L.has_transfer = true;
+    return TB_OK;
+}
+
+int tb_mg_set_prescribed(tb_mg *mg, const uint8_t *d_prescribed_fine)
+{
+    TB_REQUIRE(mg, "tb_mg_set_prescribed: NULL argument");
+    MgLevel &L = mg->lv.back();
+    TB_REQUIRE(L.pat, "tb_mg_set_prescribed: set the pattern of the finest level first (tb_mg_set_level)");
+    tb_device *dev = mg->dev;
+    TB_NO_CAPTURE(dev);
+    TB_HIP(hipSetDevice(dev->id));
+    free_plans(mg);
+    L.h_presc.clear();
+    if (!d_prescribed_fine) return TB_OK;
+    const size_t n = (size_t)L.pat->n_rows;
+    L.h_presc.resize(n);
+    TB_HIP(hipMemcpyAsync(L.h_presc.data(), d_prescribed_fine, n, hipMemcpyDeviceToHost, dev->stream));
+    TB_SYNC_STREAM(dev);
+    bool any = false;
+    for (uint8_t &f : L.h_presc) { f = f ? 1 : 0; any |= f != 0; }
+    if (!any) L.h_presc.clear();
+    return TB_OK;
+}
+
+int tb_mg_setup(tb_mg *mg, const double *d_Anz_fine, int degree, double interval_ratio)
+{
+    TB_REQUIRE(mg && d_Anz_fine, "tb_mg_setup: NULL argument");
+    TB_REQUIRE(degree >= 1 && degree <= 64, "tb_mg_setup: smoother degree must be in 1..64 (got %d)", degree);
+    TB_REQUIRE(interval_ratio > 1.0 && std::isfinite(interval_ratio), "tb_mg_setup: interval_ratio must be a finite number above 1 (got %g)", interval_ratio);
+    tb_device *dev = mg->dev;
+    TB_NO_CAPTURE(dev); // builds plans, reads λmax back
+    TB_HIP(hipSetDevice(dev->id));
+    mg->ready = false;
+    if (!mg->planned) {
+        const int rc = build_plans(mg);
+        if (rc) { free_plans(mg); return rc; }
+    }
+    const int nl = (int)mg->lv.size();
+    mg->degree = degree;
+    mg->ratio = interval_ratio;
+    MgLevel &F = mg->lv[nl - 1];
+    F.A = d_Anz_fine;
+    if (!F.h_presc.empty() && !F.d_presc) TB_TRY(upload(dev, F.h_presc, &F.d_presc));
+    for (int l = nl - 1; l >= 0; --l) {
+        MgLevel &L = mg->lv[l];
+        if (l < nl - 1) { // A_l = Pᵀ A_{l+1} P
+            MgLevel &U = mg->lv[l + 1];
+            hipLaunchKernelGGL(k_mg_galerkin, dim3(blocks_of(L.nnz * 16, 256)), dim3(256), 0, dev->stream, L.nnz, U.d_gptr, U.d_gterms, U.A, L.d_A);
+            if (L.d_presc) hipLaunchKernelGGL(k_mg_fill_diag, dim3(1), dim3(1024), 0, dev->stream, L.n, U.d_cdiag, L.d_presc, L.d_A);
+            L.A = L.d_A;
+        }
+        if (l == 0) break;
+        TB_TRY(launch_extract_inverse_diagonal(L.pat, L.A, L.dinv));
+        if (L.d_presc) hipLaunchKernelGGL(k_mg_mask, dim3(grid_for(dev, L.n, 256)), dim3(256), 0, dev->stream, L.n, L.d_presc, L.dinv);
+        // scratch of the estimate: w | d, x, r and the sixth vector of the level's block (none of them holds anything between applications)
+        TB_TRY(estimate_lambda_max(L.pat, L.A, L.dinv, L.w, L.d, L.x, L.r, L.r + L.n, mg->d_scal, &L.lmax));
+    }
+    MgLevel &C0 = mg->lv[0];
+    hipLaunchKernelGGL(k_mg_dense_inverse, dim3(1), dim3(1024), 0, dev->stream, (int)C0.n, C0.pat->d_rowptr, C0.pat->d_colidx, C0.A, mg->d_cinv);
+    TB_HIP(hipGetLastError());
+    mg->ready = true;
+    return TB_OK;
+}
+
+int tb_mg_apply(tb_mg *mg, const double *d_r, double *d_z)
+{
+    TB_REQUIRE(mg && d_r && d_z, "tb_mg_apply: NULL argument");
+    TB_REQUIRE(mg->ready, "tb_mg_apply: no numeric setup yet (tb_mg_setup)");
+    TB_REQUIRE(d_r != d_z, "tb_mg_apply: r and z alias");
+    TB_HIP(hipSetDevice(mg->dev->id));
+    return mg_apply_cb(mg, d_r, d_z);
+}
+
+int tb_mg_level_matrix(tb_mg *mg, int level, const double **d_nzval)
+{
+    TB_REQUIRE(mg && d_nzval, "tb_mg_level_matrix: NULL argument");
+    TB_REQUIRE(level >= 0 && level < (int)mg->lv.size(), "tb_mg_level_matrix: level %d of %d", level, (int)mg->lv.size());
+    TB_REQUIRE(mg->ready, "tb_mg_level_matrix: no numeric setup yet (tb_mg_setup)");
+    *d_nzval = mg->lv[level].A;
+    return TB_OK;
+}
+
+int tb_mg_level_lambda_max(tb_mg *mg, int level, double *lmax)
+{
+    TB_REQUIRE(mg && lmax, "tb_mg_level_lambda_max: NULL argument");
+    TB_REQUIRE(level >= 1 && level < (int)mg->lv.size(), "tb_mg_level_lambda_max: level %d of 1..%d (the coarsest level is inverted, not smoothed)", level, (int)mg->lv.size() - 1);
+    TB_REQUIRE(mg->ready, "tb_mg_level_lambda_max: no numeric setup yet (tb_mg_setup)");
+    *lmax = mg->lv[level].lmax;
+    return TB_OK;
+}
+
+int tb_mg_prolong(tb_mg *mg, int fine_level, const double *d_xc, double *d_xf)
+{
+    TB_REQUIRE(mg && d_xc && d_xf, "tb_mg_prolong: NULL argument");
+    TB_REQUIRE(fine_level >= 1 && fine_level < (int)mg->lv.size(), "tb_mg_prolong: fine_level %d of 1..%d", fine_level, (int)mg->lv.size() - 1);
+    TB_REQUIRE(mg->planned, "tb_mg_prolong: the transfers are planned by tb_mg_setup");
+    TB_HIP(hipSetDevice(mg->dev->id));
+    MgLevel &L = mg->lv[fine_level];
+    hipLaunchKernelGGL(k_mg_prolong<false>, dim3(blocks_of(L.n, 256)), dim3(256), 0, mg->dev->stream, L.n, L.d_pptr, L.d_pcol, L.d_pexp, d_xc, d_xf);
+    TB_HIP(hipGetLastError());
+    return TB_OK;
+}
+
+int tb_mg_restrict(tb_mg *mg, int fine_level, const double *d_rf, double *d_rc)
+{
+    TB_REQUIRE(mg && d_rf && d_rc, "tb_mg_restrict: NULL argument");
+    TB_REQUIRE(fine_level >= 1 && fine_level < (int)mg->lv.size(), "tb_mg_restrict: fine_level %d of 1..%d", fine_level, (int)mg->lv.size() - 1);
+    TB_REQUIRE(mg->planned, "tb_mg_restrict: the transfers are planned by tb_mg_setup");
+    TB_HIP(hipSetDevice(mg->dev->id));
+    MgLevel &L = mg->lv[fine_level], &Cl = mg->lv[fine_level - 1];
+    hipLaunchKernelGGL(k_mg_restrict, dim3(blocks_of(Cl.n, 256)), dim3(256), 0, mg->dev->stream, Cl.n, L.d_rptr, L.d_rcol, L.d_rexp, d_rf, (const double *)nullptr, d_rc);
+    TB_HIP(hipGetLastError());
+    return TB_OK;
+}
+
+int tb_pcg_solve_mg(tb_pattern *pat, const double *d_Anz, const double *d_b, double *d_x, double rtol, double atol, int maxiter, tb_mg *mg, int *iters,
+                    double *resnorm)
+{
+    TB_REQUIRE(pat && d_Anz && d_b && d_x && mg, "tb_pcg_solve_mg: NULL argument");
+    TB_REQUIRE(rtol >= 0 && atol >= 0 && maxiter >= 0, "tb_pcg_solve_mg: negative tolerance or iteration limit");
+    TB_REQUIRE(mg->ready, "tb_pcg_solve_mg: no numeric setup yet (tb_mg_setup)");
+    TB_REQUIRE(mg->lv.back().pat == pat, "tb_pcg_solve_mg: the pattern is not the finest level of the hierarchy");
+    TB_REQUIRE(mg->lv.back().A == d_Anz, "tb_pcg_solve_mg: the hierarchy was set up with another matrix array (tb_mg_setup follows every new matrix)");
+    TB_HIP(hipSetDevice(pat->mesh->dev->id));
+    return launch_pcg_apply(pat, d_Anz, d_b, d_x, rtol, atol, maxiter, mg_apply_cb, mg, "multigrid preconditioner", iters, resnorm);
+}

@@ -231,10 +231,9 @@ def ideal_lv_microstructure(g, alpha_endo=np.deg2rad(80.0), alpha_epi=np.deg2rad
 
 
 
-def uniform_refinement(g):
-    """uniform_refinement(grid) for hexahedral grids (src/mesh/tools.jl:257-300): every hexahedron is cut into eight by its edge, face
-    and cell centres; new nodes are appended after the old ones — edge centres, face centres, cell centres — shared between
-    neighbouring cells.  Sets are not transferred (the reference leaves that as a TODO as well)."""
+def _refine_hex(g):
+    """the refined grid of uniform_refinement with the parent nodes of every fine node: (grid, parent_ptr, parent_idx)"""
+
     if g.cell_kind != Hexahedron:
         raise NotImplementedError("uniform_refinement: hexahedral grids")
     conn = g.conn.astype(np.int64)
@@ -271,4 +270,74 @@ def uniform_refinement(g):
                 for v, (a, b, c) in enumerate(((0, 0, 0), (1, 0, 0), (1, 1, 0), (0, 1, 0), (0, 0, 1), (1, 0, 1), (1, 1, 1), (0, 1, 1))):
                     new[:, sub, v] = lat[:, i + a, j + b, k + c]
                 sub += 1
-    return Grid(Hexahedron, xyz, new.reshape(-1, 8))
+    counts = np.concatenate([np.ones(n0, dtype=np.int64), np.full(len(eu), 2, dtype=np.int64), np.full(len(fu), 4, dtype=np.int64),
+                             np.full(nc, 8, dtype=np.int64)])
+    parent_ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    parent_idx = np.concatenate([np.arange(n0), eu.ravel(), fu.ravel(), conn.ravel()]).astype(np.int32)
+    return Grid(Hexahedron, xyz, new.reshape(-1, 8)), parent_ptr, parent_idx
+
+
+def uniform_refinement(g):
+    """uniform_refinement(grid) for hexahedral grids (src/mesh/tools.jl:257-300): every hexahedron is cut into eight by its edge, face
+    and cell centres; new nodes are appended after the old ones — edge centres, face centres, cell centres — shared between
+    neighbouring cells.  Sets are not transferred (the reference leaves that as a TODO as well)."""
+    return _refine_hex(g)[0]
+
+
+# child (i, j, k) of a refined hexahedron is stored at 8·cell + i + 2j + 4k and keeps the parent's vertex order, so its local facet f is parallel to the
+# parent's facet f; the four children on the parent's facet f sit at the parent vertices of that facet
+_HEX_VPOS = ((0, 0, 0), (1, 0, 0), (1, 1, 0), (0, 1, 0), (0, 0, 1), (1, 0, 1), (1, 1, 1), (0, 1, 1))
+_BOX_FACETSETS = ("left", "right", "front", "back", "bottom", "top")
+
+
+def uniform_refinement_with_maps(g):
+    """uniform_refinement(grid) together with what a grid hierarchy needs (ext/ThunderboltFerriteMultigridExt.jl: the fine → coarse cell map of its
+    nested grids): returns (fine grid, fine2coarse, (parent_ptr, parent_idx)).  fine2coarse[c] is the parent cell of fine cell c; the parents of
+    fine node v are parent_idx[parent_ptr[v]:parent_ptr[v + 1]] — itself for a kept node, 2 for an edge centre, 4 for a face centre, 8 for a cell
+    centre.  The sets travel with the grid (the reference leaves that as a TODO): cell sets go to the eight children, facet sets to the four child
+    facets ((cell, local facet), Ferrite's numbering), node sets keep their nodes and gain the new nodes all of whose parents are in the set."""
+    fine, pptr, pidx = _refine_hex(g)
+    nc = g.n_cells
+    fine2coarse = np.repeat(np.arange(nc, dtype=np.int32), 8)
+    child_of_facet = np.array([[i + 2 * j + 4 * k for (i, j, k) in (_HEX_VPOS[v] for v in f)] for f in Grid.HEX_FACETS], dtype=np.int64)   # (6, 4)
+    facetsets = dict(getattr(g, "facetsets", None) or {})
+    if g.dims is not None:
+        for name in _BOX_FACETSETS:
+            facetsets.setdefault(name, g.facetset(name))
+    fine.facetsets = {}
+    for name, fs in facetsets.items():
+        fs = np.asarray(fs, dtype=np.int64).reshape(-1, 2)
+        cells = (8 * fs[:, 0, None] + child_of_facet[fs[:, 1]]).ravel()
+        fine.facetsets[name] = np.stack([cells, np.repeat(fs[:, 1], 4)], axis=1).astype(np.int32)
+    if getattr(g, "cellsets", None):
+        fine.cellsets = {name: (8 * np.asarray(cs, dtype=np.int64)[:, None] + np.arange(8)).ravel().astype(np.int32) for name, cs in g.cellsets.items()}
+    if getattr(g, "nodesets", None):
+        fine.nodesets = {}
+        for name, ns in g.nodesets.items():
+            inset = np.zeros(g.n_nodes, dtype=bool)
+            inset[np.asarray(ns, dtype=np.int64)] = True
+            allin = np.minimum.reduceat(inset[pidx], pptr[:-1])
+            fine.nodesets[name] = np.flatnonzero(allin).astype(np.asarray(ns).dtype)
+    return fine, fine2coarse, (pptr, pidx)
+
+
+class GridHierarchy:
+    """GridHierarchy(coarse_grid, n_refinements) — the nested grids of the multigrid extension (ext/ThunderboltFerriteMultigridExt.jl), built by
+    uniform refinement of a hexahedral grid.  `.grids`: coarsest first; `.fine2coarse[r]`: parent cell of every cell of grids[r + 1];
+    `.parents[r]`: (parent_ptr, parent_idx) of the nodes of grids[r + 1] in grids[r].  Coarse nodes are a prefix of the fine nodes."""
+
+    def __init__(self, coarse_grid, n_refinements):
+        if coarse_grid.cell_kind != Hexahedron:
+            raise NotImplementedError("GridHierarchy: hexahedral grids only (there is no tetrahedral uniform_refinement)")
+        if int(n_refinements) < 1:
+            raise ValueError("GridHierarchy: at least one refinement")
+        self.grids, self.fine2coarse, self.parents = [coarse_grid], [], []
+        for _ in range(int(n_refinements)):
+            fine, f2c, par = uniform_refinement_with_maps(self.grids[-1])
+            self.grids.append(fine)
+            self.fine2coarse.append(f2c)
+            self.parents.append(par)
+
+    @property
+    def finest(self):
+        return self.grids[-1]

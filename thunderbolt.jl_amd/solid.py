@@ -823,6 +823,13 @@ class DisplacementSystem:
     def solve_increment(self, solver, res, du, inner_rtol):
         """J Δu = residual → (iterations, residual norm or None, converged).  Not converged with a residual norm: Δu is an inexact increment and
         strict_inner_solve decides; not converged without one: there is no increment and the step fails."""
+        if hasattr(solver.inner_precond, "materialize"):
+            # GMGPrecon: the hierarchy of this pattern with this problem's Dirichlet dofs; its numeric phase follows every new Jacobian (the multigrid
+            # extension rebuilds the coarse operators per solve) and stays while simplified_newton keeps the tangent
+            mg = solver.inner_precond.materialize(self.op.pattern, self.ch)
+            mg.reuse_setup = not getattr(solver, "jacobian_is_fresh", True)
+            its, lres = pcg_solve(self.op.pattern, self.op.J, res, du, inner_rtol, solver.inner_atol, solver.inner_maxiter, mg)
+            return its, lres, solve_converged(self.op.pattern, lres)
         its, lres = inner_linear_solve(solver, self.op.pattern, self.op.J, res, du, inner_rtol)
         return its, lres, lres is None or solve_converged(self.op.pattern, lres)
 
