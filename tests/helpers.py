@@ -63,3 +63,21 @@ def hex_to_tets(xyz, conn):
     flip = det < 0
     tets[flip] = tets[flip][:, [0, 2, 1, 3]]
     return np.ascontiguousarray(tets)
+
+
+def pentagon_prism_mesh(tb, layers=2):
+    """A pentagon cut into five quadrilaterals around its centre, extruded: the centre vertices of the inner layers sit in TEN hexahedra — more than the
+    eight a structured grid ever has (the record-driven gather of the element strategy holds eight cells per node and must hand such meshes to the
+    general kernel; unstructured ventricle meshes have such vertices)."""
+    ang = 2 * np.pi * np.arange(5) / 5 + 0.3
+    p2 = np.stack([np.cos(ang), np.sin(ang)], axis=1)
+    m2 = 0.5 * (p2 + np.roll(p2, -1, axis=0))                    # m[i] between p[i] and p[i+1]
+    pts2 = np.concatenate([[[0.05, -0.03]], p2, m2])             # 0: centre (slightly off), 1..5: corners, 6..10: edge midpoints
+    xyz = np.concatenate([np.column_stack([pts2 + 0.02 * k, np.full(11, 0.45 * k)]) for k in range(layers + 1)])
+    conn = []
+    for k in range(layers):
+        lo, hi = 11 * k, 11 * (k + 1)
+        for i in range(5):
+            quad = [0, 6 + (i - 1) % 5, 1 + i, 6 + i]            # centre, m[i-1], p[i], m[i]: counter-clockwise
+            conn.append([lo + q for q in quad] + [hi + q for q in quad])
+    return tb.Grid(tb.Hexahedron, np.ascontiguousarray(xyz), np.ascontiguousarray(np.array(conn, dtype=np.int32)))

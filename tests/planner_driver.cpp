@@ -358,6 +358,62 @@ static void case_colors(const Mesh &M, const char *part, const std::vector<int32
     check_colors(M, h, cells ? (int64_t)cells->size() : M.n_cells);
 }
 
+// the host planning of the tangent gather on a three-component field: node list, row check, node records.  Everything is checked against a brute-force
+// pass over cell_dofs and rowptr that shares nothing with the planner.
+static void case_gather(const Mesh &M, const char *part, bool applies)
+{
+    const int nd = M.ndpc, nb = nd / 3;
+    const std::vector<int32_t> d0 = node_list(M.view());
+    scalar(part, "n_nodes", (long long)d0.size());
+    digest(part, "node_dof0", d0);
+    std::vector<int32_t> want;
+    for (int64_t c = 0; c < M.n_cells; ++c) for (int a = 0; a < nb; ++a) want.push_back(M.cd[c * nd + 3 * a]);
+    std::sort(want.begin(), want.end());
+    want.erase(std::unique(want.begin(), want.end()), want.end());
+    CHECK(d0 == want, "%s: the node list is not the sorted set of first-component dofs", part);
+    int64_t L = -1;
+    const int rc = node_row_check(M.pattern(), d0, L);
+    scalar(part, "check_rc", rc);
+    if (rc) return;
+    scalar(part, "max_row_len", L);
+    int64_t longest = 0;
+    for (int32_t d : d0) {
+        const int64_t l = M.rowptr[d + 1] - M.rowptr[d];
+        CHECK(l % 3 == 0 && l / 3 <= 254 && M.rowptr[d + 2] - M.rowptr[d + 1] == l && M.rowptr[d + 3] - M.rowptr[d + 2] == l, "%s: rows of node dof %d passed the check", part, d);
+        longest = std::max(longest, l);
+    }
+    CHECK(L == longest, "%s: max_row_len %lld, longest node row %lld", part, (long long)L, (long long)longest);
+    PatternView pv = M.pattern();
+    pv.max_row_len = L;
+    const GatherHost h = gather_nodes(M.view(), pv, d0);
+    scalar(part, "applicable", h.applicable);
+    std::vector<std::vector<int32_t>> slots(d0.size()); // per node: cell·ND + 3a of every cell holding it, in cell order
+    for (int64_t c = 0; c < M.n_cells; ++c)
+        for (int a = 0; a < nb; ++a) slots[std::lower_bound(d0.begin(), d0.end(), M.cd[c * nd + 3 * a]) - d0.begin()].push_back((int32_t)(c * nd + 3 * a));
+    size_t most = 0;
+    for (const auto &s : slots) most = std::max(most, s.size());
+    CHECK(h.applicable == (L <= 384 && most <= 8), "%s: applicable = %d with rows of %lld and %zu cells at a node", part, (int)h.applicable, (long long)L, most);
+    CHECK(h.applicable == applies, "%s: applicable = %d", part, (int)h.applicable);
+    if (!h.applicable) { CHECK(h.recs.empty() && h.last.empty(), "%s: arrays of a plan that does not apply", part); return; }
+    digest(part, "recs", h.recs);
+    digest(part, "last", h.last);
+    CHECK(h.recs.size() == d0.size() && h.last.size() == d0.size(), "%s: one record per node", part);
+    int32_t run = 0;
+    for (size_t i = 0; i < d0.size(); ++i) {
+        const GatherNode &g = h.recs[i];
+        const int32_t d = d0[i];
+        CHECK(g.nk >= 1 && (size_t)g.nk == slots[i].size(), "%s: node %zu sits in %zu cells, nk = %d", part, i, slots[i].size(), g.nk);
+        for (int k = 0; k < 8; ++k) {
+            if (k >= g.nk) { CHECK(g.slot[k] == 0, "%s: node %zu: unused slot %d", part, i, k); continue; }
+            const int32_t s = g.slot[k];
+            CHECK(s == slots[i][k] && s % nd % 3 == 0 && M.cd[s] == d && (k == 0 || s / nd > g.slot[k - 1] / nd), "%s: node %zu: slot %d", part, i, k);
+        }
+        CHECK(g.g0 == M.rowptr[d] && g.L == M.rowptr[d + 1] - M.rowptr[d], "%s: node %zu: row pointers", part, i);
+        run = std::max(run, g.slot[g.nk - 1] / nd);
+        CHECK(h.last[i] == run, "%s: node %zu: running maximum of the last cell", part, i);
+    }
+}
+
 template <class T>
 static bool read_file(const std::string &path, std::vector<T> &v)
 {
@@ -442,6 +498,18 @@ int main(int argc, char **argv)
         run_slot_table(M, t, ell_t);
         scalar("slots", "ell_w", t.w);
         digest("slots", "ell", t.ell); digest("slots", "h_done", t.h_done); digest("slots", "ell_t", ell_t);
+    }
+    if (only.empty() || only == "gather_nodes") { // three-component fields: the host planning of the element strategy's tangent gather
+        g_case = "gather_nodes";
+        struct Field { const char *part, *mesh; int kind; bool applies; };
+        const Field fields[] = {{"q2_box", "q2_box", TB_HEX27, true},     // 3×3×2, Q2
+                                {"q1_box", "q2_scalar", TB_HEX8, true},   // 4×3×3, Q1
+                                {"prism_q1", "prism", TB_HEX8, false},    // a vertex in ten cells
+                                {"prism_q2", "prism", TB_HEX27, false}};
+        for (const Field &fd : fields) {
+            if (!load(dir, fd.mesh, fd.kind, 3, M)) return 2;
+            case_gather(M, fd.part, fd.applies);
+        }
     }
     if (only.empty() || only == "refusals") { // return codes only
         g_case = "refusals";

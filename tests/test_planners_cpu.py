@@ -1,7 +1,8 @@
 """The host planners (thunderbolt.jl_amd/csrc/tb_planners.cpp) without a GPU: tests/planner_driver.cpp, a stand-alone program linked with the planners
 and the host generators only, plans every case, checks the invariants of each plan itself and prints a digest of every plan array.  The digests are
 compared with tests/golden/plan_digests.json, recorded from the plan builders before they were split into planners and an upload tail (every array that
-reaches the device is byte for byte what it was), at 1 and at 4 OpenMP threads.  A change that alters a plan on purpose re-records the file from the
+reaches the device is byte for byte what it was; gather_nodes: from the three host functions of tb_mechanics.hip before they moved behind the same
+seam), at 1 and at 4 OpenMP threads.  A change that alters a plan on purpose re-records the file from the
 driver's output; the invariants hold either way."""
 import json
 import os
@@ -10,12 +11,12 @@ import subprocess
 import numpy as np
 import pytest
 
-from helpers import hex_to_tets
+from helpers import hex_to_tets, pentagon_prism_mesh
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "thunderbolt.jl_amd", "csrc")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "plan_digests.json")
-CASES = ["box", "box_two_blocks", "shuffled_box", "ring", "ideal_lv", "thin_wall", "tets", "long_rows", "colouring", "refusals"]
+CASES = ["box", "box_two_blocks", "shuffled_box", "ring", "ideal_lv", "thin_wall", "tets", "long_rows", "colouring", "refusals", "gather_nodes"]
 
 
 def write_meshes(tb, out):
@@ -46,7 +47,9 @@ def write_meshes(tb, out):
     g = box((3, 3, 2))
     put("q2_box", g.xyz, g.conn)
     g = box((4, 3, 3))
-    put("q2_scalar", g.xyz, g.conn)
+    put("q2_scalar", g.xyz, g.conn)  # (also the Q1 vector field of gather_nodes)
+    g = pentagon_prism_mesh(tb)  # a vertex in ten cells: the staged gather does not apply
+    put("prism", g.xyz, g.conn)
 
 
 def build_driver(exe, extra=()):

@@ -74,10 +74,9 @@ int read_status_public(tb_device *dev) { return read_status(dev); }
 int ensure_aux_stream(tb_device *dev)
 {
     if (dev->aux_stream) return TB_OK;
-    static const bool hi = [] { const char *e = tune_env("TB_MECH_CHUNK_PRIO"); return e && atoi(e); }();
     int lo_p = 0, hi_p = 0;
     TB_HIP(hipDeviceGetStreamPriorityRange(&lo_p, &hi_p));
-    TB_HIP(hipStreamCreateWithPriority(&dev->aux_stream, hipStreamNonBlocking, hi ? hi_p : lo_p));
+    TB_HIP(hipStreamCreateWithPriority(&dev->aux_stream, hipStreamNonBlocking, lo_p));
     for (hipEvent_t &e : dev->aux_ev) TB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     return TB_OK;
 }
@@ -389,7 +388,7 @@ int tb_mesh_create(tb_device *dev, int geom_kind, int64_t n_nodes, const double 
 int tb_mesh_destroy(tb_mesh *m)
 {
     if (!m) return TB_OK;
-    hipFree(m->d_xyz); hipFree(m->d_conn); hipFree(m->d_cell_dofs); hipFree(m->d_node_dof0); hipFree(m->d_cell_xyz); hipFree(m->d_rank27);
+    hipFree(m->d_xyz); hipFree(m->d_conn); hipFree(m->d_cell_dofs); hipFree(m->d_node_dof0); hipFree(m->d_cell_xyz);
     if (m->colors) hipFree(m->colors->d_cells);
     if (m->ea) { hipFree(m->ea->d_ptr); hipFree(m->ea->d_src); hipFree(m->ea->d_ea); hipFree(m->ea->d_ell); hipFree(m->ea->d_ell_t); }
     free_patch_plan(m);

@@ -1,4 +1,4 @@
-// tb_facet_geom.hpp — FacetValues of a hexahedron facet, shared by the facet kernels (k_facets in tb_mechanics.hip, k_chamber in tb_chamber.hip):
+// tb_facet_geom.hpp — FacetValues of a hexahedron facet, shared by the facet kernels (k_facets in tb_mech_facets.hip, k_chamber in tb_chamber.hip):
 // Ferrite's local facet numbering, the Gauss points on the facet, shape values / mapped gradients of the field and dΓ, n₀ of the trilinear geometry.
 #pragma once
 #include <hip/hip_runtime.h>

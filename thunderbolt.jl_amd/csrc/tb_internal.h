@@ -207,8 +207,6 @@ struct tb_mesh {
     int32_t *d_conn = nullptr;
     int32_t *d_cell_dofs = nullptr;
     int32_t *d_node_dof0 = nullptr; // vector fields: first dof of every field node
-    uint8_t *d_rank27 = nullptr;    // 27-node vector fields: rank of every node of a cell by global dof (32 bytes per cell), see tb_mechanics.hip
-    int rank27_ok = 0;              // 0 not examined, 1 built, −1 not applicable
     double *d_cell_xyz = nullptr;   // vertex coordinates per cell (nverts × 3, cell-major), built on first use by the block-per-cell kernels
     int64_t n_nodes_field = 0;
     std::vector<int32_t> h_node_dof0;
@@ -354,7 +352,7 @@ int launch_assemble_matrix(tb_form *f, tb_pattern *p, int strategy, double t, do
 int launch_assemble_vector(tb_form *f, int strategy, double t, double *d_b);
 int tabulate_diffusion_field(tb_form *f);      // first-order hexahedra: fills tb_form::d_dtab (8 points per cell) as the first assembly would
 int tabulate_diffusion_field_tet4(tb_form *f); // the same on linear tetrahedra (4 points per cell)
-// tb_mechanics.hip, tb_mech_tet.hip, tb_chamber.hip
+// tb_mechanics.hip, tb_mech_facets.hip, tb_mech_tet.hip, tb_chamber.hip
 int launch_hyperelastic(tb_form *f, tb_pattern *p, int strategy, const double *d_u, double *d_nz, double *d_r);
 int host_material_eval_form(tb_form *form, const double *F9, double *psi, double *P, double *A);
 int host_material_eval(const tb_material *mat, const double *F9, double *psi, double *P, double *A);

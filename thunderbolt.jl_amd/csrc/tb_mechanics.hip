@@ -7,17 +7,16 @@
 // The cell loop / load_element_unknowns! / assemble! belong to FerriteOperators (third party); call sites
 // src/solver/nonlinear/newton_raphson.jl:234-238, src/solver/time/homotopy.jl:61-67.
 //
-// One workgroup per cell.  The tangent is contracted in two steps, T[a][c][d][l] = Σ_k ∇Nₐ[k] 𝔸[c][k][d][l] and then
-// Kₑ[(a,c)][(b,d)] += Σ_l T[a][c][d][l] ∇N_b[l] — 27·NB² FMAs per point instead of 81·NB².
-//  * Q2 (default): the second step is a GEMM per component d, C_d[(a,c)][b] = Σ_(q,l) T_d[(a,c)][(q,l)] · ∇N[(q,l)][b]
-//    (M = 81, N = 27, K = 81), run on v_mfma_f64_16x16x4_f64: 6×2 tiles × 3 d, 21 k-steps.  The A operand (one T entry
-//    per lane) is formed in registers from 𝔸 and ∇N straight out of LDS, so T is never staged.  FP64 MFMA is not faster
-//    than FP64 vector FMAs on CDNA4 (measured 48 vs 70 TFLOP/s, scripts/microbench/mfma_f64.hip) — the point is operand
-//    reuse: the vector version needs one LDS double per 2.25 FMAs and is LDS-bandwidth-bound at ≈20 % of peak.
-//  * Q1 and the comparison build (TB_MECH_MFMA=0): thread (a, b-group) keeps 3×3 blocks in registers, T staged in LDS.
+// One workgroup per cell (k_hyperelastic).  The tangent of a cell is contracted
+//  * Q2: by sum factorisation over the tensor-product structure of the triquadratic basis and the 3×3×3 Gauss rule, with the tangent pulled
+//    back to the reference cell (comment at "B (sum factorisation)" below); on the element strategy a symmetric tangent goes through the two
+//    kernels of tb_mech_split.hip instead, the fused kernel keeps the rate-coupled (non-symmetric) one and the other strategies;
+//  * Q1: in two steps over the quadrature points, T[a][c][d][l] = Σ_k ∇Nₐ[k] 𝔸[c][k][d][l] staged in LDS and then
+//    Kₑ[(a,c)][(b,d)] += Σ_l T[a][c][d][l] ∇N_b[l] with 3×3 blocks in registers — 27·NB² FMAs per point instead of 81·NB².
+// The contractions that were built, measured and removed (matrix cores, the plain sweep for Q2, symmetric-packed storage): DESIGN.md §4.4.
+// This unit: the kernel, the pre-pass of the condensed internal variables, the dispatch.  Second pass of the element strategy:
+// tb_mech_gather.hip; weak boundary conditions: tb_mech_facets.hip.
 #include <hip/hip_runtime.h>
-
-#include <cstring>
 
 #include <algorithm>
 
@@ -26,14 +25,8 @@
 #include "tb_material.hpp"
 #include "tb_math.hpp"
 #include "tb_mech_common.hpp"
+#include "tb_mech_gather.hpp"
 #include "tb_mech_split.hpp"
-#include "tb_facet_geom.hpp"
-
-#ifdef TB_ABLATION
-#define TB_IF_ABLATION(...) __VA_ARGS__
-#else
-#define TB_IF_ABLATION(...)
-#endif
 
 namespace tb {
 using namespace tbk;
@@ -59,28 +52,20 @@ __global__ void k_build_blockpos(const int32_t *__restrict__ cell_dofs, int64_t 
     pos[tid] = (uint16_t)(lo - lo0);
 }
 
-typedef double mfma_d4 __attribute__((ext_vector_type(4)));
-#ifndef TB_KE_DMAJOR
-#define TB_KE_DMAJOR 0
-#endif
-constexpr bool KE_DMAJOR = TB_KE_DMAJOR; // stored-Kₑ row layout of the matrix-core kernel: [d][b] or [b][d]
-
 // AD: the material is any energy of tb_energy.hpp, differentiated per pair of components of F by hyper-dual evaluation (the
 // reference's Tensors.hessian path); !AD: Holzapfel–Ogden 2009 + SimpleCompressionPenalty with the hand-derived routines.
-// CT: contraction of the tangent — 0 vector FMAs over the quadrature points (Q1; comparison build), 1 matrix cores (v_mfma_f64_16x16x4,
-// symmetric tiles), 2 sum-factorised over the tensor-product structure of the triquadratic basis and the 3×3×3 Gauss rule (Q2 default)
-template <class FE, bool NEED_K, bool NEED_R, int CT, bool AD>
+template <class FE, bool NEED_K, bool NEED_R, bool AD>
 __global__ void __launch_bounds__(FE::THREADS, FE::WAVES)
 k_hyperelastic(MechMesh m, HOParams mat, EnergyParams en, const int32_t *__restrict__ list, const double *__restrict__ u, double *__restrict__ nz,
                double *__restrict__ r, const int64_t *__restrict__ rowptr, const uint16_t *__restrict__ blockpos, int atomic /*0 rmw, 1 atomic, 2 store Kₑ/rₑ*/,
-               double *__restrict__ ke, double *__restrict__ re, Status *st, const uint8_t *__restrict__ rank27 /*non-NULL: symmetric-packed Kₑ (matrix-core path)*/)
+               double *__restrict__ ke, double *__restrict__ re, Status *st)
 {
     constexpr int NB = FE::NB, NQ = FE::NQ, ND = FE::ND, PB = FE::PB, T = FE::THREADS, NG = NB / PB;
-    constexpr bool MFMA = CT == 1, SF = CT == 2;
+    constexpr bool SF = NEED_K && NB == 27; // tangent of the triquadratic field: sum-factorised contraction; otherwise the sweep over the points
     // sum-factorised tangent: the mapped gradients ∇N = ∂̂N·J⁻¹ are never formed.  ∇u = Ĥ·J⁻¹ with Ĥ[c][s] = Σₐ uₐ[c] ∂̂ₛNₐ (reference gradients from the
     // 1-D factors in registers, concurrent with the Jacobians), the tangent and the stress are pulled back to the reference cell (stage 0), and the
     // residual contracts the pulled-back stress with the reference gradients: two barriers and the 729-task gradient pass less per cell
-    constexpr bool REFGRAD = (NEED_K && SF) || (!NEED_K && NEED_R && NB == 27 && NQ == 27 && T == 256); // (the residual-only kernel of the quadratic field too)
+    constexpr bool REFGRAD = SF || (!NEED_K && NEED_R && NB == 27 && NQ == 27 && T == 256); // (the residual-only kernel of the quadratic field too)
     const MechTables<FE> &tb = g_mech_tables<FE>;
     const int64_t cell = list ? list[blockIdx.x] : m.cell0 + blockIdx.x;
     const int tid = threadIdx.x;
@@ -91,15 +76,14 @@ k_hyperelastic(MechMesh m, HOParams mat, EnergyParams en, const int32_t *__restr
 #endif
     TB_MS(0);
     __shared__ double s_ue[ND], s_x[24], s_JI[NQ][10], s_P[NQ][9];
-    // 𝔸·dΩ per point and the mapped gradients share one block: once the contraction is done it stages the symmetric-packed Kₑ for a coalesced store
+    // 𝔸·dΩ per point and the mapped gradients (sum-factorised contraction: its stage buffer Z1) share one block
     // (dynamic LDS: with the stage buffers of the sum-factorised contraction the kernel's block exceeds the 64 KB a static allocation may have)
     constexpr int AN = (NEED_K ? NQ : 1) * 81;
     extern __shared__ double s_AG[];
     double (*s_A)[81] = reinterpret_cast<double (*)[81]>(s_AG);
     double (*s_G)[NB][3] = reinterpret_cast<double (*)[NB][3]>(s_AG + AN);
-    __shared__ uint8_t s_rank[32];
     // phase A scratch (common blocks + F) and phase B's double-buffered T share one region
-    constexpr int TC_SIZE = (NEED_K && CT == 0 && 2 * NB * 27 > NQ * HOC_SIZE) ? 2 * NB * 27 : NQ * HOC_SIZE;
+    constexpr int TC_SIZE = (NEED_K && !SF && 2 * NB * 27 > NQ * HOC_SIZE) ? 2 * NB * 27 : NQ * HOC_SIZE;
     __shared__ double s_Ji[REFGRAD ? NQ : 1][9]; // J⁻¹ kept for the pull-backs of 𝔸 and P (the slots of s_JI carry F)
     __shared__ double s_TC[TC_SIZE];
     double (*s_T)[NB][27] = reinterpret_cast<double (*)[NB][27]>(s_TC);
@@ -162,7 +146,6 @@ k_hyperelastic(MechMesh m, HOParams mat, EnergyParams en, const int32_t *__restr
         s_ue[i] = u[d];
     }
     for (int i = tid; i < 24; i += T) s_x[i] = m.xyz[3 * (int64_t)m.conn[cell * 8 + i / 3] + i % 3];
-    if (NEED_K && MFMA && rank27 && tid < 32) s_rank[tid] = rank27[cell * 32 + tid];
     __syncthreads();
     TB_MS(1);
     }
@@ -185,10 +168,6 @@ k_hyperelastic(MechMesh m, HOParams mat, EnergyParams en, const int32_t *__restr
         o[6] = c02 * id; o[7] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id; o[8] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
         o[9] = det * tb.w[q];
         if (!(o[9] > 0.0)) { st->neg_detj = 1; st->cell = cell; }
-        if constexpr (NEED_K && SF) {
-#pragma unroll
-            for (int e = 0; e < 9; ++e) s_Ji[q][e] = o[e];
-        }
     }
     if constexpr (REFGRAD) {
         // A2': Ĥ[c][s] = Σₐ uₐ[c] ∂̂ₛNₐ(ξ_q), one lane per (point, c, s) — needs the element unknowns only, so it shares the phase with A1
@@ -422,125 +401,7 @@ k_hyperelastic(MechMesh m, HOParams mat, EnergyParams en, const int32_t *__restr
         }
         return acc;
     };
-    if constexpr (NEED_K && MFMA) {
-        // B (matrix cores).  Kₑ is symmetric (𝔸 has major symmetry), so of the 6×3×2 tiles (M-tile mt, component d, N-tile nt)
-        // the nine with mt ≥ 3, nt = 0 — rows (a ≥ 16, c), columns (b < 16, d): strictly below the block diagonal — are not
-        // computed; the epilogue mirrors them from the tiles (mt ≤ 2, ·, nt = 1).  27 tiles on four waves (7, 7, 7, 6):
-        //   A-operand kinds k = 3·mt + d;  k < 9: both N-tiles;  k ≥ 9: nt = 1 only
-        //   wave 0: kinds 0, 4, 8 (both) + 9      wave 1: 1, 5 (both) + 10, 11, 12
-        //   wave 2: 2, 6 (both) + 13, 14, 15      wave 3: 3, 7 (both) + 16, 17
-        // Rows ≥ ND / columns ≥ NB of the padded tiles hold finite garbage that is never stored; only the K padding
-        // (kk ≥ 3·NQ) must vanish, which the B operand does.
-        static_assert(T == 256 && ND == 81 && NB == 27, "tile assignment below is for 6×2×3 tiles on four waves");
-        constexpr int KS = (3 * NQ + 3) / 4;
-        const int lane = tid & 63, wv = tid >> 6, lr = lane & 15, g = lane >> 4;
-        // entries: e0, e1 → both N-tiles; e2, e3 → nt = 1; e4 → nt = 1 (waves 1, 2);  wave 0 additionally runs e2 on nt = 0
-        int kind[5];
-        kind[0] = wv; kind[1] = wv + 4;
-        kind[2] = wv == 0 ? 8 : wv == 1 ? 10 : wv == 2 ? 13 : 16;
-        kind[3] = wv == 0 ? 9 : wv == 1 ? 11 : wv == 2 ? 14 : 17;
-        kind[4] = wv == 1 ? 12 : wv == 2 ? 15 : 17; // unused on waves 0 and 3
-        const bool has_e4 = wv == 1 || wv == 2, e2_both = wv == 0;
-        int offG[5], offA[5];
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            const int mt = kind[i] / 3, d = kind[i] % 3;
-            const int R = 16 * mt + lr, Rc = R < ND ? R : 0;
-            offG[i] = 3 * (Rc / 3);
-            offA[i] = 27 * (Rc % 3) + 3 * d;
-        }
-        const int b1 = 16 + lr < NB ? 16 + lr : 0;
-        mfma_d4 acc[7];
-#pragma unroll
-        for (int i = 0; i < 7; ++i) acc[i] = mfma_d4{0, 0, 0, 0};
-        const double *sG = &s_G[0][0][0], *sA = &s_A[0][0];
-#pragma unroll 3
-        for (int s = 0; s < KS; ++s) {
-            const int kk = 4 * s + g;
-            const bool kv = kk < 3 * NQ;
-            const int kc = kv ? kk : 0, q = kc / 3, l = kc - 3 * q;
-            const double *gq = sG + q * (NB * 3), *aq = sA + q * 81 + l;
-            double B0 = gq[3 * lr + l], B1 = gq[3 * b1 + l];
-            if (!kv) { B0 = 0.0; B1 = 0.0; }
-            double Aop[5];
-#pragma unroll
-            for (int i = 0; i < 5; ++i) {
-                const double *gg = gq + offG[i], *aa = aq + offA[i];
-                Aop[i] = gg[0] * aa[0] + gg[1] * aa[9] + gg[2] * aa[18];
-            }
-            acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(Aop[0], B0, acc[0], 0, 0, 0);
-            acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(Aop[0], B1, acc[1], 0, 0, 0);
-            acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(Aop[1], B0, acc[2], 0, 0, 0);
-            acc[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(Aop[1], B1, acc[3], 0, 0, 0);
-            acc[4] = __builtin_amdgcn_mfma_f64_16x16x4f64(Aop[2], B1, acc[4], 0, 0, 0);
-            acc[5] = __builtin_amdgcn_mfma_f64_16x16x4f64(Aop[3], B1, acc[5], 0, 0, 0);
-            if (e2_both) acc[6] = __builtin_amdgcn_mfma_f64_16x16x4f64(Aop[2], B0, acc[6], 0, 0, 0);
-            else if (has_e4) acc[6] = __builtin_amdgcn_mfma_f64_16x16x4f64(Aop[4], B1, acc[6], 0, 0, 0);
-        }
-        if constexpr (NEED_R) {
-            if (tid < ND) {
-                for (int q = 0; q < NQ; ++q) {
-                    const double *gr = s_G[q][tid / 3];
-                    const double *p = s_P[q] + 3 * (tid % 3);
-                    racc += gr[0] * p[0] + gr[1] * p[1] + gr[2] * p[2];
-                }
-            }
-        }
-        // C: D[row = g + 4·reg][col = lr] of tile (mt, d, nt) is Kₑ[(a,c) = 16·mt + row][(b,d), b = 16·nt + col]; tiles
-        // (mt ≤ 2, nt = 1) also supply the mirrored entries Kₑ[(b,d)][(a,c)] of the tiles that were skipped
-        auto put = [&](int R, int b, int d, double v) { // Kₑ[R][(b,d)]
-            if (atomic == 2) { // element assembly: the stored Kₑ row
-                ke[((int64_t)cell * ND + R) * ND + (KE_DMAJOR ? d * NB + b : 3 * b + d)] = v;
-            } else {
-                const int a = R / 3, c = R - 3 * a;
-                const int64_t k = rowptr[s_dof[3 * a] + c] + blockpos[cell * (NB * NB) + a * NB + b] + d;
-                if (atomic) unsafeAtomicAdd(nz + k, v); else nz[k] += v;
-            }
-        };
-        // Symmetric-packed element matrix (rank27 given): the cell's nodes are ranked by their global dof, a 3×3 node block (a, b) is stored once, at
-        // symblk(min rank, max rank), as [c][d] seen from the node of smaller rank — so the gather of a node reads, per cell, ONE contiguous run
-        // (its blocks with all nodes of higher dof) and mirrors them into the rows of those nodes.  Half the bytes of the stored 81 × 81 matrix.
-        // Entries go to the LDS block the operands lived in and leave as one coalesced 27 KB stream.
-        auto put_sym = [&](int R, int b, int d, double v) {
-            const int a = R / 3, c = R - 3 * a;
-            const int ra = s_rank[a], rb = s_rank[b];
-            int slot;
-            if (a == b) slot = symblk(ra, ra) * 9 + 3 * c + d;
-            else {
-                // the entry and its transpose share a slot; the transpose is not computed when it lies in a skipped tile (row ≥ 48, column < 16)
-                const bool partner_computed = !(b >= 16 && a < 16);
-                if (partner_computed && ra > rb) return;
-                slot = ra < rb ? symblk(ra, rb) * 9 + 3 * c + d : symblk(rb, ra) * 9 + 3 * d + c;
-            }
-            s_AG[slot] = v;
-        };
-        const bool sym = atomic == 2 && rank27 != nullptr;
-        auto emit = [&](const mfma_d4 &v, int knd, int nt) {
-            const int mt = knd / 3, d = knd % 3, b = 16 * nt + lr;
-            if (b >= NB) return;
-#pragma unroll
-            for (int rg = 0; rg < 4; ++rg) {
-                const int R = 16 * mt + g + 4 * rg;
-                if (R >= ND) continue;
-                if (sym) { put_sym(R, b, d, v[rg]); continue; }
-                put(R, b, d, v[rg]);
-                if (nt == 1 && mt <= 2) put(3 * b + d, R / 3, R % 3, v[rg]); // transpose: row (b,d), column (a,c) = R
-            }
-        };
-        if (sym) __syncthreads(); // every wave is done reading 𝔸 and ∇N (contraction, residual)
-        emit(acc[0], kind[0], 0); emit(acc[1], kind[0], 1);
-        emit(acc[2], kind[1], 0); emit(acc[3], kind[1], 1);
-        emit(acc[4], kind[2], 1); emit(acc[5], kind[3], 1);
-        if (e2_both) emit(acc[6], kind[2], 0);
-        else if (has_e4) emit(acc[6], kind[4], 1);
-        if (sym) {
-            __syncthreads();
-            static_assert(KE_SYM % 2 == 0 && KE_SYM <= AN + NQ * NB * 3, "staging block");
-            double2 *dst = reinterpret_cast<double2 *>(ke + (int64_t)cell * KE_SYM);
-            const double2 *src = reinterpret_cast<const double2 *>(s_AG);
-            for (int i = tid; i < KE_SYM / 2; i += T) dst[i] = src[i];
-        }
-    } else if constexpr (NEED_K && SF) {
+    if constexpr (SF) {
         // B (sum factorisation).  Kₑ[(a,c)][(b,d)] = Σ_q Σ_su ∂̂ₛNₐ(ξ_q) Â_q[c][s][d][u] ∂̂ᵤN_b(ξ_q) with the tangent pulled back to the reference cell,
         // Â_q[c][s][d][u] = Σ_kl J⁻¹[s][k] 𝔸_q[c][k][d][l] J⁻¹[u][l] dΩ.  Basis and Gauss rule are tensor products — node a ↔ (a₀,a₁,a₂), point
         // q ↔ (q₀,q₁,q₂), ∂̂ₛNₐ(ξ_q) = Π_dim ψ(dim == s)_{a_dim}(q_dim), ψ(false) = φ, ψ(true) = φ′ — so the sum over q is three one-dimensional
@@ -769,329 +630,6 @@ k_hyperelastic(MechMesh m, HOParams mat, EnergyParams en, const int32_t *__restr
 }
 
 
-// ElementAssemblyStrategy for the tangent: second pass, one wave per node.  A lane owns *positions* of the node's three
-// CSR rows, not source entries: per cell touching the node a byte map "neighbour-node slot of the row → local node b" is
-// built in LDS from blockpos (27 byte stores), then every lane sums its entry over the ≤8 element matrices in cell order —
-// independent loads, all in flight together, no accumulator in LDS, each nz stored once (bit-reproducible like the
-// reference's EA strategy).  DMAJOR: row layout of the stored Kₑ is [d][b] instead of [b][d].
-template <int NB, bool DMAJOR, int NK, bool TL = false>
-__device__ __forceinline__ void gather_rows(const double *const (&rowk)[8], const uint8_t *inv, int nbr_max, int L, int lane, double *dst0, bool first)
-{
-    // the three rows of the node share the position → local-node lookup: one pass over the positions with the 3·NK loads of a position in flight
-    // together (constant offsets c·ND from one address), instead of three passes of NK loads each
-    constexpr int ND = 3 * NB;
-    for (int p = lane; p < L; p += 64) {
-        const int nbr = p / 3, d = p - 3 * nbr;
-        double v[3][NK];
-        bool ok[NK];
-#pragma unroll
-        for (int k = 0; k < NK; ++k) {
-            const int b = inv[k * nbr_max + nbr];
-            ok[k] = b != 0xFF;
-            const int bb = ok[k] ? b : 0;
-            const double *src = rowk[k] + (TL ? bb + 9 * d : DMAJOR ? d * NB + bb : 3 * bb + d); // TL: the map holds cb(b) (tensor-order columns)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) v[c][k] = src[c * ND];
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            double sum = 0.0;
-#pragma unroll
-            for (int k = 0; k < NK; ++k) sum += ok[k] ? v[c][k] : 0.0;
-            double *dst = dst0 + (int64_t)c * L;
-            if (first) dst[p] = sum; else dst[p] += sum;
-        }
-    }
-}
-
-template <int NB, bool DMAJOR, bool TL = false>
-__global__ void __launch_bounds__(256)
-k_gather_node_rows(const int32_t *__restrict__ node_dof0, int64_t n_nodes, const int64_t *__restrict__ ea_ptr, const int32_t *__restrict__ ea_src,
-                   const double *__restrict__ ke, const uint16_t *__restrict__ blockpos, const int64_t *__restrict__ rowptr, double *__restrict__ nz,
-                   int nbr_max)
-{
-    constexpr int ND = 3 * NB, KC = 8;
-    extern __shared__ uint8_t s_inv[];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t node = (int64_t)blockIdx.x * (blockDim.x >> 6) + wv;
-    if (node >= n_nodes) return;
-    uint8_t *inv = s_inv + (size_t)wv * KC * nbr_max;
-    const int32_t dof0 = node_dof0[node];
-    const int64_t g0 = rowptr[dof0];
-    const int L = (int)(rowptr[dof0 + 1] - g0); // rows dof0, dof0+1, dof0+2 are consecutive runs of equal length (checked on the host)
-    const int64_t k0 = ea_ptr[dof0], k1 = ea_ptr[dof0 + 1];
-    for (int64_t kb = k0; kb < k1; kb += KC) {
-        const int nk = (int)(k1 - kb < KC ? k1 - kb : KC);
-        const int nkp = nk <= 2 ? nk : nk <= 4 ? 4 : 8; // padded slots repeat cell 0 with an all-0xFF map: contribute nothing
-        for (int i = lane; i < nkp * nbr_max / 4; i += 64) reinterpret_cast<uint32_t *>(inv)[i] = 0xFFFFFFFFu;
-        __builtin_amdgcn_wave_barrier();
-        for (int i = lane; i < nk * NB; i += 64) {
-            const int k = i / NB, b = i - k * NB;
-            const int32_t slot = ea_src[kb + k];
-            const int64_t cell = slot / ND;
-            const int a = (slot % ND) / 3;
-            inv[k * nbr_max + blockpos[cell * (NB * NB) + a * NB + b] / 3] = (uint8_t)(TL ? cb27(b) : b);
-        }
-        __builtin_amdgcn_wave_barrier();
-        const double *rowk[8];
-#pragma unroll
-        for (int k = 0; k < KC; ++k) {
-            const int32_t slot = ea_src[kb + (k < nk ? k : 0)];
-            rowk[k] = ke + ((int64_t)(slot / ND) * ND + 3 * (TL ? tix27((slot % ND) / 3) : (slot % ND) / 3)) * ND;
-        }
-        const bool first = kb == k0;
-        if (nkp == 1) gather_rows<NB, DMAJOR, 1, TL>(rowk, inv, nbr_max, L, lane, nz + g0, first);
-        else if (nkp == 2) gather_rows<NB, DMAJOR, 2, TL>(rowk, inv, nbr_max, L, lane, nz + g0, first);
-        else if (nkp == 4) gather_rows<NB, DMAJOR, 4, TL>(rowk, inv, nbr_max, L, lane, nz + g0, first);
-        else gather_rows<NB, DMAJOR, 8, TL>(rowk, inv, nbr_max, L, lane, nz + g0, first);
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-// The same gather with the source rows staged through LDS and the per-node metadata in one record (default when a node's rows hold ≤ 384 positions
-// and no node sits in more than 8 cells).  The kernel above is bound by its chain of dependent trips (dof → row pointers and slot range → slots →
-// block positions → data, then one trip per 64 positions of each row): ≈ 19 µs per node with 24 waves per CU.  Here a wave reads ONE 48-byte record,
-// then — in the same trip — the block positions of its cells and the cells' runs themselves (a node's share of an element matrix is one contiguous run,
-// rows 3a..3a+2 of Kₑ: 3·ND doubles, read coalesced, every line once), parks both in LDS and sums from LDS into registers: a lane owns positions
-// lane + 64·i of the three rows, contributions added in cell order (bit-reproducible); every nz stored once, coalesced.
-struct GatherNode {
-    int64_t g0;      // first nz of row dof0 (rows dof0+1, dof0+2 follow, L entries each)
-    int32_t L, nk;   // row length, number of cells at the node
-    int32_t slot[8]; // cell·ND + 3a: row offset of the node's run in the stored element matrices, cell-ordered
-};
-
-// LAYOUT of the stored element matrices: 0 rows / columns in Ferrite order, 1 tensor order (tb_mech_common.hpp), 2 symmetric-packed by rank (round 5): the
-// 378 node blocks (i ≤ j by the rank of the nodes' dofs within the cell) of 9 doubles, block (i, j) as [c][d] seen from node i — half the bytes written by
-// the contraction kernel.  A node A of rank r then finds its blocks with the nodes of higher rank in ONE contiguous run and those with the r nodes of
-// lower rank as r transposed 72-byte blocks (pulled, not mirrored: the round-3 variant WROTE the mirror pieces into other rows — partial lines — and lost);
-// either way 243 doubles per (node, cell) are staged, addressed by the neighbour's rank.
-template <int NB, int KC, int LAYOUT = 0>
-__global__ void __launch_bounds__(256, KC == 4 ? 4 : 2)
-k_gather_node_rows_lds(const GatherNode *__restrict__ gn, int64_t n_nodes, const double *__restrict__ ke, const uint16_t *__restrict__ blockpos,
-                       double *__restrict__ nz, int nbr_pad, const uint8_t *__restrict__ rank27)
-{
-    constexpr bool TL = LAYOUT == 1, SYM = LAYOUT == 2;
-    constexpr int ND = 3 * NB, RUN = 3 * ND, NJ = (RUN + 63) / 64, NI = 6;
-    extern __shared__ double s_stage[];
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t node = (int64_t)blockIdx.x * 4 + wv;
-    if (node >= n_nodes) return; // no workgroup barrier below: waves are independent
-    double *buf = s_stage + (size_t)wv * (KC * RUN + KC * nbr_pad / 8);
-    uint8_t *inv = reinterpret_cast<uint8_t *>(buf + KC * RUN);
-    const GatherNode rec = gn[node];
-    const int L = rec.L;
-    double acc[NI][3];
-#pragma unroll
-    for (int i = 0; i < NI; ++i) acc[i][0] = acc[i][1] = acc[i][2] = 0.0;
-#pragma unroll
-    for (int kb = 0; kb < 8; kb += KC) {
-        if (kb >= rec.nk) break;
-        const int nk = rec.nk - kb < KC ? rec.nk - kb : KC;
-        double r[KC][NJ];
-        int rA[KC]; // SYM: rank of this node in cell k (wave-uniform)
-#pragma unroll
-        for (int k = 0; k < KC; ++k) {
-            rA[k] = 0;
-            if (k < nk) {
-                int64_t row0 = rec.slot[kb + k]; // cell·ND + 3a
-                if constexpr (SYM) {
-                    const int64_t cellk = row0 / ND;
-                    const int ra = rank27[cellk * 32 + (int)(row0 - cellk * ND) / 3];
-                    rA[k] = ra;
-                    const double *src = ke + cellk * KE_SYM;
-                    const int diag = symblk(ra, ra);
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) {
-                        const int idx = lane + 64 * j, rb = idx / 9, e = idx - 9 * rb;
-                        const int blk = rb >= ra ? diag + (rb - ra) : symblk(rb, ra);
-                        r[k][j] = idx < RUN ? src[blk * 9 + e] : 0.0;
-                    }
-                } else {
-                if constexpr (TL) { const int64_t cellk = row0 / ND; row0 = cellk * ND + 3 * tix27((int)(row0 - cellk * ND) / 3); }
-                const double *src = ke + row0 * ND;
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) { const int idx = lane + 64 * j; r[k][j] = idx < RUN ? src[idx] : 0.0; }
-                }
-            }
-        }
-        for (int i = lane; i < nk * nbr_pad / 4; i += 64) reinterpret_cast<uint32_t *>(inv)[i] = 0xFFFFFFFFu;
-        __builtin_amdgcn_wave_barrier();
-        for (int i = lane; i < nk * NB; i += 64) {
-            const int k = i / NB, b = i - k * NB;
-            int32_t slot = rec.slot[kb];
-#pragma unroll
-            for (int kk = 1; kk < KC; ++kk) slot = k == kk ? rec.slot[kb + kk] : slot;
-            const int64_t cell = slot / ND;
-            const int a = (slot - (int32_t)cell * ND) / 3;
-            inv[k * nbr_pad + blockpos[cell * (NB * NB) + a * NB + b] / 3] = (uint8_t)(SYM ? rank27[cell * 32 + b] : TL ? cb27(b) : b);
-        }
-#pragma unroll
-        for (int k = 0; k < KC; ++k)
-            if (k < nk) {
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) { const int idx = lane + 64 * j; if (idx < RUN) buf[k * RUN + idx] = r[k][j]; }
-            }
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const int p = lane + 64 * i;
-            if (p < L) {
-                const int nbr = p / 3, d = p - 3 * nbr;
-#pragma unroll
-                for (int k = 0; k < KC; ++k)
-                    if (k < nk) {
-                        const int b = inv[k * nbr_pad + nbr];
-                        if (b != 0xFF) {
-                            if constexpr (SYM) { // b = the neighbour's rank: block staged at b·9, as [c][d] from this node when b ≥ its rank, transposed otherwise
-                                const bool up = b >= rA[k];
-                                const double *sv = buf + k * RUN + 9 * b + (up ? d : 3 * d);
-                                const int st = up ? 3 : 1;
-                                acc[i][0] += sv[0];
-                                acc[i][1] += sv[st];
-                                acc[i][2] += sv[2 * st];
-                            } else {
-                            const double *sv = buf + k * RUN + (TL ? b + 9 * d : 3 * b + d);
-                            acc[i][0] += sv[0];
-                            acc[i][1] += sv[ND];
-                            acc[i][2] += sv[2 * ND];
-                            }
-                        }
-                    }
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        const int p = lane + 64 * i;
-        if (p < L) {
-            nz[rec.g0 + p] = acc[i][0];
-            nz[rec.g0 + L + p] = acc[i][1];
-            nz[rec.g0 + 2 * (int64_t)L + p] = acc[i][2];
-        }
-    }
-}
-
-// Gather of the symmetric-packed element matrices (matrix-core path): one wave per node A.  Per cell around A the wave reads ONE contiguous run —
-// the 3×3 blocks of A with every node of higher dof in that cell — sums the runs of its ≤ KC cells in cell order (bit-reproducible), stores the upper
-// part of A's three rows coalesced, and mirrors every block into the rows of the other node B (rows (B,d), columns (A,0..2): 24-byte pieces; nine lanes
-// hold one block, so a store instruction covers 21 pieces).  Every stored byte is read once and every nz written once: 14 + 14 + 19 GB at 80³ instead of
-// 27 + 27 + 19.  Workgroups are dealt to the XCDs in contiguous chunks of nodes, so that the pieces of one cache line of a row — written by the waves
-// of dof-consecutive nodes — meet in one L2.
-template <int NB>
-__global__ void __launch_bounds__(256)
-k_gather_node_rows_sym(const int32_t *__restrict__ node_dof0, int64_t n_nodes, const int64_t *__restrict__ ea_ptr, const int32_t *__restrict__ ea_src,
-                       const double *__restrict__ ke, const uint16_t *__restrict__ blockpos, const uint8_t *__restrict__ rank27,
-                       const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, double *__restrict__ nz, int nbr_max, int64_t ngroups)
-{
-    constexpr int ND = 3 * NB, KC = 16, CH = 21; // CH neighbours × 3 components = 63 lanes per chunk
-    extern __shared__ uint8_t s_raw[];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t chunkg = (ngroups + 7) >> 3;
-    const int64_t grp = (int64_t)(blockIdx.x & 7) * chunkg + (blockIdx.x >> 3);
-    if (grp >= ngroups) return;
-    const int64_t node = grp * 4 + wv;
-    if (node >= n_nodes) return;
-    // per-wave LDS: inv[KC][nbr_max] bytes | posAB[nbr_max] u16 | meta[KC] (cell, a, rank) | vals[63 × 3] doubles | tgt[63] int64
-    const size_t per_wave = (size_t)KC * nbr_max + 2 * (size_t)nbr_max + 16 * KC + 63 * 3 * 8 + 64 * 8;
-    uint8_t *base = s_raw + (size_t)wv * ((per_wave + 15) & ~(size_t)15);
-    int32_t *meta = reinterpret_cast<int32_t *>(base);                       // [KC][4]: cell, a, rank of A, unused
-    double *vals = reinterpret_cast<double *>(base + 16 * KC);
-    long long *tgt = reinterpret_cast<long long *>(base + 16 * KC + 63 * 3 * 8);
-    uint16_t *posAB = reinterpret_cast<uint16_t *>(base + 16 * KC + 63 * 3 * 8 + 64 * 8);
-    uint8_t *inv = base + 16 * KC + 63 * 3 * 8 + 64 * 8 + 2 * (size_t)nbr_max;
-
-    const int32_t dof0 = node_dof0[node];
-    const int64_t g0 = rowptr[dof0];
-    const int L = (int)(rowptr[dof0 + 1] - g0); // rows dof0, dof0+1, dof0+2 are consecutive runs of equal length (checked on the host)
-    const int nn = L / 3;
-    const int64_t k0 = ea_ptr[dof0];
-    const int nk = (int)(ea_ptr[dof0 + 1] - k0); // ≤ KC (checked on the host)
-    if (lane < nk) {
-        const int32_t slot = ea_src[k0 + lane];
-        const int32_t cell = slot / ND, a = (slot % ND) / 3;
-        meta[4 * lane] = cell; meta[4 * lane + 1] = a; meta[4 * lane + 2] = rank27[(int64_t)cell * 32 + a];
-    }
-    for (int i = lane; i < (KC * nbr_max) / 4; i += 64) reinterpret_cast<uint32_t *>(inv)[i] = 0xFFFFFFFFu;
-    __builtin_amdgcn_wave_barrier();
-    const int selfpos = blockpos[(int64_t)meta[0] * (NB * NB) + meta[1] * NB + meta[1]] / 3;
-    const int nu = nn - selfpos; // A itself and its neighbours of higher dof
-    for (int i = lane; i < nk * NB; i += 64) {
-        const int k = i / NB, b = i - k * NB;
-        const int64_t cell = meta[4 * k];
-        const int a = meta[4 * k + 1], ra = meta[4 * k + 2];
-        const int rb = rank27[cell * 32 + b];
-        if (rb >= ra) {
-            const int n = blockpos[cell * (NB * NB) + a * NB + b] / 3 - selfpos;
-            inv[k * nbr_max + n] = (uint8_t)(rb - ra);
-            posAB[n] = blockpos[cell * (NB * NB) + b * NB + a]; // position of column (A,0) in the rows of B: the same from every cell holding both
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-
-    const int ln = lane / 3, d = lane - 3 * ln; // lane 63 idles
-    for (int nc0 = 0; nc0 < nu; nc0 += CH) {
-        const int n = nc0 + ln;
-        const bool valid = lane < 63 && n < nu;
-        // mirror target of this (neighbour, component): row (B, d), column (A, 0) — two dependent loads, issued before the element-matrix reads
-        long long t = -1;
-        if (valid && n > 0) {
-            const int32_t dofB = colidx[g0 + 3 * (selfpos + n)];
-            t = rowptr[dofB + d] + posAB[n];
-        }
-        double sum[3] = {0.0, 0.0, 0.0};
-        for (int kb = 0; kb < nk; kb += 8) {
-            double v[8][3];
-            bool ok[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int kk = kb + k < nk ? kb + k : kb;
-                const int rel = valid ? inv[kk * nbr_max + n] : 0xFF;
-                ok[k] = kb + k < nk && rel != 0xFF;
-                const int ra = meta[4 * kk + 2];
-                const double *src = ke + (int64_t)meta[4 * kk] * KE_SYM + (symblk(ra, ra) + (ok[k] ? rel : 0)) * 9 + d;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) v[k][c] = ok[k] ? src[3 * c] : 0.0;
-            }
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) sum[c] += v[k][c];
-        }
-        if (valid) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) nz[g0 + (int64_t)c * L + 3 * (selfpos + n) + d] = sum[c];
-        }
-        // mirror: the block of (A, B) transposed into rows (B, d); nine consecutive lanes-slots hold one block, three consecutive ones one 24-byte piece
-        if (lane < 63) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) vals[3 * lane + c] = sum[c];
-            tgt[lane] = t;
-        }
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int r_ = 0; r_ < 3; ++r_) {
-            const int q = 64 * r_ + lane;
-            if (q < 189) {
-                const long long tt = tgt[q / 3];
-                if (tt >= 0) nz[tt + (q % 3)] = vals[q];
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-// element residuals → global residual: r[d] = Σ (in cell order) rₑ slots of dof d
-__global__ void k_gather_residual(const int64_t *__restrict__ ptr, const int32_t *__restrict__ src, const double *__restrict__ re, int64_t ndofs,
-                                  double *__restrict__ r)
-{
-    const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (d >= ndofs) return;
-    double s = 0.0;
-    for (int64_t k = ptr[d]; k < ptr[d + 1]; ++k) s += re[src[k]];
-    r[d] = s;
-}
-
 // ------------------------------------------------------------------------------------------------ host side
 HOParams make_params(const tb_form *f)
 {
@@ -1161,101 +699,6 @@ int host_material_eval_form(tb_form *form, const double *F9, double *psi, double
     return TB_OK;
 }
 
-// first-component dof of every node of the vector field (rows of a node are dof0, dof0+1, dof0+2)
-static int build_node_list(tb_mesh *m)
-{
-    std::vector<int32_t> d0;
-    d0.reserve((size_t)m->ndofs / 3);
-    std::vector<uint8_t> seen(m->ndofs, 0);
-    for (int64_t i = 0; i < m->n_cells * m->nb; ++i) {
-        const int32_t d = m->h_cell_dofs[3 * i];
-        if (!seen[d]) { seen[d] = 1; d0.push_back(d); }
-    }
-    std::sort(d0.begin(), d0.end());
-    m->n_nodes_field = (int64_t)d0.size();
-    m->h_node_dof0 = d0;
-    return upload(m->dev, d0, &m->d_node_dof0);
-}
-
-// the gather kernel relies on the three rows of a node being equal-length runs of whole nodes
-static int check_node_rows(tb_pattern *p)
-{
-    if (p->max_row_len) return TB_OK;
-    const tb_mesh *m = p->mesh;
-    for (int32_t d : m->h_node_dof0) {
-        const int64_t L = p->h_rowptr[d + 1] - p->h_rowptr[d];
-        if (L % 3 || L != p->h_rowptr[d + 2] - p->h_rowptr[d + 1] || L != p->h_rowptr[d + 3] - p->h_rowptr[d + 2] || L / 3 > 254) {
-            set_error("element assembly gather: rows of node dof %d are not three equal runs of whole nodes (L = %lld)", d, (long long)L);
-            return TB_ERR_PATTERN;
-        }
-        p->max_row_len = std::max<int64_t>(p->max_row_len, L);
-    }
-    return TB_OK;
-}
-
-// node records of the staged gather (GatherNode): built once per pattern from the host dof table, cells in ascending order like the slot lists
-static int ensure_gather_nodes(tb_pattern *p)
-{
-    if (p->gnodes_state) return TB_OK;
-    TB_NO_CAPTURE(p->mesh->dev);
-    const tb_mesh *m = p->mesh;
-    const int nb = m->nb, nd = 3 * nb;
-    const int64_t nn = m->n_nodes_field;
-    if (p->max_row_len > 384 || m->n_cells * (int64_t)nd >= (int64_t)0x7fffffff) { p->gnodes_state = -1; return TB_OK; }
-    std::vector<int32_t> node_of((size_t)m->ndofs, -1);
-    for (int64_t i = 0; i < nn; ++i) node_of[m->h_node_dof0[i]] = (int32_t)i;
-    std::vector<GatherNode> recs((size_t)nn);
-    for (int64_t i = 0; i < nn; ++i) {
-        const int32_t d = m->h_node_dof0[i];
-        recs[i].g0 = p->h_rowptr[d];
-        recs[i].L = (int32_t)(p->h_rowptr[d + 1] - p->h_rowptr[d]);
-        recs[i].nk = 0;
-        for (int k = 0; k < 8; ++k) recs[i].slot[k] = 0;
-    }
-    for (int64_t c = 0; c < m->n_cells; ++c)
-        for (int a = 0; a < nb; ++a) {
-            GatherNode &g = recs[node_of[m->h_cell_dofs[c * nd + 3 * a]]];
-            if (g.nk >= 8) { p->gnodes_state = -1; return TB_OK; }
-            g.slot[g.nk++] = (int32_t)(c * nd + 3 * a);
-        }
-    // running maximum of the last contributing cell over the records (dof order): the records before the first one whose value reaches c are complete
-    // once cells [0, c) are integrated — the prefix the chunked linearisation gathers behind the integration front.  On a mesh numbered cell by cell
-    // the prefix trails the front by about one layer of cells.
-    p->h_gn_last.resize((size_t)nn);
-    int32_t run = 0;
-    for (int64_t i = 0; i < nn; ++i) { run = std::max(run, recs[i].slot[recs[i].nk - 1] / nd); p->h_gn_last[i] = run; }
-    TB_HIP(hipMalloc(&p->d_gnodes, sizeof(GatherNode) * (size_t)nn));
-    TB_HIP(hipMemcpy(p->d_gnodes, recs.data(), sizeof(GatherNode) * (size_t)nn, hipMemcpyHostToDevice));
-    p->gnodes_state = 1;
-    return TB_OK;
-}
-
-// Per cell: rank of every field node among the cell's nodes by global dof (27 bytes, padded to 32) — the order in which the symmetric-packed
-// element matrix stores its node blocks.  rank27_ok < 0: some node sits in more than 16 cells (the mirroring gather keeps 16 cell maps per wave).
-static int ensure_rank27(tb_mesh *m)
-{
-    if (m->rank27_ok) return TB_OK;
-    const int nb = m->nb;
-    if (nb != 27) { m->rank27_ok = -1; return TB_OK; }
-    std::vector<uint8_t> rk((size_t)m->n_cells * 32, 0);
-    std::vector<uint8_t> cnt((size_t)m->ndofs, 0);
-    bool ok = true;
-#pragma omp parallel for schedule(static)
-    for (int64_t c = 0; c < m->n_cells; ++c) {
-        const int32_t *d = &m->h_cell_dofs[c * 3 * nb];
-        for (int a = 0; a < nb; ++a) {
-            int r = 0;
-            for (int b = 0; b < nb; ++b) r += d[3 * b] < d[3 * a];
-            rk[(size_t)c * 32 + a] = (uint8_t)r;
-        }
-    }
-    for (int64_t i = 0; i < m->n_cells * nb; ++i) { uint8_t &k = cnt[m->h_cell_dofs[3 * i]]; if (k == 255 || ++k > 16) ok = false; }
-    if (!ok) { m->rank27_ok = -1; return TB_OK; }
-    int rc = upload(m->dev, rk, &m->d_rank27);
-    if (rc) return rc;
-    m->rank27_ok = 1;
-    return TB_OK;
-}
 
 int ensure_blockpos(tb_pattern *p)
 {
@@ -1269,258 +712,232 @@ int ensure_blockpos(tb_pattern *p)
     return TB_OK;
 }
 
-template <class FE, bool NEED_K, bool NEED_R, int CT, bool AD>
-static int run(tb_form *f, tb_pattern *p, int strategy, const double *d_u, double *d_nz, double *d_r)
+// ---- dispatch: one assembly call = the arguments below, handed to one of the three strategies
+struct MechCall {
+    tb_form *f;
+    tb_pattern *p; // NULL when only the residual is asked for
+    const double *d_u;
+    double *d_nz, *d_r;
+    MechMesh mm;
+    HOParams hp;
+    EnergyParams ep;
+};
+
+// residual-only kernel of the triquadratic field: reference-gradient path, no block of mapped gradients
+template <class FE, bool NEED_K, bool NEED_R> constexpr bool refgrad_r = !NEED_K && NEED_R && FE::NB == 27 && FE::NQ == 27 && FE::THREADS == 256;
+
+// cells list[0..n), or [cell0, cell0 + n) without a list, through k_hyperelastic
+template <class FE, bool NEED_K, bool NEED_R, bool AD>
+static int launch_cells(const MechCall &c, const int32_t *list, int64_t cell0, int64_t n, int atomic, double *kebuf = nullptr, double *rebuf = nullptr)
 {
-    constexpr bool MFMA = CT == 1;
+    if (!n) return TB_OK;
+    constexpr size_t dyn_lds = sizeof(double) * ((NEED_K ? FE::NQ : 1) * 81 + (refgrad_r<FE, NEED_K, NEED_R> ? 0 : FE::NQ * FE::NB * 3)); // 𝔸·dΩ + mapped gradients (s_AG)
+    tb_device *dev = c.f->mesh->dev;
+    MechMesh mm = c.mm;
+    mm.cell0 = cell0;
+    auto kern = k_hyperelastic<FE, NEED_K, NEED_R, AD>;
+    TB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)n), dim3(FE::THREADS), dyn_lds, dev->stream, mm, c.hp, c.ep, list, c.d_u, c.d_nz, c.d_r,
+                       c.p ? c.p->d_rowptr : nullptr, c.p ? c.p->d_blockpos : nullptr, atomic, kebuf, rebuf, dev->d_status);
+    TB_HIP(hipGetLastError());
+    return TB_OK;
+}
+
+// a per-pattern device buffer of at least `need` bytes: kept, or freed and allocated anew
+static int ensure_buffer(double *&d_buf, size_t &have, size_t need, const char *what)
+{
+    if (d_buf && have < need) { (void)hipFree(d_buf); d_buf = nullptr; }
+    if (!d_buf) {
+        hipError_t e = hipMalloc((void **)&d_buf, need);
+        if (e != hipSuccess) { (void)hipGetLastError(); set_error("%s (%zu B): %s", what, need, hipGetErrorString(e)); return TB_ERR_NOMEM; }
+        have = need;
+    }
+    return TB_OK;
+}
+
+#ifdef TB_ABLATION
+// TB_PROF_STAMPS (profiling build): 16 phase time stamps of every 256th workgroup of the fused tangent kernel
+static int prof_stamps_begin(tb_mesh *m, MechMesh &mm)
+{
+    static long long *d_mprof = nullptr;
+    static size_t have = 0;
+    const size_t need = (size_t)((m->n_cells >> 8) + 1) * 16 * sizeof(long long);
+    if (!getenv("TB_PROF_STAMPS")) return TB_OK;
+    if (d_mprof && have < need) { (void)hipFree(d_mprof); d_mprof = nullptr; }
+    if (!d_mprof) { TB_HIP(hipMalloc((void **)&d_mprof, need)); have = need; }
+    TB_HIP(hipMemsetAsync(d_mprof, 0, need, m->dev->stream));
+    mm.prof = d_mprof;
+    return TB_OK;
+}
+
+// average phase durations of the sampled workgroups (µs; wall clock 100 MHz)
+static int prof_stamps_report(tb_mesh *m, const MechMesh &mm)
+{
+    if (!mm.prof) return TB_OK;
+    tb_device *dev = m->dev;
+    const int nmprof = (int)(m->n_cells >> 8) + 1;
+    std::vector<long long> h((size_t)nmprof * 16);
+    TB_SYNC_STREAM(dev);
+    TB_HIP(hipMemcpy(h.data(), mm.prof, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
+    double ph[14] = {0};
+    int cnt = 0;
+    for (int w = 0; w < nmprof; ++w) {
+        const long long *a = &h[(size_t)w * 16];
+        if (!a[0] || !a[14]) continue;
+        for (int k = 0; k < 14; ++k) ph[k] += (double)(a[k + 1] - a[k]) * 0.01;
+        ++cnt;
+    }
+    if (cnt) {
+        fprintf(stderr, "[tbhip] mechanics phases (us, n=%d): load %.2f | A1+H %.2f | F+common %.2f | rows %.2f | stage0 %.2f | racc+setup %.2f |", cnt,
+                ph[0] / cnt, ph[1] / cnt, ph[2] / cnt, ph[3] / cnt, ph[4] / cnt, ph[5] / cnt);
+        for (int c = 0; c < 3; ++c) fprintf(stderr, " c%d: s1 %.2f s23 %.2f |", c, ph[6 + 2 * c] / cnt, ph[7 + 2 * c] / cnt);
+        fprintf(stderr, " tail %.2f | drain %.2f\n", ph[12] / cnt, ph[13] / cnt);
+    }
+    return TB_OK;
+}
+#endif
+
+// ElementAssemblyStrategy (default for mechanics): Kₑ / rₑ stored per cell, then gathered per node row / per dof (tb_mech_gather.hip)
+template <class FE, bool NEED_K, bool NEED_R, bool AD>
+static int run_element(const MechCall &c)
+{
+    tb_form *f = c.f;
+    tb_pattern *p = c.p;
     tb_mesh *m = f->mesh;
     tb_device *dev = m->dev;
-    constexpr bool refgrad_r = !NEED_K && NEED_R && FE::NB == 27 && FE::NQ == 27 && FE::THREADS == 256; // residual-only kernel on the reference-gradient path
-    if ((NEED_K && CT == 2) || refgrad_r) { int rcx = ensure_cell_xyz(m); if (rcx) return rcx; }
-    MechMesh mm{m->d_xyz, m->d_conn, m->d_cell_dofs, f->d_field, f->cond_model ? nullptr : f->d_act_field, f->cond_model ? f->d_qp_act : nullptr, f->d_u_prev ? 5 : 2,
-                m->d_cell_xyz};
+    if (!m->ea) TB_TRY(build_ea_plan(m));
+    double *const rebuf = m->ea->d_ea;
+    double *kebuf = nullptr;
+    if constexpr (NEED_K) {
+        TB_TRY(ensure_buffer(p->d_kebuf, p->kebuf_bytes, sizeof(double) * (size_t)m->n_cells * FE::ND * FE::ND, "element-matrix buffer"));
+        kebuf = p->d_kebuf;
+    }
+    // split linearisation (comment above k_mech_points in tb_mech_split.hip): point kernel + contraction kernel instead of the fused one — every
+    // symmetric tangent of the triquadratic field (the rate-coupled internal variable adds a non-symmetric term: fused kernel)
+    constexpr bool Q2K = NEED_K && FE::NB == 27;
+    const bool split = Q2K && !(f->cond_model && f->d_u_prev);
+    auto integrate = [&](int64_t c0, int64_t n) -> int { // cells [c0, c0 + n) → stored Kₑ / rₑ
+        if constexpr (Q2K) {
+            if (split) {
+                if (!n) return TB_OK;
+                MechMesh mm = c.mm;
+                mm.cell0 = c0;
+                TB_TRY(launch_mech_points(dev, mm, c.hp, AD ? &c.ep : nullptr, c.d_u, n, p->d_qpbuf));
+                return launch_mech_contract(dev, p->d_qpbuf, c0, n, kebuf, NEED_R ? rebuf : nullptr);
+            }
+        }
+        return launch_cells<FE, NEED_K, NEED_R, AD>(c, nullptr, c0, n, 2, kebuf, rebuf);
+    };
+    // Chunked linearisation (TB_MECH_CHUNKS=n; default 8 for large Q2 meshes, see below; 0 / 1 = one launch): the cells go in n launches, and behind each the
+    // staged gather of the node rows that chunk completes runs on a second queue — the HBM-bound gather (46 GB at 80³) beside the LDS / VALU-bound
+    // integration of the next chunk.  Same kernels, same sums (a node's cells are still added in cell order): the unchunked result bit for bit.
+    // Measured at 80³ (kernel trace, profiles/r04_v2/mechanics_chunk_timeline.txt): the pairs do run side by side, but a CU that holds three
+    // integration workgroups has neither LDS (3 × 53 KB) nor registers (3 × 168) left, so every gather workgroup displaces an integration one —
+    // 2.55 ms per pair against 1.42 + 1.18 ms alone; the gain is what the pipeline ends and the dispatch gaps cost before: 21.3 → 20.7 ms.
+    // default: the triquadratic field from 262 144 cells (below that, and for the first-order field, sixteen small launches cost more than the overlap returns:
+    // the 111 616-cell ventricle with a Q1 displacement took 1.26 instead of 1.11 ms)
+    const int chunks_default = FE::NB == 27 && m->n_cells >= 262144 ? 8 : 0;
+    const int chunks = [&] { const char *e = getenv("TB_MECH_CHUNKS"); return e ? atoi(e) : chunks_default; }(); // read per call: a 20 ms operation
+    bool chunked = false;
+    if constexpr (NEED_K) {
+        if (chunks > 1 && m->n_cells >= 4096 * (int64_t)chunks) {
+            TB_TRY(prepare_tangent_gather(p));
+            chunked = p->gnodes_state > 0; // the direct gather cannot take a range of nodes before all cells are stored
+        }
+    }
+    if (chunked) TB_TRY(ensure_aux_stream(dev));
+    if (split) TB_TRY(ensure_buffer(p->d_qpbuf, p->qpbuf_bytes, sizeof(double) * (size_t)(chunked ? m->n_cells / chunks + 1 : m->n_cells) * QP_REC, "quadrature-point record buffer"));
+    if (chunked) {
+        int64_t n_done = 0;
+        const int rcl = [&]() -> int {
+            for (int k = 0; k < chunks; ++k) {
+                const int64_t c0 = m->n_cells * k / chunks, c1 = m->n_cells * (k + 1) / chunks;
+                TB_TRY(integrate(c0, c1 - c0));
+                TB_HIP(hipEventRecord(dev->aux_ev[0], dev->stream));
+                TB_HIP(hipStreamWaitEvent(dev->aux_stream, dev->aux_ev[0], 0));
+                const int64_t n1 = k + 1 == chunks ? m->n_nodes_field : std::upper_bound(p->h_gn_last.begin(), p->h_gn_last.end(), (int32_t)(c1 - 1)) - p->h_gn_last.begin();
+                if (n1 > n_done) {
+                    TB_TRY(launch_tangent_gather(p, dev->aux_stream, n_done, n1, kebuf, c.d_nz));
+                    n_done = n1;
+                }
+            }
+            return TB_OK;
+        }();
+        // the second queue is joined on every path, also behind an error half way through the chunks
+        TB_HIP(hipEventRecord(dev->aux_ev[1], dev->aux_stream));
+        TB_HIP(hipStreamWaitEvent(dev->stream, dev->aux_ev[1], 0));
+        if (rcl) return rcl;
+    } else {
+        TB_TRY(integrate(0, m->n_cells));
+    }
 #ifdef TB_ABLATION
-    static long long *d_mprof = nullptr;
-    const int nmprof = (int)(m->n_cells >> 8) + 1;
-    if (!d_mprof && getenv("TB_PROF_STAMPS") && NEED_K) TB_HIP(hipMalloc((void **)&d_mprof, (size_t)nmprof * 16 * sizeof(long long)));
-    if (d_mprof && NEED_K) TB_HIP(hipMemsetAsync(d_mprof, 0, (size_t)nmprof * 16 * sizeof(long long), dev->stream));
-    mm.prof = NEED_K ? d_mprof : nullptr;
+    TB_TRY(prof_stamps_report(m, c.mm));
 #endif
-    const HOParams hp = make_params(f);
-    const EnergyParams ep = make_energy_params(f);
+    if constexpr (NEED_K) {
+        if (!chunked) {
+            TB_TRY(prepare_tangent_gather(p));
+            TB_TRY(launch_tangent_gather(p, dev->stream, 0, m->n_nodes_field, kebuf, c.d_nz));
+        }
+    }
+    if (NEED_R) TB_TRY(launch_residual_gather(m, rebuf, c.d_r));
+    return TB_OK;
+}
+
+// PerColorAssemblyStrategy: one launch per colour, read-modify-write without atomics
+template <class FE, bool NEED_K, bool NEED_R, bool AD>
+static int run_per_color(const MechCall &c)
+{
+    tb_form *f = c.f;
+    tb_mesh *m = f->mesh;
+    const ColorPlan *cp;
+    if (f->has_cellset) {
+        if (!f->set_colors) TB_TRY(build_color_plan_subset(m, f->h_cellset, f->set_colors));
+        cp = f->set_colors.get();
+    } else {
+        if (!m->colors) TB_TRY(build_color_plan(m));
+        cp = m->colors.get();
+    }
+    for (int k = 0; k < cp->ncolors; ++k) TB_TRY((launch_cells<FE, NEED_K, NEED_R, AD>(c, cp->d_cells + cp->offsets[k], 0, cp->offsets[k + 1] - cp->offsets[k], 0)));
+    return TB_OK;
+}
+
+// AtomicAssemblyStrategy: all cells (of the subdomain) in one launch
+template <class FE, bool NEED_K, bool NEED_R, bool AD>
+static int run_atomic(const MechCall &c)
+{
+    const tb_form *f = c.f;
+    return f->has_cellset ? launch_cells<FE, NEED_K, NEED_R, AD>(c, f->d_cellset, 0, f->n_set, 1) : launch_cells<FE, NEED_K, NEED_R, AD>(c, nullptr, 0, f->mesh->n_cells, 1);
+}
+
+template <class FE, bool NEED_K, bool NEED_R, bool AD>
+static int run(tb_form *f, tb_pattern *p, int strategy, const double *d_u, double *d_nz, double *d_r)
+{
+    tb_mesh *m = f->mesh;
+    tb_device *dev = m->dev;
+    if ((NEED_K && FE::NB == 27) || refgrad_r<FE, NEED_K, NEED_R>) TB_TRY(ensure_cell_xyz(m)); // the kernels on the reference-gradient path read the cell-major coordinates
+    MechCall c{f, p, d_u, d_nz, d_r,
+               MechMesh{m->d_xyz, m->d_conn, m->d_cell_dofs, f->d_field, f->cond_model ? nullptr : f->d_act_field, f->cond_model ? f->d_qp_act : nullptr, f->d_u_prev ? 5 : 2, m->d_cell_xyz},
+               make_params(f), make_energy_params(f)};
+#ifdef TB_ABLATION
+    if (NEED_K) TB_TRY(prof_stamps_begin(m, c.mm));
+#endif
     const bool ea = strategy == TB_STRATEGY_ELEMENT || strategy == TB_STRATEGY_PATCH;
     if (ea && (f->has_cellset || f->accumulate)) {
         set_error("hyperelastic assembly: subdomain / accumulating forms need TB_STRATEGY_PER_COLOR or TB_STRATEGY_ATOMIC (the element strategy writes whole rows)");
         return TB_ERR_UNSUPPORTED;
     }
     if (NEED_K) {
-        int rc = ensure_blockpos(p);
-        if (rc) return rc;
+        TB_TRY(ensure_blockpos(p));
         if (!ea && !f->accumulate) TB_HIP(hipMemsetAsync(d_nz, 0, (size_t)p->nnz * sizeof(double), dev->stream));
     }
     if (NEED_R && !ea && !f->accumulate) TB_HIP(hipMemsetAsync(d_r, 0, (size_t)m->ndofs * sizeof(double), dev->stream));
-    const int64_t *rowptr = p ? p->d_rowptr : nullptr;
-    const uint16_t *bp = p ? p->d_blockpos : nullptr;
-    double *kebuf = nullptr, *rebuf = nullptr;
-    const uint8_t *rank27 = nullptr;
-    constexpr size_t dyn_lds = sizeof(double) * ((NEED_K ? FE::NQ : 1) * 81 + (refgrad_r ? 0 : FE::NQ * FE::NB * 3)); // 𝔸·dΩ + mapped gradients (s_AG; no gradient block on the reference-gradient residual path)
-    auto go = [&](const int32_t *list, int64_t n, int atomic) -> int {
-        if (!n) return TB_OK;
-        auto kern = k_hyperelastic<FE, NEED_K, NEED_R, CT, AD>;
-        TB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds));
-        hipLaunchKernelGGL(kern, dim3((unsigned)n), dim3(FE::THREADS), dyn_lds, dev->stream, mm, hp, ep, list, d_u, d_nz, d_r,
-                           rowptr, bp, atomic, kebuf, rebuf, dev->d_status, rank27);
-        TB_HIP(hipGetLastError());
-        return TB_OK;
-    };
-    if (ea) {
-        // ElementAssemblyStrategy (default for mechanics): Kₑ / rₑ stored per cell, then gathered per node row
-        if (!m->ea) { int rc = build_ea_plan(m); if (rc) return rc; }
-        rebuf = m->ea->d_ea;
-        int rc;
-        // TB_MECH_KE=sym: symmetric-packed element matrices + mirroring gather on the matrix-core path (its tangent is symmetric by construction; meshes
-        // where no node sits in more than 16 cells).  A measured alternative, parity-green, slower on MI355X than the full 81 × 81 storage although it
-        // moves 47 GB instead of 73 GB at 80³: integration 23.2 vs 21.3 ms (the store was never the bound; the LDS staging adds two barriers),
-        // gather 15.2 vs 13.3 ms (24-byte mirror pieces cost more than the halved reads save) — profiles/r03_v1/mechanics_sym_vs_full.txt
-        bool sym = false;
-        if (NEED_K && MFMA) {
-            const char *e = tune_env("TB_MECH_KE");
-            if (e && !strcmp(e, "sym")) { rc = ensure_rank27(m); if (rc) return rc; sym = m->rank27_ok > 0; }
-        }
-        // split linearisation (round 5; comment above k_mech_points in tb_mech_split.hip): point kernel + contraction kernel instead of the fused one —
-        // every symmetric tangent of the triquadratic field (the rate-coupled internal variable adds a non-symmetric term: fused kernel)
-        bool split = false, ke_sym2 = false;
-        if constexpr (NEED_K && CT == 2 && FE::NB == 27) {
-            const char *e = tune_env("TB_MECH_SPLIT");
-            split = !(e && atoi(e) == 0) && !(f->cond_model && f->d_u_prev);
-            // TB_MECH_KE=sym2 (profiling build only): the element matrices symmetric-packed by rank — half the bytes of the largest stream — with a staged gather
-            // that PULLS the transposed 72-byte blocks of the lower-ranked neighbours.  Parity-green and SLOWER (round 5, 80³, same box): the contraction
-            // kernel is unchanged (9.0 ms: it was never bound by its stores), the gather takes 13.1 instead of 9.4 ms — a wave-load that touches seven
-            // separate 72-byte blocks costs the address path more than the halved bytes save — linearize 23.6–24.0 against 19.6–19.9 ms.  Third negative
-            // for symmetric storage (round 3: mirror writes from the matrix-core kernel): the 81 × 81 tensor-order form stays.
-            if (split && tune_env("TB_MECH_KE") && !strcmp(tune_env("TB_MECH_KE"), "sym2")) {
-                if (!m->d_node_dof0) { rc = build_node_list(m); if (rc) return rc; }
-                rc = check_node_rows(p);
-                if (rc) return rc;
-                rc = ensure_gather_nodes(p);
-                if (rc) return rc;
-                rc = ensure_rank27(m);
-                if (rc) return rc;
-                ke_sym2 = p->gnodes_state > 0 && m->rank27_ok > 0;
-            }
-        }
-        if (NEED_K) {
-            const size_t need = sizeof(double) * (size_t)m->n_cells * (sym || ke_sym2 ? (size_t)KE_SYM : (size_t)FE::ND * FE::ND);
-            if (p->d_kebuf && p->kebuf_bytes < need) { (void)hipFree(p->d_kebuf); p->d_kebuf = nullptr; }
-            if (!p->d_kebuf) {
-                hipError_t e = hipMalloc((void **)&p->d_kebuf, need);
-                if (e != hipSuccess) { set_error("element-matrix buffer (%zu B): %s", need, hipGetErrorString(e)); return TB_ERR_NOMEM; }
-                p->kebuf_bytes = need;
-            }
-            kebuf = p->d_kebuf;
-            if (sym) rank27 = m->d_rank27;
-        }
-        // Chunked linearisation (TB_MECH_CHUNKS=n; default 8 for large Q2 meshes, see below; 0 / 1 = one launch): the cells go in n launches, and behind each the
-        // staged gather of the node rows that chunk completes runs on a second queue — the HBM-bound gather (46 GB at 80³) beside the LDS / VALU-bound
-        // integration of the next chunk.  Same kernels, same sums (a node's cells are still added in cell order): the unchunked result bit for bit.
-        // Measured at 80³ (kernel trace, profiles/r04_v2/mechanics_chunk_timeline.txt): the pairs do run side by side, but a CU that holds three
-        // integration workgroups has neither LDS (3 × 53 KB) nor registers (3 × 168) left, so every gather workgroup displaces an integration one —
-        // 2.55 ms per pair against 1.42 + 1.18 ms alone; the gain is what the pipeline ends and the dispatch gaps cost before: 21.3 → 20.7 ms.
-        // default: the triquadratic field from 262 144 cells (below that, and for the first-order field, sixteen small launches cost more than the overlap returns:
-        // the 111 616-cell ventricle with a Q1 displacement took 1.26 instead of 1.11 ms)
-        const int chunks_default = FE::NB == 27 && m->n_cells >= 262144 ? 8 : 0;
-        const int chunks_env = [&] { const char *e = getenv("TB_MECH_CHUNKS"); return e ? atoi(e) : chunks_default; }(); // read per call: a 20 ms operation
-        auto go_ea = [&](int64_t c0, int64_t n) -> int { // cells [c0, c0 + n) → stored Kₑ / rₑ
-            if constexpr (NEED_K && CT == 2 && FE::NB == 27) {
-                if (split) {
-                    if (!n) return TB_OK;
-                    mm.cell0 = c0;
-                    int rcs = launch_mech_points(dev, mm, hp, AD ? &ep : nullptr, d_u, n, p->d_qpbuf);
-                    if (!rcs) rcs = launch_mech_contract(dev, p->d_qpbuf, c0, n, kebuf, NEED_R ? rebuf : nullptr, ke_sym2 ? m->d_rank27 : nullptr);
-                    if (rcs) return rcs;
-                    mm.cell0 = 0;
-                    return TB_OK;
-                }
-            }
-            mm.cell0 = c0;
-            const int rcg = go(nullptr, n, 2);
-            mm.cell0 = 0;
-            return rcg;
-        };
-        auto ensure_qpbuf = [&](int64_t ncell_max) -> int {
-            const size_t need = sizeof(double) * (size_t)ncell_max * QP_REC;
-            if (p->d_qpbuf && p->qpbuf_bytes < need) { (void)hipFree(p->d_qpbuf); p->d_qpbuf = nullptr; }
-            if (!p->d_qpbuf) {
-                hipError_t e = hipMalloc((void **)&p->d_qpbuf, need);
-                if (e != hipSuccess) { (void)hipGetLastError(); set_error("quadrature-point record buffer (%zu B): %s", need, hipGetErrorString(e)); return TB_ERR_NOMEM; }
-                p->qpbuf_bytes = need;
-            }
-            return TB_OK;
-        };
-        bool chunked = false;
-        if (NEED_K && !sym && !MFMA && chunks_env > 1 && m->n_cells >= 4096 * (int64_t)chunks_env) {
-            if (!m->d_node_dof0) { rc = build_node_list(m); if (rc) return rc; }
-            rc = check_node_rows(p);
-            if (rc) return rc;
-            rc = ensure_gather_nodes(p);
-            if (rc) return rc;
-            chunked = p->gnodes_state > 0;
-        }
-        if (chunked) {
-            rc = ensure_aux_stream(dev);
-            if (rc) return rc;
-            const int nbr_pad = ((((int)p->max_row_len / 3 + 3) & ~3) + 7) & ~7;
-            const size_t glds = (size_t)4 * 4 * (3 * FE::ND * sizeof(double) + (size_t)nbr_pad);
-            int64_t n_done = 0;
-            if (split) { rc = ensure_qpbuf(m->n_cells / chunks_env + 1); if (rc) return rc; }
-            const int rcl = [&]() -> int {
-                for (int k = 0; k < chunks_env; ++k) {
-                    const int64_t c0 = m->n_cells * k / chunks_env, c1 = m->n_cells * (k + 1) / chunks_env;
-                    rc = go_ea(c0, c1 - c0);
-                    if (rc) return rc;
-                    TB_HIP(hipEventRecord(dev->aux_ev[0], dev->stream));
-                    TB_HIP(hipStreamWaitEvent(dev->aux_stream, dev->aux_ev[0], 0));
-                    const int64_t n1 = k + 1 == chunks_env ? m->n_nodes_field : std::upper_bound(p->h_gn_last.begin(), p->h_gn_last.end(), (int32_t)(c1 - 1)) - p->h_gn_last.begin();
-                    if (n1 > n_done) {
-                        const auto launch_g = [&](auto kg) { hipLaunchKernelGGL(kg, dim3((unsigned)((n1 - n_done + 3) / 4)), dim3(256), glds, dev->aux_stream, (const GatherNode *)p->d_gnodes + n_done,
-                                           n1 - n_done, kebuf, bp, d_nz, nbr_pad, ke_sym2 ? m->d_rank27 : nullptr); };
-                        TB_IF_ABLATION(if (ke_sym2) launch_g(k_gather_node_rows_lds<FE::NB, 4, 2>); else) launch_g(k_gather_node_rows_lds<FE::NB, 4, (NEED_K && CT == 2 && FE::NB == 27) ? 1 : 0>);
-                        TB_HIP(hipGetLastError());
-                        n_done = n1;
-                    }
-                }
-                return TB_OK;
-            }();
-            // the second queue is joined on every path, also behind an error half way through the chunks
-            TB_HIP(hipEventRecord(dev->aux_ev[1], dev->aux_stream));
-            TB_HIP(hipStreamWaitEvent(dev->stream, dev->aux_ev[1], 0));
-            if (rcl) return rcl;
-        } else {
-        if (split) { rc = ensure_qpbuf(m->n_cells); if (rc) return rc; }
-        rc = go_ea(0, m->n_cells);
-        if (rc) return rc;
-        }
-#ifdef TB_ABLATION
-        if (mm.prof) { // average phase durations of the sampled workgroups (µs; wall clock 100 MHz)
-            std::vector<long long> h((size_t)nmprof * 16);
-            TB_SYNC_STREAM(dev);
-            TB_HIP(hipMemcpy(h.data(), mm.prof, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-            double ph[14] = {0};
-            int cnt = 0;
-            for (int w = 0; w < nmprof; ++w) {
-                const long long *a = &h[(size_t)w * 16];
-                if (!a[0] || !a[14]) continue;
-                for (int k = 0; k < 14; ++k) ph[k] += (double)(a[k + 1] - a[k]) * 0.01;
-                ++cnt;
-            }
-            if (cnt) {
-                fprintf(stderr, "[tbhip] mechanics phases (us, n=%d): load %.2f | A1+H %.2f | F+common %.2f | rows %.2f | stage0 %.2f | racc+setup %.2f |", cnt,
-                        ph[0] / cnt, ph[1] / cnt, ph[2] / cnt, ph[3] / cnt, ph[4] / cnt, ph[5] / cnt);
-                for (int c = 0; c < 3; ++c) fprintf(stderr, " c%d: s1 %.2f s23 %.2f |", c, ph[6 + 2 * c] / cnt, ph[7 + 2 * c] / cnt);
-                fprintf(stderr, " tail %.2f | drain %.2f\n", ph[12] / cnt, ph[13] / cnt);
-            }
-        }
-#endif
-        if (NEED_K && sym) {
-            if (!m->d_node_dof0) { rc = build_node_list(m); if (rc) return rc; }
-            rc = check_node_rows(p);
-            if (rc) return rc;
-            const int nbr_max = (((int)p->max_row_len / 3) + 3) & ~3;
-            const size_t per_wave = ((size_t)16 * nbr_max + 2 * (size_t)nbr_max + 16 * 16 + 63 * 3 * 8 + 64 * 8 + 15) & ~(size_t)15;
-            const int64_t ngroups = (m->n_nodes_field + 3) / 4;
-            auto k = k_gather_node_rows_sym<FE::NB>;
-            hipLaunchKernelGGL(k, dim3((unsigned)(8 * ((ngroups + 7) / 8))), dim3(256), 4 * per_wave, dev->stream, m->d_node_dof0, m->n_nodes_field, m->ea->d_ptr,
-                               m->ea->d_src, kebuf, bp, rank27, rowptr, p->d_colidx, d_nz, nbr_max, ngroups);
-            TB_HIP(hipGetLastError());
-        } else if (NEED_K && !chunked) {
-            if (!m->d_node_dof0) { rc = build_node_list(m); if (rc) return rc; }
-            rc = check_node_rows(p);
-            if (rc) return rc;
-            const int nbr_max = (((int)p->max_row_len / 3) + 3) & ~3;
-            // TB_MECH_GATHER=direct: the trip-bound kernel above, kept as the comparison build (12.8 ms against 9.1 ms at 80³; a variant staging all 8
-            // cells of a vertex node at once was slower still: 66 KB of LDS per workgroup leave 8 waves per CU)
-            static const bool direct = [] { const char *e = tune_env("TB_MECH_GATHER"); return e && !strcmp(e, "direct"); }();
-            if (!(MFMA && KE_DMAJOR) && !direct) { rc = ensure_gather_nodes(p); if (rc) return rc; }
-            if (!(MFMA && KE_DMAJOR) && !direct && p->gnodes_state > 0) {
-                const int nbr_pad = (nbr_max + 7) & ~7;
-                const size_t lds = (size_t)4 * 4 * (3 * FE::ND * sizeof(double) + (size_t)nbr_pad);
-                const auto launch_g = [&](auto k) { hipLaunchKernelGGL(k, dim3((unsigned)((m->n_nodes_field + 3) / 4)), dim3(256), lds, dev->stream, (const GatherNode *)p->d_gnodes,
-                                   m->n_nodes_field, kebuf, bp, d_nz, nbr_pad, ke_sym2 ? m->d_rank27 : nullptr); };
-                TB_IF_ABLATION(if (ke_sym2) launch_g(k_gather_node_rows_lds<FE::NB, 4, 2>); else) launch_g(k_gather_node_rows_lds<FE::NB, 4, (NEED_K && CT == 2 && FE::NB == 27) ? 1 : 0>);
-            } else {
-                const size_t lds = (size_t)4 * 8 * nbr_max;
-                auto k = k_gather_node_rows<FE::NB, MFMA && KE_DMAJOR, (NEED_K && CT == 2 && FE::NB == 27)>;
-                hipLaunchKernelGGL(k, dim3((unsigned)((m->n_nodes_field + 3) / 4)), dim3(256), lds, dev->stream, m->d_node_dof0, m->n_nodes_field,
-                                   m->ea->d_ptr, m->ea->d_src, kebuf, bp, rowptr, d_nz, nbr_max);
-            }
-            TB_HIP(hipGetLastError());
-        }
-        if (NEED_R) {
-            hipLaunchKernelGGL(k_gather_residual, dim3((unsigned)((m->ndofs + 255) / 256)), dim3(256), 0, dev->stream, m->ea->d_ptr, m->ea->d_src,
-                               rebuf, m->ndofs, d_r);
-            TB_HIP(hipGetLastError());
-        }
-        return TB_OK;
-    }
-    if (strategy == TB_STRATEGY_PER_COLOR) {
-        const ColorPlan *cp;
-        if (f->has_cellset) {
-            if (!f->set_colors) { int rc = build_color_plan_subset(m, f->h_cellset, f->set_colors); if (rc) return rc; }
-            cp = f->set_colors.get();
-        } else {
-            if (!m->colors) { int rc = build_color_plan(m); if (rc) return rc; }
-            cp = m->colors.get();
-        }
-        for (int c = 0; c < cp->ncolors; ++c) {
-            int rc = go(cp->d_cells + cp->offsets[c], cp->offsets[c + 1] - cp->offsets[c], 0);
-            if (rc) return rc;
-        }
-        return TB_OK;
-    }
-    if (strategy == TB_STRATEGY_ATOMIC) return f->has_cellset ? go(f->d_cellset, f->n_set, 1) : go(nullptr, m->n_cells, 1);
+    if (ea) return run_element<FE, NEED_K, NEED_R, AD>(c);
+    if (strategy == TB_STRATEGY_PER_COLOR) return run_per_color<FE, NEED_K, NEED_R, AD>(c);
+    if (strategy == TB_STRATEGY_ATOMIC) return run_atomic<FE, NEED_K, NEED_R, AD>(c);
     set_error("hyperelastic assembly: unknown strategy %d", strategy);
     return TB_ERR_UNSUPPORTED;
 }
+
 
 // ---- condensed internal variables, stage 0: fibre stretch λ = ‖F f₀‖ and calcium at every quadrature point (the inputs of the local
 // problem; solve_local_constraint, materials.jl:1575-1590).  One workgroup per cell, one lane per quadrature point.
@@ -1643,169 +1060,18 @@ int launch_hyperelastic(tb_form *f, tb_pattern *p, int strategy, const double *d
     const bool q2 = m->field_kind == TB_HEX27;
     if (!q2 && !(m->field_kind == TB_HEX8 && f->qorder == 2)) { set_error("hyperelastic: Q1 field needs quadrature order 2"); return TB_ERR_UNSUPPORTED; }
     if (q2 && f->qorder != 3) { set_error("hyperelastic: Q2 field needs quadrature order 3"); return TB_ERR_UNSUPPORTED; }
-    // Q2 tangents: sum-factorised contraction (default); TB_MECH_CONTRACT=mfma selects the matrix-core build, =vector the plain FMA sweep over
-    // the points (comparison builds; TB_MECH_MFMA=0 is the older spelling of "vector")
-    const char *ce = tune_env("TB_MECH_CONTRACT");
-    const bool old_vec = tune_env("TB_MECH_MFMA") && atoi(tune_env("TB_MECH_MFMA")) == 0;
-    const int ct2 = (ce && !strcmp(ce, "mfma")) ? 1 : ((ce && !strcmp(ce, "vector")) || old_vec) ? 0 : 2;
     const bool ad = !form_is_fast_path(f);
     if (f->cond_model) {
         rc = q2 ? condensed_prepass<Q2Vec>(f, d_u, d_nz != nullptr) : condensed_prepass<Q1Vec>(f, d_u, d_nz != nullptr);
         if (rc) return rc;
     }
-    const bool nonsym = f->cond_model && f->d_u_prev; // rate-coupled internal variable: the symmetric-tile matrix-core kernel does not apply
-    const int ct = !q2 ? 0 : (ct2 == 1 && nonsym) ? 0 : ct2;
-#define TB_RUN(FEV, K, R, C) (ad ? run<FEV, K, R, C, true>(f, p, strategy, d_u, d_nz, d_r) : run<FEV, K, R, C, false>(f, p, strategy, d_u, d_nz, d_r))
-    if (d_nz && d_r) rc = !q2 ? TB_RUN(Q1Vec, true, true, 0) : ct == 2 ? TB_RUN(Q2Vec, true, true, 2) : ct == 1 ? TB_RUN(Q2Vec, true, true, 1) : TB_RUN(Q2Vec, true, true, 0);
-    else if (d_nz) rc = !q2 ? TB_RUN(Q1Vec, true, false, 0) : ct == 2 ? TB_RUN(Q2Vec, true, false, 2) : ct == 1 ? TB_RUN(Q2Vec, true, false, 1) : TB_RUN(Q2Vec, true, false, 0);
-    else rc = q2 ? TB_RUN(Q2Vec, false, true, 0) : TB_RUN(Q1Vec, false, true, 0);
+#define TB_RUN(FEV, K, R) (ad ? run<FEV, K, R, true>(f, p, strategy, d_u, d_nz, d_r) : run<FEV, K, R, false>(f, p, strategy, d_u, d_nz, d_r))
+    if (d_nz && d_r) rc = q2 ? TB_RUN(Q2Vec, true, true) : TB_RUN(Q1Vec, true, true);
+    else if (d_nz) rc = q2 ? TB_RUN(Q2Vec, true, false) : TB_RUN(Q1Vec, true, false);
+    else rc = q2 ? TB_RUN(Q2Vec, false, true) : TB_RUN(Q1Vec, false, true);
 #undef TB_RUN
     if (rc) return rc;
     return check_status(m->dev);
-}
-
-
-// ------------------------------------------------------------------------------------------------ weak boundary conditions
-// Facet integrals of src/modeling/core/weak_boundary_conditions.jl (RobinBC :102-198, NormalSpringBC :200-300, pressure
-// follower load :419-515).  One 64-thread workgroup per (cell, local facet): per facet Gauss point the shape values,
-// mapped gradients and the few tensors the integrand needs are parked in LDS, then every thread sums its (i, j) pairs over
-// the points and adds the result to the CSR entry / residual entry with one atomic each (surface terms are O(n²) work, the
-// volume term O(n³): this kernel is not on the critical path).  FacetValues conventions are Ferrite's (tbhip.h).
-// (numbering, Gauss points and the geometry stage: tb_facet_geom.hpp)
-template <int NB>
-__global__ void __launch_bounds__(64)
-k_facets(MechMesh m, const int32_t *__restrict__ facets, int bc, double param, int fq, const double *__restrict__ pfield, const double *__restrict__ u, double *__restrict__ nz,
-         double *__restrict__ r, const int64_t *__restrict__ rowptr, const uint16_t *__restrict__ blockpos, Status *st)
-{
-    constexpr int ND = 3 * NB, MAXQ = 9;
-    const int tid = threadIdx.x;
-    const int64_t cell = facets[2 * blockIdx.x];
-    const int lf = facets[2 * blockIdx.x + 1];
-    __shared__ double s_ue[ND], s_x[24], s_N[MAXQ][NB], s_G[MAXQ][NB][3];
-    __shared__ double s_q[MAXQ][32]; // per point: dΓ, n₀[3], grad[3] (Robin / spring) or J·cofF·n₀ [3], H[9] / invF[9], J, invFᵀ… (see below)
-    __shared__ int32_t s_dof[ND];
-    for (int i = tid; i < ND; i += 64) { const int32_t d = m.cell_dofs[cell * ND + i]; s_dof[i] = d; s_ue[i] = u[d]; }
-    for (int i = tid; i < 24; i += 64) s_x[i] = m.xyz[3 * (int64_t)m.conn[cell * 8 + i / 3] + i % 3];
-    __syncthreads();
-    const int nq = fq * fq;
-    facet_geometry_stage<NB>(tid, cell, lf, fq, s_x, s_N, s_G, s_q, st); // shape values, mapped gradients, dΓ and n₀ per point
-    __syncthreads();
-    // field values per point (one thread per point): u_q, F, and the tensors of the integrand
-    //   slots: [4..6] g = residual vector density (δuᵢ·g), [7..15] H (Robin / spring: Hessian; pressure: invF), [16] J, [17..19] cofF·n₀,
-    //          [20..22] invFᵀ-weighted normal  fin[d] = Σ_r invF[r][d] n₀[r]
-    if (tid < nq) {
-        const int q = tid;
-        double uq[3] = {0, 0, 0}, F[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-        for (int a = 0; a < NB; ++a)
-            for (int c = 0; c < 3; ++c) {
-                uq[c] += s_N[q][a] * s_ue[3 * a + c];
-                for (int k = 0; k < 3; ++k) F[c][k] += s_ue[3 * a + c] * s_G[q][a][k];
-            }
-        const double *n0 = &s_q[q][1];
-        double *o = s_q[q];
-        if (bc == TB_BC_ROBIN) {
-            for (int c = 0; c < 3; ++c) o[4 + c] = 2.0 * param * uq[c];
-            for (int e = 0; e < 9; ++e) o[7 + e] = (e % 4 == 0) ? 2.0 * param : 0.0;
-        } else if (bc == TB_BC_NORMAL_SPRING) {
-            const double un = uq[0] * n0[0] + uq[1] * n0[1] + uq[2] * n0[2];
-            for (int c = 0; c < 3; ++c) o[4 + c] = param * un * n0[c];
-            for (int c = 0; c < 3; ++c) for (int d = 0; d < 3; ++d) o[7 + 3 * c + d] = param * n0[c] * n0[d];
-        } else {
-            double pq = param;
-            if (bc == TB_BC_PRESSURE_FIELD && pfield) { // evaluate_coefficient(pc, cell, qp, t): nodal data × M_a at the facet point
-                double xi[3];
-                facet_xi(lf, fq, q, xi);
-                double v = 0.0;
-                for (int a = 0; a < 8; ++a) { double Ma, dMa[3]; shape_at<8>(a, xi, Ma, dMa); v += Ma * pfield[cell * 8 + a]; }
-                pq = param * v;
-            }
-            const double c00 = F[1][1] * F[2][2] - F[1][2] * F[2][1], c01 = F[1][2] * F[2][0] - F[1][0] * F[2][2], c02 = F[1][0] * F[2][1] - F[1][1] * F[2][0];
-            const double Jf = F[0][0] * c00 + F[0][1] * c01 + F[0][2] * c02, id = 1.0 / Jf;
-            const double Fi[9] = {c00 * id, (F[0][2] * F[2][1] - F[0][1] * F[2][2]) * id, (F[0][1] * F[1][2] - F[0][2] * F[1][1]) * id,
-                                  c01 * id, (F[0][0] * F[2][2] - F[0][2] * F[2][0]) * id, (F[0][2] * F[1][0] - F[0][0] * F[1][2]) * id,
-                                  c02 * id, (F[0][1] * F[2][0] - F[0][0] * F[2][1]) * id, (F[0][0] * F[1][1] - F[0][1] * F[1][0]) * id};
-            for (int e = 0; e < 9; ++e) o[7 + e] = Fi[e];
-            o[16] = bc == TB_BC_BENDING_SPRING ? Jf : pq * Jf;      // pressure: p·J folded here
-            double vv[3];
-            for (int c = 0; c < 3; ++c) {
-                const double cn = Fi[0 + c] * n0[0] + Fi[3 + c] * n0[1] + Fi[6 + c] * n0[2]; // v = F⁻ᵀ n₀
-                vv[c] = cn;
-                o[17 + c] = cn;
-                o[4 + c] = pq * Jf * cn;
-            }
-            if (bc == TB_BC_BENDING_SPRING) { // w = v − N, z = F⁻¹ w, B = F⁻¹ F⁻ᵀ (slots 20..22, 23..31)
-                const double w[3] = {vv[0] - n0[0], vv[1] - n0[1], vv[2] - n0[2]};
-                for (int j = 0; j < 3; ++j) o[20 + j] = Fi[3 * j + 0] * w[0] + Fi[3 * j + 1] * w[1] + Fi[3 * j + 2] * w[2];
-                for (int j = 0; j < 3; ++j)
-                    for (int l = 0; l < 3; ++l) o[23 + 3 * j + l] = Fi[3 * j + 0] * Fi[3 * l + 0] + Fi[3 * j + 1] * Fi[3 * l + 1] + Fi[3 * j + 2] * Fi[3 * l + 2];
-            }
-        }
-    }
-    __syncthreads();
-    // residual: rₑ[i] += δuᵢ·g dΓ   (bending spring: ∇δuᵢ ⊡ P dΓ with P = −kᵇ v ⊗ z)
-    if (r)
-        for (int i = tid; i < ND; i += 64) {
-            const int a = i / 3, c = i % 3;
-            double v = 0.0;
-            if (bc == TB_BC_BENDING_SPRING) {
-                for (int q = 0; q < nq; ++q) {
-                    const double *o = s_q[q], *g = s_G[q][a];
-                    v -= param * o[17 + c] * (g[0] * o[20] + g[1] * o[21] + g[2] * o[22]) * o[0];
-                }
-            } else {
-                for (int q = 0; q < nq; ++q) v += s_N[q][a] * s_q[q][4 + c] * s_q[q][0];
-            }
-            if (v != 0.0) unsafeAtomicAdd(r + s_dof[i], v);
-        }
-    // tangent
-    if (nz)
-        for (int ij = tid; ij < ND * ND; ij += 64) {
-            const int i = ij / ND, j = ij % ND, a = i / 3, c = i % 3, b = j / 3, d = j % 3;
-            double v = 0.0;
-            if (bc == TB_BC_ROBIN || bc == TB_BC_NORMAL_SPRING) {
-                for (int q = 0; q < nq; ++q) v += s_N[q][a] * s_q[q][7 + 3 * c + d] * s_N[q][b] * s_q[q][0];
-            } else if (bc == TB_BC_BENDING_SPRING) {
-                // 𝔸[c][k][d][l] = kᵇ [ v_d F⁻¹_lc z_k + v_c (F⁻¹_kd z_l + v_d B_kl) ],  Kₑ += ∇N_a[k] 𝔸 ∇N_b[l] dΓ
-                for (int q = 0; q < nq; ++q) {
-                    const double *o = s_q[q], *Fi = o + 7, *ga = s_G[q][a], *gb = s_G[q][b], *z = o + 20, *B = o + 23;
-                    const double gaz = ga[0] * z[0] + ga[1] * z[1] + ga[2] * z[2], gbz = gb[0] * z[0] + gb[1] * z[1] + gb[2] * z[2];
-                    const double gaFd = ga[0] * Fi[0 + d] + ga[1] * Fi[3 + d] + ga[2] * Fi[6 + d];
-                    const double gbFc = gb[0] * Fi[0 + c] + gb[1] * Fi[3 + c] + gb[2] * Fi[6 + c];
-                    double gaBgb = 0.0;
-                    for (int k = 0; k < 3; ++k) gaBgb += ga[k] * (B[3 * k] * gb[0] + B[3 * k + 1] * gb[1] + B[3 * k + 2] * gb[2]);
-                    v += param * (o[17 + d] * gbFc * gaz + o[17 + c] * (gaFd * gbz + o[17 + d] * gaBgb)) * o[0];
-                }
-            } else {
-                for (int q = 0; q < nq; ++q) {
-                    const double *o = s_q[q], *Fi = o + 7, *g = s_G[q][b];
-                    double gF[3];
-                    for (int k = 0; k < 3; ++k) gF[k] = g[0] * Fi[0 + k] + g[1] * Fi[3 + k] + g[2] * Fi[6 + k];
-                    // δJ·cofF·n₀ + J·δcofF·n₀ for δF = e_d ⊗ ∇N_b
-                    v += o[16] * (gF[d] * o[17 + c] - gF[c] * o[17 + d]) * s_N[q][a] * o[0];
-                }
-            }
-            if (v != 0.0) unsafeAtomicAdd(nz + rowptr[s_dof[3 * a] + c] + blockpos[cell * (NB * NB) + a * NB + b] + d, v);
-        }
-}
-
-int launch_facets(tb_form *f, tb_pattern *p, const double *d_u, double *d_nz, double *d_r)
-{
-    tb_mesh *m = f->mesh;
-    tb_device *dev = m->dev;
-    int rc = reset_status(dev);
-    if (rc) return rc;
-    if (d_nz) { rc = ensure_blockpos(p); if (rc) return rc; }
-    const MechMesh mm{m->d_xyz, m->d_conn, m->d_cell_dofs, nullptr, nullptr};
-    const int64_t *rowptr = p ? p->d_rowptr : nullptr;
-    const uint16_t *bp = p ? p->d_blockpos : nullptr;
-    if (m->field_kind == TB_HEX27)
-        hipLaunchKernelGGL((k_facets<27>), dim3((unsigned)f->n_facets), dim3(64), 0, dev->stream, mm, f->d_facets, f->bc_kind, f->bc_param, f->facet_q, f->d_field,
-                           d_u, d_nz, d_r, rowptr, bp, dev->d_status);
-    else
-        hipLaunchKernelGGL((k_facets<8>), dim3((unsigned)f->n_facets), dim3(64), 0, dev->stream, mm, f->d_facets, f->bc_kind, f->bc_param, f->facet_q, f->d_field,
-                           d_u, d_nz, d_r, rowptr, bp, dev->d_status);
-    TB_HIP(hipGetLastError());
-    return check_status(dev);
 }
 
 } // namespace tb

@@ -905,5 +905,71 @@ Outcome fit_fused(const MeshView &m, const PatternView &p, const Options &o, int
     return refused(ERR_UNSUPPORTED);
 }
 
+// ---- tangent gather of the element strategy on three-component fields (tb_mech_gather.hip) ----
+
+// first-component dof of every node of the vector field (rows of a node are dof0, dof0+1, dof0+2), ascending
+std::vector<int32_t> node_list(const MeshView &m)
+{
+    std::vector<int32_t> d0;
+    d0.reserve((size_t)m.ndofs / 3);
+    std::vector<uint8_t> seen(m.ndofs, 0);
+    for (int64_t i = 0; i < m.n_cells * (m.ndpc / 3); ++i) {
+        const int32_t d = m.cell_dofs[3 * i];
+        if (!seen[d]) { seen[d] = 1; d0.push_back(d); }
+    }
+    std::sort(d0.begin(), d0.end());
+    return d0;
+}
+
+// the gather kernels rely on the three rows of a node being equal-length runs of whole nodes
+int node_row_check(const PatternView &p, const std::vector<int32_t> &dof0, int64_t &max_row_len)
+{
+    max_row_len = 0;
+    for (int32_t d : dof0) {
+        const int64_t L = p.rowptr[d + 1] - p.rowptr[d];
+        if (L % 3 || L != p.rowptr[d + 2] - p.rowptr[d + 1] || L != p.rowptr[d + 3] - p.rowptr[d + 2] || L / 3 > 254) {
+            set_error("element assembly gather: rows of node dof %d are not three equal runs of whole nodes (L = %lld)", d, (long long)L);
+            return ERR_PATTERN;
+        }
+        max_row_len = std::max<int64_t>(max_row_len, L);
+    }
+    return 0;
+}
+
+// node records of the staged gather, cells in ascending order like the slot lists.  Not applicable: a node row of more than 384 positions, slots
+// beyond int32, or a node in more than 8 cells (the direct gather takes those meshes).
+GatherHost gather_nodes(const MeshView &m, const PatternView &p, const std::vector<int32_t> &dof0)
+{
+    GatherHost out;
+    const int nd = m.ndpc, nb = nd / 3;
+    const int64_t nn = (int64_t)dof0.size();
+    if (p.max_row_len > 384 || m.n_cells * (int64_t)nd >= (int64_t)0x7fffffff) return out;
+    std::vector<int32_t> node_of((size_t)m.ndofs, -1);
+    for (int64_t i = 0; i < nn; ++i) node_of[dof0[i]] = (int32_t)i;
+    std::vector<GatherNode> recs((size_t)nn);
+    for (int64_t i = 0; i < nn; ++i) {
+        const int32_t d = dof0[i];
+        recs[i].g0 = p.rowptr[d];
+        recs[i].L = (int32_t)(p.rowptr[d + 1] - p.rowptr[d]);
+        recs[i].nk = 0;
+        for (int k = 0; k < 8; ++k) recs[i].slot[k] = 0;
+    }
+    for (int64_t c = 0; c < m.n_cells; ++c)
+        for (int a = 0; a < nb; ++a) {
+            GatherNode &g = recs[node_of[m.cell_dofs[c * nd + 3 * a]]];
+            if (g.nk >= 8) return out;
+            g.slot[g.nk++] = (int32_t)(c * nd + 3 * a);
+        }
+    // running maximum of the last contributing cell over the records (dof order): the records before the first one whose value reaches c are complete
+    // once cells [0, c) are integrated — the prefix the chunked linearisation gathers behind the integration front.  On a mesh numbered cell by cell
+    // the prefix trails the front by about one layer of cells.
+    out.last.resize((size_t)nn);
+    int32_t run = 0;
+    for (int64_t i = 0; i < nn; ++i) { run = std::max(run, recs[i].slot[recs[i].nk - 1] / nd); out.last[i] = run; }
+    out.recs = std::move(recs);
+    out.applicable = true;
+    return out;
+}
+
 } // namespace plan
 } // namespace tb

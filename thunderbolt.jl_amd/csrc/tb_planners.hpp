@@ -17,6 +17,13 @@ struct RowDesc {      // one owned row of a patch
     uint32_t len;     // row length
 };
 
+// Staged tangent gather of the element strategy on three-component fields (k_gather_node_rows_lds): one record per field node
+struct GatherNode {
+    int64_t g0;      // first nz of row dof0 (rows dof0+1, dof0+2 follow, L entries each)
+    int32_t L, nk;   // row length, number of cells at the node
+    int32_t slot[8]; // cell·ND + 3a: row offset of the node's run in the stored element matrices, cell-ordered
+};
+
 // wall time of the plan builders, stage by stage, on stderr (TB_PLAN_VERBOSE; what `setup_s.first_step_incl_plan_build` of bench.py is made of)
 struct StageTimer {
     const char *name;
@@ -106,10 +113,16 @@ struct VecHost {
 };
 struct ColorHost { int ncolors = 0; std::vector<int64_t> offsets; std::vector<int32_t> cells; }; // offsets: ncolors+1, into cells (grouped by colour)
 struct SlotTable { int w = 0; std::vector<int32_t> ell, h_done; }; // ell: ndofs × w, −1 padded; h_done: running maximum of the last contributing cell
+struct GatherHost { bool applicable = false; std::vector<GatherNode> recs; std::vector<int32_t> last; }; // last: running maximum of the records' last contributing cell
 
 void dof_slots(const MeshView &m, std::vector<int64_t> &ptr, std::vector<int32_t> &src); // dof → (cell·ndpc + local) slots, cell-ordered
 SlotTable slot_table(const MeshView &m);
 void tensor_order(std::vector<int32_t> &ell); // 27 dofs per cell: the local row of every slot replaced by its tensor index i₀ + 3 i₁ + 9 i₂
+// three-component fields: the first dofs of the field nodes; the "three equal runs of whole nodes, ≤ 254 neighbours" condition on their rows (0 or
+// ERR_PATTERN with the message set; max_row_len: the longest node row); the node records of the staged gather (p.max_row_len from the check)
+std::vector<int32_t> node_list(const MeshView &m);
+int node_row_check(const PatternView &p, const std::vector<int32_t> &dof0, int64_t &max_row_len);
+GatherHost gather_nodes(const MeshView &m, const PatternView &p, const std::vector<int32_t> &dof0);
 int color_cells(const MeshView &m, const int32_t *cells, int64_t n, ColorHost &out); // cells == nullptr: all n = n_cells cells
 int patch_plan(const MeshView &m, const Options &o, int leaf, int shrink, PatchHost &out); // leaf > 0: bisection leaves of that size (shrink is then ignored)
 std::vector<RowDesc> row_descs(const PatchHost &pp, const PatternView &p, int64_t &maxlen, int64_t &max_entries);
