@@ -188,6 +188,8 @@ const char *tb_version(void);
  * Added under 10, purely additive (no existing entry changes what it reads or writes): tb_ecg_*, tb_scrub_scale (pseudo-ECG).
  * Added under 10, purely additive: tb_newmark_predict / _stage / _correct, tb_hermite_interpolate (Newmark elastodynamics); tb_assemble_matrix accepts
  * the mass form of a 3-component field, which it used to refuse (scalar calls are unchanged).
+ * Added under 10, purely additive: tb_mg_set_p_transfer, tb_mg_level_plan, tb_mg_galerkin (p-multigrid); tb_mg_set_level accepts a TB_HEX27 field, which it used
+ * to refuse (first-order calls are unchanged).
  * A host binding compares tb_abi_revision() with the
  * TB_ABI_REVISION it was written against and refuses to run on a mismatch (julia/ThunderboltHIPBackend.jl does, in __init__) */
 #define TB_ABI_REVISION 10
@@ -790,19 +792,25 @@ int tb_heat_matrix_f32(tb_device *dev, int64_t nnz, const float *d_Mnz, const fl
 int tb_axpy_f32(tb_device *dev, int64_t n, double a, const float *d_x, float *d_y);
 int tb_cg_solve_f32(tb_pattern *pat, const float *d_Anz, const float *d_b, float *d_x, double rtol, double atol, int maxiter, int jacobi, int *iters, double *resnorm);
 
-/* ------------------------------------------------------------------ geometric multigrid preconditioner (h-levels, first-order hexahedra)
- * GMGPrecon of the reference (src/solver/linear/multigrid.jl, ext/ThunderboltFerriteMultigridExt.jl, docs/src/literate-howto/multigrid.jl) on the
+/* ------------------------------------------------------------------ multigrid preconditioner (h-levels of first-order hexahedra, one p-level on top)
+ * GMGPrecon, PMGPrecon and ChainedMGPrecon of the reference (src/solver/linear/multigrid.jl, ext/ThunderboltFerriteMultigridExt.jl, docs/src/literate-howto/multigrid.jl) on the
  * nested grids of uniform refinement: Galerkin coarse operators A_c = PᵀA_fP rebuilt from every new matrix, one V(degree, degree) cycle with the
  * Chebyshev–Jacobi smoother of multigrid.jl:28-33 on [λmax/interval_ratio, λmax] of D⁻¹A, an explicit inverse on the coarsest level.  A symmetric
- * positive-definite operator, so plain PCG applies.  Out of scope and refused: p-levels (PMGPrecon / ChainedMGPrecon), second-order fields,
- * tetrahedra, W- and F-cycles, other smoothers, GMRES, several ranks.
+ * positive-definite operator, so plain PCG applies.  The finest level may carry a second-order (TB_HEX27) field: one p-level joins it to the first-order field on the
+ * same cells (PMGPrecon; with h-levels below: ChainedMGPrecon).  Out of scope and refused: orders above 2, more than one p-level, tetrahedra, W- and
+ * F-cycles, other smoothers, GMRES, several ranks.
  *   tb_mg_create        an empty hierarchy of n_levels ≥ 2 levels; level 0 is the coarsest, level n_levels − 1 the one the solve runs on
- *   tb_mg_set_level     the pattern of a level: the allocate_matrix pattern of a first-order field (1 or 3 components) on that level's grid; the
- *                       pattern (and its mesh) must outlive the hierarchy
+ *   tb_mg_set_level     the pattern of a level: the allocate_matrix pattern of a first-order field (1 or 3 components) on that level's grid — on the
+ *                       finest level also of a TB_HEX27 field on TB_HEX8 geometry; the pattern (and its mesh) must outlive the hierarchy
  *   tb_mg_set_transfer  the parent nodes of every node of level fine_level in level fine_level − 1 (host arrays, 0-based, parent_ptr of n_fine_nodes + 1
  *                       entries): 1 parent for a kept node — itself: the coarse nodes are a prefix of the fine ones —, 2 for an edge centre, 4 for
  *                       a face centre, 8 for a cell centre.  A fine dof interpolates the same component of its parents with weight 1/#parents.  Both
- *                       levels must be set; a parent list that does not fit them is TB_ERR_BAD_ARG.
+ *                       levels must be set; a parent list that does not fit them is TB_ERR_BAD_ARG, a second-order level TB_ERR_UNSUPPORTED.
+ *   tb_mg_set_p_transfer  the p-level: level fine_level carries a TB_HEX27 field, level fine_level − 1 a TB_HEX8 field on the same cells (same device,
+ *                       n_cells and ncomp), fine_level = n_levels − 1.  P follows from the two cell-dof tables: the Q2 node of tensor index
+ *                       (t_x, t_y, t_z) — the node order of TB_HEX27: vertices, edges, faces, volume — takes the mean of the 1, 2, 4 or 8 vertices its
+ *                       index selects, on any trilinear geometry; any dof numbering on either level.  A coarse dof gathers at most 27 fine dofs, a
+ *                       fine dof at most 8 parents, as on an h-level.  Anything else is TB_ERR_BAD_ARG or TB_ERR_UNSUPPORTED with the condition named.
  *   tb_mg_set_prescribed  flags of the Dirichlet dofs of the finest level (device, one byte per dof, as tb_apply_zero_csr takes them; NULL: none).  A
  *                       coarse dof is prescribed iff the fine dof it coincides with is; rows of P at prescribed fine dofs and columns at prescribed
  *                       coarse dofs are dropped — elimination on the free dofs, for matrices as tb_apply_zero_csr leaves them.  Copies the flags.
@@ -815,12 +823,20 @@ int tb_cg_solve_f32(tb_pattern *pat, const float *d_Anz, const float *d_b, float
  *   tb_mg_apply         z = M⁻¹ r, one V cycle from z = 0; enqueues only (fits inside tb_graph_begin / tb_graph_end); z = 0 at prescribed dofs
  *   tb_mg_level_matrix / tb_mg_level_lambda_max / tb_mg_prolong (x_f = P x_c) / tb_mg_restrict (r_c = Pᵀ r_f): what the cycle is made of, for tests
  *                       and callers that inspect levels; prolong and restrict need the plans, i.e. one tb_mg_setup
+ *   tb_mg_level_plan    which Galerkin plan the transfer below fine_level uses and how many terms it recorded (after one tb_mg_setup): blocked = 1
+ *                       when both patterns are CSRs of 3 × 3 blocks (3 components, node-blocked numbering) — one term per (coarse block, fine block)
+ *                       pair, evaluated by k_mg_galerkin_b3; the p-level takes it where it applies — and 0 for the per-dof plan, one term per
+ *                       (coarse non-zero, fine non-zero) pair.  A term is 4 bytes and names a fine non-zero (block) in 29 bits: the per-dof plan
+ *                       refuses 2²⁹ fine non-zeros or more (TB_ERR_UNSUPPORTED), the blocked one reaches nine times as far.
+ *   tb_mg_galerkin      the product A_{fine_level − 1} = Pᵀ A_{fine_level} P alone, from the level matrices of the latest tb_mg_setup (which it leaves as
+ *                       they are: the same plan, the same bits); enqueues only.  What a measurement of the Galerkin kernels times.
  *   tb_pcg_solve_mg     tb_pcg_solve with z = M⁻¹ r by tb_mg_apply (KrylovMGSolver with CG): same stopping rule, tb_solver_last_tolerance and
  *                       non-finite behaviour; pat and d_Anz are the finest level's and the array of the latest tb_mg_setup */
 typedef struct tb_mg tb_mg;
 int tb_mg_create(tb_device *dev, int n_levels, tb_mg **out);
 int tb_mg_set_level(tb_mg *mg, int level, tb_pattern *pat);
 int tb_mg_set_transfer(tb_mg *mg, int fine_level, int64_t n_fine_nodes, const int64_t *parent_ptr, const int32_t *parent_idx);
+int tb_mg_set_p_transfer(tb_mg *mg, int fine_level);
 int tb_mg_set_prescribed(tb_mg *mg, const uint8_t *d_prescribed_fine);
 int tb_mg_setup(tb_mg *mg, const double *d_Anz_fine, int degree, double interval_ratio);
 int tb_mg_apply(tb_mg *mg, const double *d_r, double *d_z);
@@ -828,6 +844,8 @@ int tb_mg_level_matrix(tb_mg *mg, int level, const double **d_nzval);
 int tb_mg_level_lambda_max(tb_mg *mg, int level, double *lmax);
 int tb_mg_prolong(tb_mg *mg, int fine_level, const double *d_xc, double *d_xf);
 int tb_mg_restrict(tb_mg *mg, int fine_level, const double *d_rf, double *d_rc);
+int tb_mg_level_plan(tb_mg *mg, int fine_level, int *blocked, int64_t *n_terms);
+int tb_mg_galerkin(tb_mg *mg, int fine_level);
 int tb_mg_destroy(tb_mg *mg);
 int tb_pcg_solve_mg(tb_pattern *pat, const double *d_Anz, const double *d_b, double *d_x, double rtol, double atol, int maxiter, tb_mg *mg, int *iters,
                     double *resnorm);

@@ -701,13 +701,15 @@ l1gs_apply!(z::HIPVector{Float64}, A::HIPSparseMatrixCSR{Float64}, r::HIPVector{
 # `patterns`: the tb_pattern handles of the levels, coarsest first (DeviceDofHandlers of the hierarchy's grids with the fine handler's field); `parents`:
 # per refinement (parent_ptr::Vector{Int64}, parent_idx::Vector{Int32}), 0-based, of the fine nodes in the next coarser grid; `prescribed`: the flag
 # vector tb_apply_zero_csr takes (device pointer, or C_NULL).  `setup!` is the numeric phase of every new Jacobian.
+# `p_level = true` (PMGPrecon / ChainedMGPrecon): the last pattern carries a second-order field, the one before it the first-order field on the same
+# grid; `parents` then lists the h-levels below only, and the top transfer follows from the two dof tables (tb_mg_set_p_transfer).
 mutable struct HIPGMGPrecon
     handle::Ptr{Cvoid}
     degree::Int
     interval_ratio::Float64
 end
 function HIPGMGPrecon(dev::MI355XDevice, patterns::Vector{Ptr{Cvoid}}, n_nodes::Vector{Int64}, parents::Vector{Tuple{Vector{Int64},Vector{Int32}}};
-                      prescribed::Ptr{UInt8} = Ptr{UInt8}(C_NULL), degree = 2, interval_ratio = 4.0)
+                      prescribed::Ptr{UInt8} = Ptr{UInt8}(C_NULL), degree = 2, interval_ratio = 4.0, p_level::Bool = false)
     h = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:tb_mg_create, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ref{Ptr{Cvoid}}), dev.handle, length(patterns), h))
     for (l, p) in enumerate(patterns)
@@ -716,6 +718,7 @@ function HIPGMGPrecon(dev::MI355XDevice, patterns::Vector{Ptr{Cvoid}}, n_nodes::
     for (l, (pptr, pidx)) in enumerate(parents)
         check(ccall((:tb_mg_set_transfer, libtbhip), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Int64}, Ptr{Int32}), h[], l, n_nodes[l + 1], pptr, pidx))
     end
+    p_level && check(ccall((:tb_mg_set_p_transfer, libtbhip), Cint, (Ptr{Cvoid}, Cint), h[], length(patterns) - 1))
     check(ccall((:tb_mg_set_prescribed, libtbhip), Cint, (Ptr{Cvoid}, Ptr{UInt8}), h[], prescribed))
     mg = HIPGMGPrecon(h[], degree, interval_ratio)
     finalizer(m -> ccall((:tb_mg_destroy, libtbhip), Cint, (Ptr{Cvoid},), m.handle), mg)
@@ -739,6 +742,14 @@ function mg_lambda_max(mg::HIPGMGPrecon, level::Integer)
     check(ccall((:tb_mg_level_lambda_max, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ref{Cdouble}), mg.handle, level, r))
     return r[]
 end
+# (blocked, n_terms) of the Galerkin plan below fine_level: blocked = one term per pair of 3 × 3 blocks
+function mg_level_plan(mg::HIPGMGPrecon, fine_level::Integer)
+    b = Ref{Cint}(0); n = Ref{Int64}(0)
+    check(ccall((:tb_mg_level_plan, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ref{Cint}, Ref{Int64}), mg.handle, fine_level, b, n))
+    return b[] != 0, n[]
+end
+# the Galerkin product below fine_level alone (what the set-up does per level), for measurements
+mg_galerkin!(mg::HIPGMGPrecon, fine_level::Integer) = check(ccall((:tb_mg_galerkin, libtbhip), Cint, (Ptr{Cvoid}, Cint), mg.handle, fine_level))
 # KrylovMGSolver(CG, mg): rebuild the numeric phase from the matrix, then CG with one cycle per iteration
 function pcg_mg!(x::HIPVector{Float64}, A::HIPSparseMatrixCSR{Float64}, b::HIPVector{Float64}, mg::HIPGMGPrecon; rtol = 1e-5, atol = 1e-6, maxiter = 1000, setup = true)
     setup && setup!(mg, A)

@@ -208,6 +208,7 @@ SIGNATURES = {
     "tb_mg_create": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
     "tb_mg_set_level": (C.c_int, [vp, C.c_int, vp]),
     "tb_mg_set_transfer": (C.c_int, [vp, C.c_int, C.c_int64, c_i64p, c_i32p]),
+    "tb_mg_set_p_transfer": (C.c_int, [vp, C.c_int]),
     "tb_mg_set_prescribed": (C.c_int, [vp, vp]),
     "tb_mg_setup": (C.c_int, [vp, vp, C.c_int, C.c_double]),
     "tb_mg_apply": (C.c_int, [vp, vp, vp]),
@@ -215,6 +216,8 @@ SIGNATURES = {
     "tb_mg_level_lambda_max": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double)]),
     "tb_mg_prolong": (C.c_int, [vp, C.c_int, vp, vp]),
     "tb_mg_restrict": (C.c_int, [vp, C.c_int, vp, vp]),
+    "tb_mg_level_plan": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "tb_mg_galerkin": (C.c_int, [vp, C.c_int]),
     "tb_mg_destroy": (C.c_int, [vp]),
     "tb_pcg_solve_mg": (C.c_int, [vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "tb_host_generate_grid_hex": (C.c_int, [C.c_int, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_i32p]),

@@ -1,6 +1,8 @@
-// tb_multigrid.hip — geometric multigrid preconditioner on nested first-order hexahedral grids (GMGPrecon of the reference: src/solver/linear/multigrid.jl,
-// ext/ThunderboltFerriteMultigridExt.jl).  The plans come from tb_mg_planners.cpp (P row-wise, Pᵀ row-wise, the gather plan of PᵀAP); this file holds
-// the hierarchy object, the numeric Galerkin kernel, the transfers, the Chebyshev–Jacobi smoother step, the coarsest inverse and the V-cycle driver.
+// tb_multigrid.hip — multigrid preconditioner on hexahedral grids (GMGPrecon, PMGPrecon and ChainedMGPrecon of the reference: src/solver/linear/multigrid.jl,
+// ext/ThunderboltFerriteMultigridExt.jl): h-levels of first-order fields on nested grids and, at the top, one p-level from a second-order field to the
+// first-order field on the same cells.  The plans come from tb_mg_planners.cpp (P row-wise, Pᵀ row-wise, the gather plan of PᵀAP, per dof or per
+// 3 × 3 block); this file holds the hierarchy object, the two numeric Galerkin kernels, the transfers, the Chebyshev–Jacobi smoother step, the
+// coarsest inverse and the V-cycle driver.
 // Every sum has one recorded order and no kernel uses an atomic: two setups, and two applications, give the same bits.
 #include <hip/hip_runtime.h>
 
@@ -30,7 +32,9 @@ struct MgLevel {
     // to the level below (levels ≥ 1)
     std::vector<int64_t> parent_ptr;
     std::vector<int32_t> parent_idx;
-    bool has_transfer = false;
+    bool has_transfer = false, p_transfer = false; // p_transfer: the level below carries the first-order field on the same cells (tb_mg_set_p_transfer)
+    bool blocked = false;           // the Galerkin plan to the level below is per 3 × 3 block (k_mg_galerkin_b3)
+    int32_t *d_brow = nullptr;      // block row of every 3 × 3 block of the level's pattern (levels on either side of a blocked plan)
     int64_t *d_pptr = nullptr, *d_rptr = nullptr, *d_gptr = nullptr, *d_cdiag = nullptr;
     int32_t *d_pcol = nullptr, *d_rcol = nullptr;
     uint8_t *d_pexp = nullptr, *d_rexp = nullptr;
@@ -72,6 +76,66 @@ k_mg_galerkin(int64_t cnnz, const int64_t *__restrict__ gptr, const uint32_t *__
 #pragma unroll
     for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 16);
     if (sub == 0) Ac[k] = s;
+}
+
+// The same product on CSRs of 3 × 3 blocks: 16 lanes share a coarse block, a term names a fine block and moves its nine values — three 24-byte runs
+// in the rows 3i, 3i + 1, 3i + 2, whose lengths are equal, so the block offset of a row triple is rowptr[3i] / 9 as in k_spmv_b3.  Nine lane sums in term
+// order, the fixed butterfly, nine stores by the lanes 0, 1, 2 (a row each).  FLAGS: prescribed dofs may cut through a block; an entry enters only when
+// its fine row and column and its coarse row and column are free — selected, not multiplied by 0: whatever a dropped position holds stays out.
+template <bool FLAGS>
+__global__ void __launch_bounds__(256)
+k_mg_galerkin_b3(int64_t ncb, const int64_t *__restrict__ gptr, const uint32_t *__restrict__ terms, const int32_t *__restrict__ fbrow, const int32_t *__restrict__ fbcol,
+                 const int64_t *__restrict__ frowptr, const double *__restrict__ Af, const uint8_t *__restrict__ fpresc, const int32_t *__restrict__ cbrow,
+                 const int32_t *__restrict__ cbcol, const int64_t *__restrict__ crowptr, const uint8_t *__restrict__ cpresc, double *__restrict__ Ac)
+{
+    const int64_t kb = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    if (kb >= ncb) return; // (the 16 lanes of a group leave together)
+    const int sub = threadIdx.x & 15;
+    const int64_t I = cbrow[kb];
+    unsigned keep = 0x1ffu; // bit 3a + b: entry (a, b) of the block
+    if (FLAGS) {
+        const int64_t J = cbcol[kb];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            if (cpresc[3 * I + a]) keep &= ~(7u << (3 * a));
+            if (cpresc[3 * J + a]) keep &= ~(0x49u << a);
+        }
+    }
+    double s[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int64_t q = gptr[kb] + sub, hi = gptr[kb + 1]; q < hi; q += 16) {
+        const uint32_t t = terms[q];
+        const int64_t B = t & ((1u << mgplan::TERM_BITS) - 1u);
+        const double w = pow2_neg(t >> mgplan::TERM_BITS);
+        const int64_t i = fbrow[B], k0 = frowptr[3 * i], len = frowptr[3 * i + 1] - k0;
+        const double *p = Af + k0 + 3 * (B - k0 / 9);
+        unsigned m = keep;
+        if (FLAGS) {
+            const int64_t j = fbcol[B];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                if (fpresc[3 * i + a]) m &= ~(7u << (3 * a));
+                if (fpresc[3 * j + a]) m &= ~(0x49u << a);
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int b = 0; b < 3; ++b) {
+                const double v = w * p[a * len + b];
+                s[3 * a + b] += (!FLAGS || ((m >> (3 * a + b)) & 1u)) ? v : 0.0;
+            }
+    }
+#pragma unroll
+    for (int e = 0; e < 9; ++e)
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) s[e] += __shfl_xor(s[e], o, 16);
+    if (sub < 3) {
+        const int64_t K0 = crowptr[3 * I], clen = crowptr[3 * I + 1] - K0;
+        double *out = Ac + K0 + sub * clen + 3 * (kb - K0 / 9);
+        out[0] = sub == 0 ? s[0] : sub == 1 ? s[3] : s[6];
+        out[1] = sub == 0 ? s[1] : sub == 1 ? s[4] : s[7];
+        out[2] = sub == 0 ? s[2] : sub == 1 ? s[5] : s[8];
+    }
 }
 
 // one workgroup: the diagonal of every prescribed dof of a coarse level becomes the mean |diagonal| of its free dofs (fixed order: strided lane sums, LDS tree)
@@ -121,7 +185,8 @@ k_mg_cheb(int64_t n, double c1, double c2, const double *__restrict__ dinv, cons
     }
 }
 
-// r_c = Pᵀ(r − w) (w NULL: Pᵀ r): one thread per coarse dof gathers its fine dofs (at most 27 per component)
+// r_c = Pᵀ(r − w) (w NULL: Pᵀ r): one thread per coarse dof gathers its fine dofs (at most 27 on either kind of level: the nodes of the 8 children
+// around a coarse node, or the Q2 nodes of the 8 cells around a vertex)
 __global__ void __launch_bounds__(256)
 k_mg_restrict(int64_t nc, const int64_t *__restrict__ rptr, const int32_t *__restrict__ rcol, const uint8_t *__restrict__ rexp, const double *__restrict__ r,
               const double *__restrict__ w, double *__restrict__ rc)
@@ -136,7 +201,8 @@ k_mg_restrict(int64_t nc, const int64_t *__restrict__ rptr, const int32_t *__res
     rc[I] = s;
 }
 
-// x_f (+)= P x_c: one thread per fine dof gathers its at most 8 parents
+// x_f (+)= P x_c: one thread per fine dof gathers its at most 8 parents (h-level: the vertices of the parent cell's edge, face or cell the node lies on;
+// p-level: the vertices of the edge, face or cell the Q2 node belongs to)
 template <bool ADD>
 __global__ void __launch_bounds__(256)
 k_mg_prolong(int64_t nf, const int64_t *__restrict__ pptr, const int32_t *__restrict__ pcol, const uint8_t *__restrict__ pexp, const double *__restrict__ xc,
@@ -202,10 +268,11 @@ static inline unsigned blocks_of(int64_t n, int bs) { return (unsigned)std::max<
 static void free_plans(tb_mg *mg)
 {
     for (MgLevel &L : mg->lv) {
-        void *ptrs[] = {L.d_A, L.d_vec, L.d_presc, L.d_pptr, L.d_rptr, L.d_gptr, L.d_cdiag, L.d_pcol, L.d_rcol, L.d_pexp, L.d_rexp, L.d_gterms};
+        void *ptrs[] = {L.d_A, L.d_vec, L.d_presc, L.d_pptr, L.d_rptr, L.d_gptr, L.d_cdiag, L.d_pcol, L.d_rcol, L.d_pexp, L.d_rexp, L.d_gterms, L.d_brow};
         for (void *p : ptrs) if (p) (void)hipFree(p);
         L.d_A = nullptr; L.d_vec = nullptr; L.d_presc = nullptr; L.d_pptr = L.d_rptr = L.d_gptr = L.d_cdiag = nullptr;
-        L.d_pcol = L.d_rcol = nullptr; L.d_pexp = L.d_rexp = nullptr; L.d_gterms = nullptr;
+        L.d_pcol = L.d_rcol = nullptr; L.d_pexp = L.d_rexp = nullptr; L.d_gterms = nullptr; L.d_brow = nullptr;
+        L.blocked = false; L.n_terms = 0;
         L.A = nullptr;
     }
     if (mg->d_cinv) (void)hipFree(mg->d_cinv);
@@ -216,7 +283,7 @@ static void free_plans(tb_mg *mg)
 static mgplan::LevelView view_of(const tb_pattern *p)
 {
     const tb_mesh *m = p->mesh;
-    return mgplan::LevelView{m->n_nodes, m->n_cells, m->ndofs, m->nverts, m->ncomp, m->h_conn.data(), m->h_cell_dofs.data(), p->h_rowptr.data(), p->h_colidx.data()};
+    return mgplan::LevelView{m->n_nodes, m->n_cells, m->ndofs, m->nverts, m->ncomp, m->h_conn.data(), m->h_cell_dofs.data(), p->h_rowptr.data(), p->h_colidx.data(), m->nb};
 }
 
 // symbolic phase: transfers, Galerkin plans, level storage, the SpMV plan of every level
@@ -227,10 +294,15 @@ static int build_plans(tb_mg *mg)
     const int nl = (int)mg->lv.size();
     for (int l = 0; l < nl; ++l) {
         TB_REQUIRE(mg->lv[l].pat, "tb_mg_setup: level %d has no pattern (tb_mg_set_level)", l);
-        TB_REQUIRE(l == 0 || mg->lv[l].has_transfer, "tb_mg_setup: level %d has no transfer to level %d (tb_mg_set_transfer)", l, l - 1);
+        TB_REQUIRE(l == 0 || mg->lv[l].has_transfer, "tb_mg_setup: level %d has no transfer to level %d (tb_mg_set_transfer, tb_mg_set_p_transfer)", l, l - 1);
+        if (mg->lv[l].pat->mesh->field_kind == TB_HEX27)
+            TB_REQUIRE(l == nl - 1 && mg->lv[l].p_transfer, "tb_mg_setup: level %d carries a second-order field: it must be the finest level, with a p-transfer below it (tb_mg_set_p_transfer)", l);
+        else
+            TB_REQUIRE(l == 0 || !mg->lv[l].p_transfer, "tb_mg_setup: level %d has a p-transfer below it but carries a first-order field", l);
     }
     if (mg->lv[0].pat->n_rows > MG_COARSEST_MAX) {
-        set_error("tb_mg_setup: the coarsest level has %lld dofs; its dense inverse takes at most %d - add a level", (long long)mg->lv[0].pat->n_rows, MG_COARSEST_MAX);
+        set_error("tb_mg_setup: the coarsest level has %lld dofs; its dense inverse takes at most %d - add a level%s", (long long)mg->lv[0].pat->n_rows, MG_COARSEST_MAX,
+                  nl == 2 && mg->lv[1].p_transfer ? " (h-levels below the p-level: ChainedMGPrecon(PMGPrecon(), GMGPrecon(gh)))" : "");
         return TB_ERR_UNSUPPORTED;
     }
     PlanTimer timer("multigrid");
@@ -241,15 +313,30 @@ static int build_plans(tb_mg *mg)
         if (l > 0) {
             MgLevel &Cl = mg->lv[l - 1];
             const mgplan::LevelView fv = view_of(L.pat), cv = view_of(Cl.pat);
-            TB_REQUIRE((int64_t)L.parent_ptr.size() == fv.n_nodes + 1, "tb_mg_setup: the transfer of level %d lists %lld nodes, its pattern's grid has %lld", l,
-                       (long long)L.parent_ptr.size() - 1, (long long)fv.n_nodes);
             const uint8_t *flags = L.h_presc.empty() ? nullptr : L.h_presc.data();
             mgplan::Transfer t;
             mgplan::Galerkin g;
-            TB_TRY(mgplan::build_transfer(fv, cv, L.parent_ptr.data(), L.parent_idx.data(), flags, t));
+            if (L.p_transfer) TB_TRY(mgplan::build_p_transfer(fv, cv, flags, t));
+            else {
+                TB_REQUIRE((int64_t)L.parent_ptr.size() == fv.n_nodes + 1, "tb_mg_setup: the transfer of level %d lists %lld nodes, its pattern's grid has %lld", l,
+                           (long long)L.parent_ptr.size() - 1, (long long)fv.n_nodes);
+                TB_TRY(mgplan::build_transfer(fv, cv, L.parent_ptr.data(), L.parent_idx.data(), flags, t));
+            }
             timer.lap("transfer");
-            TB_TRY(mgplan::build_galerkin(fv, cv, t, flags, g));
+            // The blocked plan where both patterns are CSRs of 3 × 3 blocks (what the SpMV's examination decides) and P moves node triples: the
+            // p-level, whose fine matrix is the one that outgrows the per-dof term word.  h-levels stay on the per-dof plan.  TB_MG_GALERKIN=dof
+            // keeps the p-level there too (measurements).
+            TB_TRY(spmv_plans(L.pat));
+            TB_TRY(spmv_plans(Cl.pat));
+            const bool dof_only = tune_env("TB_MG_GALERKIN") && !strcmp(tune_env("TB_MG_GALERKIN"), "dof"); // (read per hierarchy: one process times both)
+            L.blocked = L.p_transfer && !dof_only && L.pat->b3 > 0 && Cl.pat->b3 > 0 && mgplan::node_blocked(t);
+            if (L.blocked) TB_TRY(mgplan::build_galerkin_blocked(fv, cv, t, g));
+            else TB_TRY(mgplan::build_galerkin(fv, cv, t, flags, g));
             timer.lap("galerkin plan");
+            if (L.blocked) {
+                TB_TRY(upload(dev, g.fine_brow, &L.d_brow));
+                TB_TRY(upload(dev, g.coarse_brow, &Cl.d_brow));
+            }
             if (flags) Cl.h_presc = t.coarse_prescribed; else Cl.h_presc.clear();
             L.n_terms = (int64_t)g.terms.size();
             TB_TRY(upload_all(dev, t.p_ptr, &L.d_pptr, t.p_col, &L.d_pcol, t.p_exp, &L.d_pexp, t.r_ptr, &L.d_rptr, t.r_col, &L.d_rcol, t.r_exp, &L.d_rexp,
@@ -266,6 +353,24 @@ static int build_plans(tb_mg *mg)
     if (!mg->d_scal) TB_HIP(hipMalloc((void **)&mg->d_scal, 16 * sizeof(double)));
     mg->planned = true;
     return TB_OK;
+}
+
+// A_{l−1} = Pᵀ A_l P by the plan of level l (fine_level), then the diagonal of the prescribed coarse dofs; enqueues only
+static void launch_galerkin(tb_mg *mg, int fine_level)
+{
+    tb_device *dev = mg->dev;
+    MgLevel &U = mg->lv[fine_level], &L = mg->lv[fine_level - 1];
+    if (U.blocked) {
+        const int64_t ncb = L.nnz / 9;
+        if (U.d_presc)
+            hipLaunchKernelGGL(k_mg_galerkin_b3<true>, dim3(blocks_of(ncb * 16, 256)), dim3(256), 0, dev->stream, ncb, U.d_gptr, U.d_gterms, U.d_brow, U.pat->d_bcol,
+                               U.pat->d_rowptr, U.A, U.d_presc, L.d_brow, L.pat->d_bcol, L.pat->d_rowptr, L.d_presc, L.d_A);
+        else
+            hipLaunchKernelGGL(k_mg_galerkin_b3<false>, dim3(blocks_of(ncb * 16, 256)), dim3(256), 0, dev->stream, ncb, U.d_gptr, U.d_gterms, U.d_brow, U.pat->d_bcol,
+                               U.pat->d_rowptr, U.A, (const uint8_t *)nullptr, L.d_brow, L.pat->d_bcol, L.pat->d_rowptr, (const uint8_t *)nullptr, L.d_A);
+    } else
+        hipLaunchKernelGGL(k_mg_galerkin, dim3(blocks_of(L.nnz * 16, 256)), dim3(256), 0, dev->stream, L.nnz, U.d_gptr, U.d_gterms, U.A, L.d_A);
+    if (L.d_presc) hipLaunchKernelGGL(k_mg_fill_diag, dim3(1), dim3(1024), 0, dev->stream, L.n, U.d_cdiag, L.d_presc, L.d_A);
 }
 
 static int smooth(tb_mg *mg, int l, const double *r, double *x, bool from_zero)
@@ -349,8 +454,8 @@ int tb_mg_set_level(tb_mg *mg, int level, tb_pattern *pat)
     TB_REQUIRE(mg && pat, "tb_mg_set_level: NULL argument");
     TB_REQUIRE(level >= 0 && level < (int)mg->lv.size(), "tb_mg_set_level: level %d of %d", level, (int)mg->lv.size());
     TB_REQUIRE(pat->mesh && pat->mesh->dev == mg->dev, "tb_mg_set_level: the pattern lives on another device");
-    if (pat->mesh->geom_kind != TB_HEX8 || pat->mesh->field_kind != TB_HEX8) {
-        set_error("tb_mg_set_level: the multigrid covers first-order fields on hexahedra only (no p-levels, no second-order fields, no tetrahedra)");
+    if (pat->mesh->geom_kind != TB_HEX8 || (pat->mesh->field_kind != TB_HEX8 && pat->mesh->field_kind != TB_HEX27)) {
+        set_error("tb_mg_set_level: the multigrid covers first-order fields on hexahedra and a second-order field on the finest level (no tetrahedra)");
         return TB_ERR_UNSUPPORTED;
     }
     TB_HIP(hipSetDevice(mg->dev->id));
@@ -365,6 +470,11 @@ int tb_mg_set_transfer(tb_mg *mg, int fine_level, int64_t n_fine_nodes, const in
     TB_REQUIRE(fine_level >= 1 && fine_level < (int)mg->lv.size(), "tb_mg_set_transfer: fine_level %d of 1..%d", fine_level, (int)mg->lv.size() - 1);
     MgLevel &L = mg->lv[fine_level], &Cl = mg->lv[fine_level - 1];
     TB_REQUIRE(L.pat && Cl.pat, "tb_mg_set_transfer: set the patterns of levels %d and %d first (tb_mg_set_level)", fine_level, fine_level - 1);
+    if (L.pat->mesh->field_kind != TB_HEX8 || Cl.pat->mesh->field_kind != TB_HEX8) {
+        set_error("tb_mg_set_transfer: an h-transfer joins two first-order fields; level %d carries a second-order field (tb_mg_set_p_transfer joins it to the first-order field on its grid)",
+                  L.pat->mesh->field_kind != TB_HEX8 ? fine_level : fine_level - 1);
+        return TB_ERR_UNSUPPORTED;
+    }
     TB_REQUIRE(L.pat->mesh->ncomp == Cl.pat->mesh->ncomp, "tb_mg_set_transfer: the levels carry %d and %d components", L.pat->mesh->ncomp, Cl.pat->mesh->ncomp);
     TB_REQUIRE(n_fine_nodes == L.pat->mesh->n_nodes, "tb_mg_set_transfer: %lld fine nodes, but the grid of level %d has %lld: the pattern does not match the transfer",
                (long long)n_fine_nodes, fine_level, (long long)L.pat->mesh->n_nodes);
@@ -384,6 +494,46 @@ int tb_mg_set_transfer(tb_mg *mg, int fine_level, int64_t n_fine_nodes, const in
     L.parent_ptr.assign(parent_ptr, parent_ptr + n_fine_nodes + 1);
     L.parent_idx.assign(parent_idx, parent_idx + parent_ptr[n_fine_nodes]);
     L.has_transfer = true;
+    L.p_transfer = false;
+    return TB_OK;
+}
+
+int tb_mg_set_p_transfer(tb_mg *mg, int fine_level)
+{
+    TB_REQUIRE(mg, "tb_mg_set_p_transfer: NULL argument");
+    const int nl = (int)mg->lv.size();
+    TB_REQUIRE(fine_level >= 1 && fine_level < nl, "tb_mg_set_p_transfer: fine_level %d of 1..%d", fine_level, nl - 1);
+    MgLevel &L = mg->lv[fine_level], &Cl = mg->lv[fine_level - 1];
+    TB_REQUIRE(L.pat && Cl.pat, "tb_mg_set_p_transfer: set the patterns of levels %d and %d first (tb_mg_set_level)", fine_level, fine_level - 1);
+    const tb_mesh *f = L.pat->mesh, *c = Cl.pat->mesh;
+    if (f->field_kind != TB_HEX27 || c->field_kind != TB_HEX8) {
+        set_error("tb_mg_set_p_transfer: a p-transfer joins a second-order field (level %d) to a first-order field (level %d) on hexahedra; the levels carry field kinds %d and %d",
+                  fine_level, fine_level - 1, f->field_kind, c->field_kind);
+        return TB_ERR_UNSUPPORTED;
+    }
+    if (fine_level != nl - 1) {
+        set_error("tb_mg_set_p_transfer: one p-level, from order 2 to order 1, at the top of the hierarchy: fine_level must be %d (got %d)", nl - 1, fine_level);
+        return TB_ERR_UNSUPPORTED;
+    }
+    TB_REQUIRE(f->n_cells == c->n_cells, "tb_mg_set_p_transfer: levels %d and %d have %lld and %lld cells (a p-transfer joins two fields on the same cells)", fine_level,
+               fine_level - 1, (long long)f->n_cells, (long long)c->n_cells);
+    TB_REQUIRE(f->ncomp == c->ncomp, "tb_mg_set_p_transfer: the levels carry %d and %d components", f->ncomp, c->ncomp);
+    TB_HIP(hipSetDevice(mg->dev->id));
+    free_plans(mg);
+    L.parent_ptr.clear();
+    L.parent_idx.clear();
+    L.has_transfer = true;
+    L.p_transfer = true;
+    return TB_OK;
+}
+
+int tb_mg_level_plan(tb_mg *mg, int fine_level, int *blocked, int64_t *n_terms)
+{
+    TB_REQUIRE(mg && blocked && n_terms, "tb_mg_level_plan: NULL argument");
+    TB_REQUIRE(fine_level >= 1 && fine_level < (int)mg->lv.size(), "tb_mg_level_plan: fine_level %d of 1..%d", fine_level, (int)mg->lv.size() - 1);
+    TB_REQUIRE(mg->planned, "tb_mg_level_plan: the Galerkin products are planned by tb_mg_setup");
+    *blocked = mg->lv[fine_level].blocked ? 1 : 0;
+    *n_terms = mg->lv[fine_level].n_terms;
     return TB_OK;
 }
 
@@ -430,9 +580,7 @@ int tb_mg_setup(tb_mg *mg, const double *d_Anz_fine, int degree, double interval
     for (int l = nl - 1; l >= 0; --l) {
         MgLevel &L = mg->lv[l];
         if (l < nl - 1) { // A_l = Pᵀ A_{l+1} P
-            MgLevel &U = mg->lv[l + 1];
-            hipLaunchKernelGGL(k_mg_galerkin, dim3(blocks_of(L.nnz * 16, 256)), dim3(256), 0, dev->stream, L.nnz, U.d_gptr, U.d_gterms, U.A, L.d_A);
-            if (L.d_presc) hipLaunchKernelGGL(k_mg_fill_diag, dim3(1), dim3(1024), 0, dev->stream, L.n, U.d_cdiag, L.d_presc, L.d_A);
+            launch_galerkin(mg, l + 1);
             L.A = L.d_A;
         }
         if (l == 0) break;
@@ -463,6 +611,17 @@ int tb_mg_level_matrix(tb_mg *mg, int level, const double **d_nzval)
     TB_REQUIRE(level >= 0 && level < (int)mg->lv.size(), "tb_mg_level_matrix: level %d of %d", level, (int)mg->lv.size());
     TB_REQUIRE(mg->ready, "tb_mg_level_matrix: no numeric setup yet (tb_mg_setup)");
     *d_nzval = mg->lv[level].A;
+    return TB_OK;
+}
+
+int tb_mg_galerkin(tb_mg *mg, int fine_level)
+{
+    TB_REQUIRE(mg, "tb_mg_galerkin: NULL argument");
+    TB_REQUIRE(fine_level >= 1 && fine_level < (int)mg->lv.size(), "tb_mg_galerkin: fine_level %d of 1..%d", fine_level, (int)mg->lv.size() - 1);
+    TB_REQUIRE(mg->ready, "tb_mg_galerkin: no numeric setup yet (tb_mg_setup)");
+    TB_HIP(hipSetDevice(mg->dev->id));
+    launch_galerkin(mg, fine_level);
+    TB_HIP(hipGetLastError());
     return TB_OK;
 }
 

@@ -1,9 +1,10 @@
-"""Geometric multigrid preconditioner on the nested hexahedral grids of a GridHierarchy — GMGPrecon and KrylovMGSolver of the reference's multigrid
-extension (src/solver/linear/multigrid.jl, ext/ThunderboltFerriteMultigridExt.jl, docs/src/literate-howto/multigrid.jl) over tb_mg_* of libtbhip.so:
-Galerkin coarse operators rebuilt from every new matrix, one V(degree, degree) cycle with a Chebyshev–Jacobi smoother, an explicit coarsest inverse.
+"""Multigrid preconditioner on hexahedral grids — GMGPrecon, PMGPrecon, ChainedMGPrecon and KrylovMGSolver of the reference's multigrid extension
+(src/solver/linear/multigrid.jl, ext/ThunderboltFerriteMultigridExt.jl, docs/src/literate-howto/multigrid.jl) over tb_mg_* of libtbhip.so: Galerkin
+coarse operators rebuilt from every new matrix, one V(degree, degree) cycle with a Chebyshev–Jacobi smoother, an explicit coarsest inverse.
 
-Covered: h-levels, first-order hexahedra, one field of 1 or 3 components on the whole grid, CG.  Refused with a message: PMGPrecon / ChainedMGPrecon
-and second-order fields, tetrahedra, GMRES, W- and F-cycles, other smoothers, hierarchies over several ranks, subdomain dof handlers."""
+Covered: h-levels of first-order hexahedra on the nested grids of a GridHierarchy (GMGPrecon); one p-level from a second-order field to the first-order
+field on the same grid (PMGPrecon), alone or on top of the h-levels (ChainedMGPrecon); one field of 1 or 3 components on the whole grid, CG.  Refused
+with a message: orders above 2, tetrahedra, GMRES, W- and F-cycles, other smoothers, hierarchies over several ranks, subdomain dof handlers."""
 import ctypes as C
 
 import numpy as np
@@ -22,10 +23,7 @@ class GMGPrecon:
     def __init__(self, gh, degree=2, interval_ratio=4.0, cycle="V", smoother="chebyshev"):
         if not isinstance(gh, GridHierarchy):
             raise TypeError("GMGPrecon: pass a GridHierarchy")
-        if cycle != "V":
-            raise NotImplementedError("GMGPrecon: V-cycles only (W- and F-cycles are out of scope)")
-        if smoother != "chebyshev":
-            raise NotImplementedError("GMGPrecon: the Chebyshev-Jacobi smoother only")
+        _check_cycle("GMGPrecon", cycle, smoother)
         self.gh, self.degree, self.interval_ratio = gh, int(degree), float(interval_ratio)
         self._materialized = {}
 
@@ -39,47 +37,101 @@ class GMGPrecon:
         return self._materialized[key][0]
 
 
-def PMGPrecon(*args, **kwargs):
-    raise NotImplementedError("PMGPrecon: p-levels are out of scope; GMGPrecon covers h-levels of first-order hexahedra")
+def _check_cycle(who, cycle, smoother):
+    if cycle != "V":
+        raise NotImplementedError("%s: V-cycles only (W- and F-cycles are out of scope)" % who)
+    if smoother != "chebyshev":
+        raise NotImplementedError("%s: the Chebyshev-Jacobi smoother only" % who)
 
 
-def ChainedMGPrecon(*args, **kwargs):
-    raise NotImplementedError("ChainedMGPrecon: p-levels are out of scope; GMGPrecon covers h-levels of first-order hexahedra")
+class PMGPrecon:
+    """PMGPrecon(degree=2, interval_ratio=4.0): the recipe of polynomial multigrid — a second-order field over the first-order field on the same grid.
+    Keyword-only, no grid hierarchy.  Alone it materialises two levels with the dense inverse on the first-order one (at most 1 024 first-order dofs);
+    ChainedMGPrecon puts the h-levels of a GMGPrecon below."""
+
+    def __init__(self, *args, degree=2, interval_ratio=4.0, cycle="V", smoother="chebyshev"):
+        if args:
+            raise NotImplementedError("PMGPrecon takes keywords only (degree, interval_ratio): p-levels need no grid hierarchy.  For h-levels below the "
+                                      "p-level pass ChainedMGPrecon(PMGPrecon(), GMGPrecon(gh))")
+        _check_cycle("PMGPrecon", cycle, smoother)
+        self.degree, self.interval_ratio = int(degree), float(interval_ratio)
+        self._materialized = {}
+
+    gh = None      # no h-levels (ChainedMGPrecon sets the hierarchy of its GMGPrecon)
+
+    def check(self, dh):
+        check_supported(self.gh, dh, order=2, who=type(self).__name__)
+
+    def materialize(self, pattern, ch=None):
+        key = (id(pattern), id(ch))
+        if key not in self._materialized:
+            self._materialized[key] = (MultigridHierarchy(pattern, self.gh, self.degree, self.interval_ratio, ch, p_level=True), pattern, ch)
+        return self._materialized[key][0]
 
 
-def check_supported(gh, dh):
-    """what the multigrid covers, checked on the host: raises for a DofHandler the hierarchy cannot serve"""
+class ChainedMGPrecon(PMGPrecon):
+    """ChainedMGPrecon(pmg, gmg): polynomial multigrid on the fine level with the geometric multigrid of `gmg` as its coarse solver — the h-levels of
+    gmg.gh with first-order fields, the caller's second-order field on gmg.gh.grids[-1] on top.  One degree and interval ratio serve all levels."""
+
+    def __init__(self, *args):
+        if len(args) != 2 or isinstance(args[0], GridHierarchy):
+            raise NotImplementedError("ChainedMGPrecon takes the two recipes it chains, not a grid hierarchy: ChainedMGPrecon(PMGPrecon(), GMGPrecon(gh)) "
+                                      "(p-levels on top of the h-levels of gh)")
+        pmg, gmg = args
+        if not (type(pmg) is PMGPrecon and isinstance(gmg, GMGPrecon)):
+            raise TypeError("ChainedMGPrecon(pmg, gmg): a PMGPrecon and a GMGPrecon, in this order")
+        if pmg.degree != gmg.degree:
+            raise ValueError("ChainedMGPrecon: the recipes disagree on degree (%d and %d); the cycle has one for all levels" % (pmg.degree, gmg.degree))
+        if pmg.interval_ratio != gmg.interval_ratio:
+            raise ValueError("ChainedMGPrecon: the recipes disagree on interval_ratio (%g and %g); the cycle has one for all levels" % (pmg.interval_ratio, gmg.interval_ratio))
+        self.pmg, self.gmg, self.gh = pmg, gmg, gmg.gh
+        self.degree, self.interval_ratio = pmg.degree, pmg.interval_ratio
+        self._materialized = {}
+
+
+def check_supported(gh, dh, order=1, who="GMGPrecon"):
+    """what the multigrid covers, checked on the host: raises for a DofHandler the hierarchy cannot serve (gh None: a p-level alone)"""
     if dh.grid.cell_kind != Hexahedron:
-        raise NotImplementedError("GMGPrecon: hexahedral grids only (there is no tetrahedral uniform_refinement)")
-    if dh.ip.order != 1:
-        raise NotImplementedError("GMGPrecon: first-order fields only (p-levels / quadratic fields are out of scope)")
+        raise NotImplementedError("%s: hexahedral grids only (there is no tetrahedral uniform_refinement)" % who)
+    if order == 1 and dh.ip.order != 1:
+        raise NotImplementedError("GMGPrecon: first-order fields only (a second-order field takes ChainedMGPrecon(PMGPrecon(), GMGPrecon(gh)))")
+    if order == 2 and dh.ip.order != 2:
+        raise NotImplementedError("%s: a field of order 2 only (order %d given; first-order fields take GMGPrecon, orders above 2 are out of scope)" % (who, dh.ip.order))
+    if gh is None:
+        return
     fine = gh.grids[-1]
     if dh.grid is not fine and not (dh.grid.conn.shape == fine.conn.shape and np.array_equal(dh.grid.conn, fine.conn) and np.array_equal(dh.grid.xyz, fine.xyz)):
-        raise ValueError("GMGPrecon: the finest grid of the hierarchy is not the grid of the matrix's DofHandler")
+        raise ValueError("%s: the finest grid of the hierarchy is not the grid of the matrix's DofHandler" % who)
     if dh.cell_dofs.shape[0] != fine.n_cells:
-        raise NotImplementedError("GMGPrecon: subdomain dof handlers are out of scope")
+        raise NotImplementedError("%s: subdomain dof handlers are out of scope" % who)
 
 
 class MultigridHierarchy:
-    """A materialised GMGPrecon: per-level DofHandlers with the fine handler's field, their patterns, the transfer and Galerkin plans (tb_mg).
-    `pattern`: the DevicePattern of the system matrix on gh.grids[-1]; `ch`: its ConstraintHandler (None: no Dirichlet dofs)."""
+    """A materialised GMGPrecon, PMGPrecon or ChainedMGPrecon: per-level DofHandlers with the fine handler's components, their patterns, the transfer
+    and Galerkin plans (tb_mg).  `pattern`: the DevicePattern of the system matrix on gh.grids[-1]; `ch`: its ConstraintHandler (None: no Dirichlet
+    dofs).  p_level: the matrix's field is second order; the level below it is the first-order field on the same grid, the h-levels of `gh` (None: no
+    h-levels) follow below that."""
 
-    def __init__(self, pattern, gh, degree=2, interval_ratio=4.0, ch=None):
+    def __init__(self, pattern, gh, degree=2, interval_ratio=4.0, ch=None, p_level=False):
         dh, device = pattern.dmesh.dh, pattern.dmesh.device
-        check_supported(gh, dh)
+        check_supported(gh, dh, order=2 if p_level else 1, who="ChainedMGPrecon" if p_level and gh is not None else "PMGPrecon" if p_level else "GMGPrecon")
         self.device, self.gh, self.pattern, self.degree, self.interval_ratio = device, gh, pattern, int(degree), float(interval_ratio)
-        nl = len(gh.grids)
-        self.dhs = [DofHandler(g, LagrangeCollection(1, dh.ip.ncomp)) for g in gh.grids[:-1]] + [dh]
+        self.p_level = bool(p_level)
+        grids = [dh.grid] if gh is None else list(gh.grids)
+        nl = len(grids) + (1 if p_level else 0)
+        self.dhs = [DofHandler(g, LagrangeCollection(1, dh.ip.ncomp)) for g in (grids if p_level else grids[:-1])] + [dh]
         self.sps = [allocate_matrix(d) for d in self.dhs[:-1]] + [pattern.sp]
         self.patterns = [d.device_mesh(device).pattern(sp) for d, sp in zip(self.dhs[:-1], self.sps[:-1])] + [pattern]
         self.h = C.c_void_p()
         check(lib().tb_mg_create(device.h, nl, C.byref(self.h)))
         for l, p in enumerate(self.patterns):
             check(lib().tb_mg_set_level(self.h, l, p.h))
-        for l in range(1, nl):
+        if p_level:
+            check(lib().tb_mg_set_p_transfer(self.h, nl - 1))
+        for l in range(1, len(grids)):
             pptr, pidx = gh.parents[l - 1]
             pptr, pidx = np.ascontiguousarray(pptr, dtype=np.int64), np.ascontiguousarray(pidx, dtype=np.int32)
-            check(lib().tb_mg_set_transfer(self.h, l, gh.grids[l].n_nodes, pptr.ctypes.data_as(L.c_i64p), pidx.ctypes.data_as(L.c_i32p)))
+            check(lib().tb_mg_set_transfer(self.h, l, grids[l].n_nodes, pptr.ctypes.data_as(L.c_i64p), pidx.ctypes.data_as(L.c_i32p)))
         self.ch = ch
         if ch is not None:
             check(lib().tb_mg_set_prescribed(self.h, ch.flags(device).ptr))
@@ -106,6 +158,24 @@ class MultigridHierarchy:
         out = np.empty(self.sps[level].nnz)
         check(lib().tb_memcpy_d2h(self.device.h, out.ctypes.data_as(C.c_void_p), p, out.nbytes))
         return out
+
+    def plan(self, level):
+        """(blocked, n_terms) of the Galerkin plan between `level` and the level below (after one setup): blocked — one 4-byte term per pair of
+        3 × 3 blocks instead of one per pair of non-zeros"""
+        blocked, n = C.c_int(), C.c_int64()
+        check(lib().tb_mg_level_plan(self.h, level, C.byref(blocked), C.byref(n)))
+        return bool(blocked.value), n.value
+
+    def galerkin(self, level):
+        """the product below `level` alone, as the latest setup computed it (enqueues only): what a measurement of the Galerkin kernels times"""
+        check(lib().tb_mg_galerkin(self.h, level))
+
+    def plan_bytes(self, level):
+        """device bytes of that plan: the terms, the pointer per coarse non-zero (block) and, blocked, the block-row tables of the two patterns"""
+        blocked, n = self.plan(level)
+        per = 9 if blocked else 1
+        extra = 4 * (self.sps[level].nnz + self.sps[level - 1].nnz) // 9 if blocked else 0
+        return 4 * n + 8 * (self.sps[level - 1].nnz // per + 1) + extra
 
     def lambda_max(self, level):
         out = C.c_double()
@@ -155,12 +225,12 @@ class KrylovMGSolver:
     def __init__(self, krylov="cg", mg=None, maxiters=None, rtol=1e-8, atol=1e-14):
         if krylov != "cg":
             raise NotImplementedError("KrylovMGSolver(%r): the multigrid preconditions CG only (GMRES is out of scope)" % (krylov,))
-        if not isinstance(mg, (GMGPrecon, MultigridHierarchy)):
-            raise TypeError("KrylovMGSolver: mg must be a GMGPrecon or a materialised MultigridHierarchy")
+        if not isinstance(mg, (GMGPrecon, PMGPrecon, MultigridHierarchy)):
+            raise TypeError("KrylovMGSolver: mg must be a GMGPrecon, a PMGPrecon, a ChainedMGPrecon or a materialised MultigridHierarchy")
         self.mg, self.maxiters, self.rtol, self.atol = mg, maxiters, rtol, atol
 
     def solve(self, pattern, A, b, x, ch=None):
-        mg = self.mg.materialize(pattern, ch) if isinstance(self.mg, GMGPrecon) else self.mg
+        mg = self.mg.materialize(pattern, ch) if hasattr(self.mg, "materialize") else self.mg
         return mg.solve(A, b, x, self.rtol, self.atol, self.maxiters if self.maxiters is not None else 1000)
 
     def __call__(self, pattern, J, b, x):
