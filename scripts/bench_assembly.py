@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Times the Q1 matrix assembly paths at one size: fused M+K pass, the same kernel per matrix, and (TB_PATCH_KERNEL=legacy) the general
-patch kernel.  Tile shape via TB_PATCH_TILE=tx,ty,tz.  usage: python3 scripts/bench_assembly.py [--n 216] [--reps 10]"""
+patch kernel.  The legacy switch is read by the profiling build only (make -C thunderbolt.jl_amd/csrc ablation, loaded with
+TB_LIBTBHIP=.../libtbhip_ablation.so); the product library ignores it and the "kernel" field below then still says legacy.  Tile shape via TB_PATCH_TILE=tx,ty,tz.  usage: python3 scripts/bench_assembly.py [--n 216] [--reps 10]"""
 import argparse
 import json
 import os

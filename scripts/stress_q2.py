@@ -1,5 +1,5 @@
 """Repeat the quadratic-field matrix assemblies and compare every run with the first: the element strategy is bit-reproducible (exact equality),
-the scattering strategies agree to rounding.  Looks for races in the persistent, LDS-barrier-only integration kernel (tb_assembly.hip, k_matrix_q2)."""
+the scattering strategies agree to rounding.  Looks for races in the persistent, LDS-barrier-only integration kernels (tb_assembly_q2.hip: k_matrix_q2_sf under the element strategy, k_matrix_q2 under the scattering ones)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

@@ -400,6 +400,31 @@ def test_q2_scalar_forms_parity(tb, oracle, device):
     assert np.abs(x.to_host() - xref).max() < 1e-9 * np.abs(xref).max()
 
 
+def test_q2_position_tables_are_built_independently(tb, oracle, device):
+    """The two position tables of the triquadratic forms are built on first use, each by the strategy that reads it: the element strategy
+    (tensor-order table, tensor-order slot table) and the per-colour strategy (Ferrite-order table) give the same bits whichever of them a
+    pattern meets first.  40 cells = 13 triples of the sum-factorised kernel and one single cell: its last pass is ragged."""
+    g = tb.generate_mesh(tb.Hexahedron, (5, 4, 2), (0, 0, 0), (1.0, 0.7, 0.5), perturb=0.15)
+    dh = tb.DofHandler(g, tb.LagrangeCollection(2))
+    assert g.n_cells == 40
+    nonsym = np.array([[2.0, 0.5, 0.0], [-0.1, 1.5, 0.2], [0.3, 0.0, 1.0]])
+    forms = (lambda: tb.BilinearMassIntegrator(tb.ConstantCoefficient(1.7)), lambda: tb.BilinearDiffusionIntegrator(tb.ConstantCoefficient(nonsym)))
+    got = {}
+    for name, order in (("A", ("element", "color")), ("B", ("color", "element"))):
+        sp = tb.allocate_matrix(dh)                            # a fresh pattern: no table yet
+        for s in order:
+            st = tb.ElementAssemblyStrategy(device) if s == "element" else tb.PerColorAssemblyStrategy(device)
+            got[name, s] = [tb.update_operator(tb.setup_operator(st, f(), dh, sp), 0.0).A.to_host() for f in forms]
+    om = oracle.Mesh(oracle.HEX27, 3, g.xyz, g.conn, dh.cell_dofs)
+    ref = [oracle.assemble_matrix(om, 0, oracle.Coef(oracle.COEF_CONST_SCALAR, [1.7]), sp.rowptr, sp.colidx),
+           oracle.assemble_matrix(om, 1, oracle.Coef(oracle.COEF_CONST_TENSOR, nonsym.ravel()), sp.rowptr, sp.colidx)]
+    for s in ("element", "color"):
+        for k in range(2):
+            assert np.array_equal(got["A", s][k], got["B", s][k]), (s, k)
+            for name in ("A", "B"):
+                assert rel_err(got[name, s][k], ref[k]) < TOL, (name, s, k)
+
+
 # ------------------------------------------------------------------------------------------- reaction
 MODELS = [("FHNModel", "CELL_FHN"), ("AlievPanfilovModel", "CELL_ALIEV_PANFILOV"), ("PCG2019", "CELL_PCG2019"), ("TT06", "CELL_TT06"), ("ORd2011", "CELL_ORD11")]
 

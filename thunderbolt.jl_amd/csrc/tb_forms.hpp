@@ -1,4 +1,4 @@
-// tb_forms.hpp — kernel-argument views of a mesh and of a scalar form (shared by tb_assembly.hip and tb_patch_fused.hip).
+// tb_forms.hpp — kernel-argument views of a mesh and of a scalar form (shared by the tb_assembly*.hip units and tb_patch_fused.hip).
 #pragma once
 #include <cmath>
 #include <cstdlib>

@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
@@ -27,6 +28,13 @@ inline const char *tune_env(const char *name) { return getenv(name); }
 #else
 inline const char *tune_env(const char *) { return nullptr; }
 #endif
+// TB_PATCH_KERNEL=legacy (profiling build; scripts/bench_assembly.py): first-order matrices of the PATCH strategy stay on the general patch kernel —
+// the one predicate behind hex8_patch_applicable and tet4_patch_applicable
+inline bool patch_kernel_legacy()
+{
+    static const bool legacy = tune_env("TB_PATCH_KERNEL") && !strcmp(tune_env("TB_PATCH_KERNEL"), "legacy");
+    return legacy;
+}
 void set_last_kernel(const char *fmt, ...); // tb_last_kernel_name: the instance an assembly call launched
 const char *last_kernel();
 
@@ -261,10 +269,10 @@ struct tb_pattern {
     uint64_t mir_stamp[MIRRORS] = {0, 0}, mir_clock = 0; // bind / refresh order: a new binding evicts the slot bound or refreshed longest ago (true LRU, what api.py keeps alive)
     uint32_t *d_wrunrec = nullptr;  // wave-private SpMV (TB_SPMV_KERNEL=wave): runs of ≤ 21 rows as 16-byte records
     int64_t n_wrun = 0;
-    uint16_t *d_q2pos = nullptr;    // scalar Q2 forms: position of col dof(j) in row dof(i), per cell and pair
-    uint16_t *d_q2pos_t = nullptr;  // the same in the order of the stored element matrices (element strategy: tensor order, k_matrix_q2_sf)
-    double *d_kebuf = nullptr;      // element-matrix buffer of the ElementAssemblyStrategy (vector fields)
-    size_t kebuf_bytes = 0;
+    uint16_t *d_q2pos = nullptr;    // scalar Q2 forms: position of col dof(j) in row dof(i), per cell and pair (built by the first scattering assembly)
+    uint16_t *d_q2pos_t = nullptr;  // the same in the order of the stored element matrices (tensor order, k_matrix_q2_sf; built by the first element-strategy assembly)
+    double *d_kebuf = nullptr;      // element-matrix buffer of the ElementAssemblyStrategy (vector fields: tb_mechanics.hip; scalar Q2 forms: tb_assembly_q2.hip)
+    size_t kebuf_bytes = 0;         // its size (ensure_buffer)
     double *d_qpbuf = nullptr;      // quadrature-point records of the split mechanics linearisation (k_mech_points → k_mech_contract), one launch's worth
     size_t qpbuf_bytes = 0;
     void *d_gnodes = nullptr;       // per field node: {first nz, row length, cell count, ≤ 8 element-matrix run offsets} of the staged gather
@@ -330,6 +338,7 @@ int build_color_plan_subset(tb_mesh *m, const std::vector<int32_t> &cells, std::
 int build_ea_plan(tb_mesh *m);
 int ensure_ea_ell(tb_mesh *m);
 int ensure_ea_ell_q2t(tb_mesh *m);
+void ensure_max_row_len(tb_pattern *p); // fills tb_pattern::max_row_len (the longest CSR row) on first use
 int ensure_patch_records(tb_pattern *p); // one-trip records of the fused plan (after ensure_patch_fused); TB_ERR_UNSUPPORTED when the patches do not fit the form
 int ensure_patch_plans(tb_mesh *m, tb_pattern *p); // builds / refits both so the LDS block allows two workgroups per CU
 void free_patch_plan(tb_mesh *m);
@@ -340,7 +349,7 @@ int ensure_patch_fused(tb_mesh *m, tb_pattern *p, int nregions); // plan of the 
 void free_patch_fused_plan(tb_pattern *p);
 int launch_assemble_hex8_patch(tb_form *fK, tb_form *fM, tb_pattern *p, double t, double *d_nzK, double *d_nzM); // either form may be NULL
 bool hex8_patch_applicable(const tb_form *f, const tb_pattern *p);
-int launch_assemble_tet4_patch(tb_form *fK, tb_form *fM, tb_pattern *p, double t, double *d_nzK, double *d_nzM); // linear tetrahedra; either form may be NULL
+int launch_assemble_tet4_patch(tb_form *fK, tb_form *fM, tb_pattern *p, double t, double *d_nzK, double *d_nzM); // tb_assembly_tet4.hip: linear tetrahedra; either form may be NULL
 bool tet4_patch_applicable(const tb_form *f, const tb_pattern *p);
 int ensure_aux_stream(tb_device *dev); // tb_api.cpp: second queue + two events of the chunked element assemblies (tb_mechanics.hip, scalar Q2 forms)
 
@@ -352,6 +361,10 @@ int launch_assemble_matrix(tb_form *f, tb_pattern *p, int strategy, double t, do
 int launch_assemble_vector(tb_form *f, int strategy, double t, double *d_b);
 int tabulate_diffusion_field(tb_form *f);      // first-order hexahedra: fills tb_form::d_dtab (8 points per cell) as the first assembly would
 int tabulate_diffusion_field_tet4(tb_form *f); // the same on linear tetrahedra (4 points per cell)
+int tabulate_diffusion_field_q2(tb_form *f);   // the same at the 27 points of the triquadratic forms (first-order nodal data)
+// tb_assembly_q2.hip: scalar forms on the triquadratic field
+int launch_q2_matrix(tb_form *f, tb_pattern *p, int strategy, double t, double *d_nz); // ELEMENT, ATOMIC or PER_COLOR
+int launch_q2_vector(tb_form *f, int strategy, double t, double *d_b);                 // ATOMIC (also taken for ELEMENT) or PER_COLOR
 // tb_mechanics.hip, tb_mech_facets.hip, tb_mech_tet.hip, tb_chamber.hip
 int launch_hyperelastic(tb_form *f, tb_pattern *p, int strategy, const double *d_u, double *d_nz, double *d_r);
 int host_material_eval_form(tb_form *form, const double *F9, double *psi, double *P, double *A);
@@ -466,6 +479,18 @@ int upload(tb_device *dev, const std::vector<T> &h, T **d)
     TB_HIP(hipMalloc((void **)d, h.size() * sizeof(T)));
     TB_HIP(hipMemcpyAsync(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, dev->stream));
     TB_SYNC_STREAM(dev);
+    return TB_OK;
+}
+
+// a per-pattern device buffer of at least `need` bytes: kept, or freed and allocated anew
+inline int ensure_buffer(double *&d_buf, size_t &have, size_t need, const char *what)
+{
+    if (d_buf && have < need) { (void)hipFree(d_buf); d_buf = nullptr; }
+    if (!d_buf) {
+        hipError_t e = hipMalloc((void **)&d_buf, need);
+        if (e != hipSuccess) { (void)hipGetLastError(); set_error("%s (%zu B): %s", what, need, hipGetErrorString(e)); return TB_ERR_NOMEM; }
+        have = need;
+    }
     return TB_OK;
 }
 

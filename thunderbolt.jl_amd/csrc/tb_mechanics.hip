@@ -743,18 +743,6 @@ static int launch_cells(const MechCall &c, const int32_t *list, int64_t cell0, i
     return TB_OK;
 }
 
-// a per-pattern device buffer of at least `need` bytes: kept, or freed and allocated anew
-static int ensure_buffer(double *&d_buf, size_t &have, size_t need, const char *what)
-{
-    if (d_buf && have < need) { (void)hipFree(d_buf); d_buf = nullptr; }
-    if (!d_buf) {
-        hipError_t e = hipMalloc((void **)&d_buf, need);
-        if (e != hipSuccess) { (void)hipGetLastError(); set_error("%s (%zu B): %s", what, need, hipGetErrorString(e)); return TB_ERR_NOMEM; }
-        have = need;
-    }
-    return TB_OK;
-}
-
 #ifdef TB_ABLATION
 // TB_PROF_STAMPS (profiling build): 16 phase time stamps of every 256th workgroup of the fused tangent kernel
 static int prof_stamps_begin(tb_mesh *m, MechMesh &mm)

@@ -621,8 +621,7 @@ k_patch_hex8_record(FormArgs faK, FormArgs faM, const uint8_t *__restrict__ rec,
 
 bool hex8_patch_applicable(const tb_form *f, const tb_pattern *p)
 {
-    static const bool legacy = getenv("TB_PATCH_KERNEL") && !strcmp(getenv("TB_PATCH_KERNEL"), "legacy");
-    if (legacy) return false;
+    if (patch_kernel_legacy()) return false;
     const tb_mesh *m = f->mesh;
     if (m->field_kind != TB_HEX8 || m->geom_kind != TB_HEX8 || m->ncomp != 1 || f->qorder != 2) return false;
     if (f->kind == TB_FORM_DIFFUSION && !f->symmetric) return false;

@@ -10,6 +10,12 @@ using namespace plan;
 static MeshView view(const tb_mesh *m) { return {m->n_nodes, m->n_cells, m->ndofs, m->nverts, m->ndpc, m->ncomp, m->h_xyz.data(), m->h_conn.data(), m->h_cell_dofs.data()}; }
 static PatternView view(const tb_pattern *p) { return {p->n_rows, p->h_rowptr.data(), p->h_colidx.data(), p->max_row_len}; }
 
+void ensure_max_row_len(tb_pattern *p)
+{
+    if (p->max_row_len) return;
+    for (int64_t r = 0; r < p->n_rows; ++r) p->max_row_len = std::max<int64_t>(p->max_row_len, p->h_rowptr[r + 1] - p->h_rowptr[r]);
+}
+
 static bool parse3(const char *e, int *t)
 {
     int a, b, c;
@@ -191,7 +197,7 @@ int ensure_patch_fused(tb_mesh *m, tb_pattern *p, int nregions)
     int version;
     PatchPlan &cur = patch_slot(m, version);
     FusedHost h;
-    if (!p->max_row_len && m->nverts == 8 && m->ndpc == 8) for (int64_t r = 0; r < p->n_rows; ++r) p->max_row_len = std::max<int64_t>(p->max_row_len, p->h_rowptr[r + 1] - p->h_rowptr[r]);
+    if (m->nverts == 8 && m->ndpc == 8) ensure_max_row_len(p);
     const Outcome r = fit_fused(view(m), view(p), o, nregions, m->fit, cur, replaced, h);
     free_patch_fused_plan(p);
     TB_TRY(sync_patch_plan(m, replaced, version));
