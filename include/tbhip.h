@@ -27,7 +27,8 @@
  *   TB_PATCH_ISO = 0                              constant positive definite tensors through the DIAG / general instances instead of the ISO one
  *   TB_PATCH_CANON = 0 | 1                        record kernel: 0 = canonical patches (lexicographic lattice rows) through the general instance too, 1 = through
  *                                                 the CANON instance at any size (default: from 64 canonical patches per CU on)
- *   TB_SPMV_KERNEL = rows                         CSR rows kernel also where the pattern compresses (what patterns without shared signatures run)
+ *   TB_SPMV_KERNEL = rows                         CSR rows kernel also where the pattern compresses (what patterns without shared signatures run); read at a
+ *                                                 pattern's first product; any other value is ignored
  *   TB_MECH_CHUNKS = n                            launches of the chunked Q2 linearisation (0 / 1: one)
  *   TB_NEWMARK_STAGE = rows                       tb_newmark_stage runs its fused general CSR kernel on every pattern (read at a pattern's first stage call)
  *   TB_PLAN_VERBOSE = 1                           plan statistics on stderr;   TB_RCCL_LIBRARY = path   the RCCL to open
@@ -549,7 +550,9 @@ int tb_cell_model_defaults(int model, double *params, double *u0);
 /* ------------------------------------------------------------------ heat-step algebra
  * Anz = Mnz − Δt·Knz (src/solver/time/euler.jl:110-116) */
 int tb_heat_matrix(tb_device *dev, int64_t nnz, const double *d_Mnz, const double *d_Knz, double dt, double *d_Anz);
-/* y = α·A·x + β·y, CSR (src/utils.jl:185-231; `b = M uₙ₋₁`, src/solver/time/euler.jl:85) */
+/* y = α·A·x + β·y, CSR (src/utils.jl:185-231; `b = M uₙ₋₁`, src/solver/time/euler.jl:85).  The pattern's product plans are built on the host at its
+ * first product (tb_spmv_csr, tb_spmv_csr_dot or a solver; tb_pattern_spmv_plan builds them too).  Inside tb_graph_begin … tb_graph_end a product
+ * whose plans are not built returns TB_ERR_BAD_ARG and enqueues nothing (the capture stays valid): make the first product before the capture. */
 int tb_spmv_csr(tb_pattern *pat, const double *d_nzval, const double *d_x, double alpha, double beta, double *d_y);
 /* Jacobi-preconditioned CG for the heat step A uₙ = b, A = M − Δt·K SPD (src/solver/time/euler.jl:94-100; the tutorials
  * configure KrylovJL_CG(atol = 1e-6, rtol = 1e-5)).  d_x holds the initial guess (uₙ₋₁) and the solution.
@@ -690,7 +693,10 @@ int tb_comm_exchange_end(tb_comm *comm);
  * tb_graph_launch replays the whole sequence with one launch.  Rules while a capture is open: the status is deferred (tb_device_defer_status
  * semantics; tb_device_poll_status after a launch reads what the replayed kernels raised); nothing that reads back to the host may be called
  * (tb_memcpy_d2h, tb_dot, the solvers' convergence looks, tb_reaction_step_rtc) — tb_graph_end then fails with TB_ERR_HIP; every plan the calls
- * need must exist already (run the sequence once, uncaptured, first).  Scalar arguments are frozen in a captured launch EXCEPT the time: forms and
+ * need must exist already (run the sequence once, uncaptured, first).  A product whose plans are not built — tb_spmv_csr, tb_spmv_csr_dot, the
+ * tb_cgd_* / tb_cg1_* iterations, the composition path of tb_newmark_stage, on a pattern that has not multiplied yet — is REFUSED inside an open
+ * capture: TB_ERR_BAD_ARG, tb_last_error_string names the capture, nothing is enqueued and the capture stays valid.
+ * Scalar arguments are frozen in a captured launch EXCEPT the time: forms and
  * ionic models read it from a device slot while captured, and tb_graph_launch(graph, t) sets that slot (t and cos 2πt) ahead of the replay.
  * TB_ERR_UNSUPPORTED: the HIP runtime lacks a graph call this needs (the caller falls back to plain calls).  tb_graph_node_count: nodes captured
  * (kernels, memsets), for reports. */

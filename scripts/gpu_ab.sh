@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B runs of the bench kernels through the library's environment switches, one gpurun call:
-#   gpurun -- bash scripts/gpu_ab.sh "TB_PATCH_KERNEL=staged" "TB_PATCH_KERNEL=record" "TB_SPMV_KERNEL=wave" …
+#   bash scripts/gpu_ab.sh "TB_PATCH_KERNEL=staged" "TB_PATCH_KERNEL=record" …
 # every argument is one environment assignment list (quoted); each is run twice, interleaved, so that box drift shows.
 mkdir -p gpurun_out
 {

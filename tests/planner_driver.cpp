@@ -1,4 +1,5 @@
-// Stand-alone driver of the host planners (thunderbolt.jl_amd/csrc/tb_planners.cpp): no GPU, no HIP.  Links tb_planners.cpp and tb_hostgen.cpp only.
+// Stand-alone driver of the host planners (thunderbolt.jl_amd/csrc/tb_planners.cpp, tb_spmv_planners.cpp): no GPU, no HIP.  Links the two planner files and
+// tb_hostgen.cpp only.
 //   planner_driver <mesh directory> [case]
 // reads the meshes tests/test_planners_cpu.py wrote (<name>.xyz: float64 × 3 per node, <name>.conn: int32 per cell vertex), plans every case, checks
 // the invariants a plan must keep whatever its layout (they do not depend on the recorded digests) and prints "case/part/array value" lines:
@@ -7,11 +8,13 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 
 #include "tbhip.h"
 #include "tb_planners.hpp"
+#include "tb_spmv_planners.hpp"
 
 namespace tb { void set_error(const char *fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); fputc('\n', stderr); } }
 using namespace tb;
@@ -446,6 +449,217 @@ static bool load(const std::string &dir, const char *name, int kind, int ncomp, 
     return tb_host_build_pattern(M.n_cells, M.ndpc, M.cd.data(), M.ndofs, M.rowptr.data(), M.colidx.data()) == nnz;
 }
 
+// ---- the SpMV plans (tb_spmv_planners.cpp): block columns, row runs, signatures, mirror slices, diagonal positions of one CSR pattern ----
+
+struct Csr {
+    std::vector<int64_t> rp{0};
+    std::vector<int32_t> ci;
+    int64_t n() const { return (int64_t)rp.size() - 1; }
+    PatternView view() const { return {n(), rp.data(), ci.data(), 0}; }
+    void row(const std::vector<int32_t> &cols) { ci.insert(ci.end(), cols.begin(), cols.end()); rp.push_back((int64_t)ci.size()); }
+    static Csr of(const Mesh &M) { Csr A; A.rp = M.rowptr; A.ci = M.colidx; return A; }
+};
+static std::vector<int32_t> span(int32_t first, int32_t count) { std::vector<int32_t> v(count); for (int32_t k = 0; k < count; ++k) v[k] = first + k; return v; }
+
+constexpr int SPMV_CAP = 2048; // what tb_spmv.hip passes: the capacity of a run, and the table budget max(nnz / 4, 64)
+enum { NO = 0, YES = 1, ANY = -1 };
+struct Expect { int b3, streams, compresses, mirror; };
+
+static void check_block3(const char *part, const Csr &A, bool is, const std::vector<int32_t> &bcol, int expect)
+{
+    CHECK(expect == ANY || is == (expect == YES), "%s: block-3 = %d", part, (int)is);
+    if (!is) { CHECK(bcol.empty(), "%s: block columns of a pattern that has none", part); return; }
+    CHECK(A.n() % 3 == 0 && bcol.size() * 9 == A.ci.size(), "%s: block columns: size", part);
+    for (int64_t r = 0; r < A.n(); ++r) {
+        const int64_t k0 = A.rp[r - r % 3];
+        CHECK(k0 % 9 == 0 && A.rp[r + 1] - A.rp[r] == A.rp[r - r % 3 + 1] - k0, "%s: row %lld of a block pattern", part, (long long)r);
+        for (int64_t j = 0; j < A.rp[r + 1] - A.rp[r]; ++j) CHECK(A.ci[A.rp[r] + j] == 3 * bcol[k0 / 9 + j / 3] + j % 3, "%s: bcol does not rebuild row %lld", part, (long long)r);
+    }
+}
+
+static void check_runs(const char *part, const Csr &A, bool ok, const std::vector<uint32_t> &rec, int expect)
+{
+    int64_t longest = 0;
+    for (int64_t r = 0; r < A.n(); ++r) longest = std::max(longest, A.rp[r + 1] - A.rp[r]);
+    CHECK(ok == (longest <= SPMV_CAP - 2) && (expect == ANY || ok == (expect == YES)), "%s: streams = %d with a row of %lld entries", part, (int)ok, (long long)longest);
+    if (!ok) { CHECK(rec.empty(), "%s: records of a pattern that does not stream", part); return; }
+    CHECK(!rec.empty() && rec.size() % 4 == 0, "%s: run records: size", part);
+    int64_t next = 0;
+    for (size_t b = 0; b < rec.size() / 4; ++b) {
+        const int64_t r0 = rec[4 * b], nr = rec[4 * b + 1] & 0xffffu, len = rec[4 * b + 1] >> 16, k0 = (int64_t)((uint64_t)rec[4 * b + 3] << 32 | rec[4 * b + 2]);
+        CHECK(r0 == next && r0 + nr <= A.n() && (nr > 0 || A.n() == 0), "%s: run %zu does not continue the partition", part, b);
+        CHECK(nr <= 60000 && len <= SPMV_CAP - 2, "%s: run %zu exceeds a limit (%lld rows, %lld entries)", part, b, (long long)nr, (long long)len);
+        CHECK(k0 == A.rp[r0] && len == A.rp[r0 + nr] - k0, "%s: run %zu: record fields", part, b);
+        next = r0 + nr;
+    }
+    CHECK(next == A.n(), "%s: the runs end at row %lld of %lld", part, (long long)next, (long long)A.n());
+}
+
+static void check_sig(const char *part, const Csr &A, int64_t budget, bool ok, const SigHost &h, int expect)
+{
+    // brute force: the table of the distinct offset lists in order of first appearance (an empty row owns one position)
+    std::map<std::vector<int32_t>, int64_t> first;
+    int64_t total = 0;
+    for (int64_t r = 0; r < A.n(); ++r) {
+        std::vector<int32_t> sg;
+        for (int64_t k = A.rp[r]; k < A.rp[r + 1]; ++k) sg.push_back(A.ci[k] - (int32_t)r);
+        if (first.emplace(sg, total).second) total += std::max<int64_t>((int64_t)sg.size(), 1);
+    }
+    // (the planner gives up at the first signature that takes the table past the budget; the table only grows, so that is total > budget)
+    CHECK(ok == (A.n() > 0 && total <= budget) && (expect == ANY || ok == (expect == YES)), "%s: compresses = %d with a table of %lld entries, budget %lld", part, (int)ok, (long long)total, (long long)budget);
+    if (!ok) { CHECK(h.n_sig == 0 && h.rowsig.empty() && h.tab.empty(), "%s: arrays of a pattern that does not compress", part); return; }
+    CHECK((int64_t)h.rowsig.size() == A.n() && (int64_t)h.tab.size() == total + SIG_SLACK && h.n_sig == (int64_t)first.size(), "%s: signature plan: %lld signatures in %zu entries, expected %zu in %lld + slack",
+          part, (long long)h.n_sig, h.tab.size(), first.size(), (long long)total);
+    for (int k = 0; k < SIG_SLACK; ++k) CHECK(h.tab[h.tab.size() - 1 - k] == 0, "%s: the slack is not zero", part);
+    for (int64_t r = 0; r < A.n(); ++r) {
+        std::vector<int32_t> sg;
+        for (int64_t k = A.rp[r]; k < A.rp[r + 1]; ++k) sg.push_back(A.ci[k] - (int32_t)r);
+        CHECK(h.rowsig[r] == first[sg], "%s: row %lld: signature at %u, first stored at %lld", part, (long long)r, h.rowsig[r], (long long)first[sg]); // equal signatures are stored once
+        for (size_t k = 0; k < sg.size(); ++k) CHECK(h.tab[h.rowsig[r] + k] == sg[k], "%s: row %lld entry %zu: the table does not reproduce colidx - row", part, (long long)r, k);
+    }
+}
+
+static void check_mirror(const char *part, const Csr &A, const uint32_t *rowsig, bool ok, const MirrorHost &h, int expect)
+{
+    const int64_t n = A.n(), ns = (n + 63) / 64;
+    int64_t longest = 0;
+    for (int64_t r = 0; r < n; ++r) longest = std::max(longest, A.rp[r + 1] - A.rp[r]);
+    CHECK(ok == (longest <= 255) && (expect == ANY || ok == (expect == YES)), "%s: mirror = %d with a row of %lld entries", part, (int)ok, (long long)longest);
+    if (!ok) { CHECK(h.slices.empty() && h.offs.empty() && h.entries == 0, "%s: arrays of a pattern without a mirror", part); return; }
+    CHECK((int64_t)h.slices.size() == ns + 1, "%s: %zu slice records for %lld slices", part, h.slices.size(), (long long)ns);
+    int64_t base = 0, obase = 0;
+    for (int64_t s = 0; s < ns; ++s) {
+        const MirrorSlice &m = h.slices[s];
+        const int64_t r0 = 64 * s, r1 = std::min(r0 + 64, n);
+        int64_t w = 0;
+        bool uni = rowsig && r1 - r0 == 64;
+        for (int64_t r = r0; r < r1; ++r) { w = std::max(w, A.rp[r + 1] - A.rp[r]); uni = uni && rowsig[r] == rowsig[r0]; }
+        CHECK(m.base == base && m.width == w && m.pad[0] == 0 && m.pad[1] == 0, "%s: slice %lld: base / width", part, (long long)s);
+        CHECK(uni ? m.sig == rowsig[r0] && m.obase == -1 : m.sig == MIRROR_MIXED && m.obase == obase, "%s: slice %lld: uniform = %d", part, (long long)s, (int)uni);
+        if (!uni) {
+            CHECK(obase + 64 * w <= (int64_t)h.offs.size(), "%s: slice %lld: offsets past the array", part, (long long)s);
+            for (int64_t k = 0; k < w; ++k)
+                for (int64_t l = 0; l < 64; ++l) {
+                    const int64_t r = r0 + l;
+                    const bool on = r < r1 && k < A.rp[r + 1] - A.rp[r];
+                    CHECK(h.offs[obase + 64 * k + l] == (on ? A.ci[A.rp[r] + k] - (int32_t)r : MIRROR_NONE), "%s: slice %lld entry %lld lane %lld", part, (long long)s, (long long)k, (long long)l);
+                }
+            obase += 64 * w;
+        }
+        base += 64 * w;
+    }
+    const MirrorSlice &t = h.slices[ns];
+    CHECK(t.base == base && t.obase == -1 && t.sig == MIRROR_MIXED && t.width == 0 && t.pad[0] == 0 && t.pad[1] == 0 && h.entries == base, "%s: terminator record", part);
+    CHECK(obase ? (int64_t)h.offs.size() == obase : h.offs.size() == 1 && h.offs[0] == 0, "%s: offsets: %zu entries, the mixed slices hold %lld", part, h.offs.size(), (long long)obase);
+}
+
+static void check_diag(const char *part, const Csr &A, const std::vector<int64_t> &pos)
+{
+    CHECK((int64_t)pos.size() == A.n(), "%s: diagonal positions: size", part);
+    for (int64_t r = 0; r < A.n(); ++r) {
+        bool stored = false;
+        for (int64_t k = A.rp[r]; k < A.rp[r + 1]; ++k) stored = stored || A.ci[k] == r;
+        CHECK(pos[r] == -1 ? !stored : pos[r] >= A.rp[r] && pos[r] < A.rp[r + 1] && A.ci[pos[r]] == r, "%s: diagonal position of row %lld", part, (long long)r);
+    }
+}
+
+// every plan of one pattern, as the upload tails of tb_spmv.hip call the planners (the mirror gets the signatures only where the pattern compresses)
+static void spmv_pattern(const char *part, const Csr &A, const Expect &e, bool block3_only = false)
+{
+    const PatternView v = A.view();
+    std::vector<int32_t> bcol;
+    const bool b3 = block3_columns(v, bcol);
+    scalar(part, "b3", b3); digest(part, "bcol", bcol);
+    check_block3(part, A, b3, bcol, e.b3);
+    if (block3_only) return;
+    std::vector<uint32_t> rec;
+    const bool streams = row_runs(v, SPMV_CAP, rec);
+    scalar(part, "streams", streams); scalar(part, "n_runs", (long long)rec.size() / 4); digest(part, "runrec", rec);
+    check_runs(part, A, streams, rec, e.streams);
+    const int64_t budget = std::max<int64_t>(nnz_of(v) / 4, 64);
+    SigHost sg;
+    const bool compresses = row_signatures(v, budget, sg);
+    scalar(part, "compresses", compresses); scalar(part, "n_sig", sg.n_sig); digest(part, "rowsig", sg.rowsig); digest(part, "sigoff", sg.tab);
+    check_sig(part, A, budget, compresses, sg, e.compresses);
+    MirrorHost mh;
+    const uint32_t *rowsig = compresses ? sg.rowsig.data() : nullptr;
+    const bool mirror = mirror_slices(v, rowsig, mh);
+    scalar(part, "mirror", mirror); scalar(part, "mir_entries", mh.entries); digest(part, "slices", mh.slices); digest(part, "mir_off", mh.offs);
+    check_mirror(part, A, rowsig, mirror, mh, e.mirror);
+    const std::vector<int64_t> pos = diagonal_positions(v);
+    digest(part, "diagpos", pos);
+    check_diag(part, A, pos);
+}
+
+static bool case_spmv(const std::string &dir)
+{
+    Mesh M;
+    if (!load(dir, "box", TB_HEX8, 1, M)) return false;
+    const Csr box = Csr::of(M);
+    spmv_pattern("box", box, {NO, YES, NO, YES}); // 13·11·9 = 1287 rows: a ragged last slice; so small a box is mostly boundary layers of the first-visit numbering: the budget refuses
+    if (box.n() % 64 == 0) { fprintf(stderr, "spmv: the box is meant to end in a ragged slice\n"); ++g_failed; }
+    { // the same with one row emptied
+        Csr A;
+        for (int64_t r = 0; r < box.n(); ++r) A.row(r == 70 ? std::vector<int32_t>() : std::vector<int32_t>(box.ci.begin() + box.rp[r], box.ci.begin() + box.rp[r + 1]));
+        spmv_pattern("empty_row", A, {NO, YES, NO, YES});
+    }
+    if (!load(dir, "shuffled_box", TB_HEX8, 1, M)) return false;
+    spmv_pattern("shuffled_box", Csr::of(M), {NO, YES, NO, YES}); // every row its own signature: the budget refuses
+    if (!load(dir, "thin_wall", TB_HEX8, 1, M)) return false;
+    spmv_pattern("thin_wall", Csr::of(M), {NO, YES, ANY, YES});
+    { // the 27-point stencil on 12 × 10 × 8 nodes numbered lexicographically, row 70 emptied: compresses to a handful of signatures (28: 27 positions in the box and the empty row)
+        Csr A;
+        for (int32_t z = 0; z < 8; ++z) for (int32_t y = 0; y < 10; ++y) for (int32_t x = 0; x < 12; ++x) {
+            std::vector<int32_t> cols;
+            for (int32_t c = std::max(z - 1, 0); c <= std::min(z + 1, 7); ++c) for (int32_t b = std::max(y - 1, 0); b <= std::min(y + 1, 9); ++b) for (int32_t a = std::max(x - 1, 0); a <= std::min(x + 1, 11); ++a) cols.push_back(a + 12 * (b + 10 * c));
+            A.row(A.n() == 70 ? std::vector<int32_t>() : cols);
+        }
+        spmv_pattern("lexicographic_box", A, {NO, YES, YES, YES});
+    }
+    if (!load(dir, "q2_scalar", TB_HEX27, 1, M)) return false;
+    spmv_pattern("q2_scalar", Csr::of(M), {NO, YES, ANY, YES});
+    if (!load(dir, "q2_box", TB_HEX27, 3, M)) return false;
+    spmv_pattern("long_rows", Csr::of(M), {YES, YES, ANY, NO}); // rows of 375 entries
+    if (!load(dir, "box", TB_HEX8, 3, M)) return false;
+    const Csr box3 = Csr::of(M);
+    spmv_pattern("box3", box3, {YES, YES, ANY, YES});
+    { // one row's column triple broken: the last column of the first block of row 4 names the next node
+        Csr A = box3;
+        A.ci[A.rp[4] + 2] += 3;
+        spmv_pattern("box3_broken_triple", A, {NO, ANY, ANY, ANY}, true);
+    }
+    { // a node row that does not start at a multiple of nine: three entries in front of row 0's, six behind the last row's
+        Csr A = box3;
+        A.ci.insert(A.ci.begin(), 3, 0);
+        A.ci.insert(A.ci.end(), 6, 0);
+        for (int64_t &k : A.rp) k += 3;
+        A.rp.back() += 6;
+        spmv_pattern("box3_k0_not_9", A, {NO, ANY, ANY, ANY}, true);
+    }
+    { // 130 rows of a tridiagonal matrix: three signatures; slice 0 mixed, slice 1 of one signature, slice 2 ragged
+        Csr A;
+        for (int32_t r = 0; r < 130; ++r) A.row(span(std::max(r - 1, 0), (r > 0) + 1 + (r < 129)));
+        spmv_pattern("tridiagonal", A, {NO, YES, YES, YES});
+    }
+    { // a 256-entry row among diagonal rows: no mirror
+        Csr A;
+        for (int32_t r = 0; r < 3000; ++r) A.row(r == 10 ? span(0, 256) : span(r, 1));
+        spmv_pattern("row_of_256", A, {NO, YES, YES, NO});
+    }
+    for (int extra = 0; extra < 2; ++extra) { // rows of exactly cap − 2 entries stream, a run each; one entry more and the pattern falls back
+        Csr A;
+        for (int32_t r = 0; r < 2100; ++r) A.row(r < 3 ? span(r, SPMV_CAP - 2 + (r == 1 ? extra : 0)) : span(r, 1));
+        spmv_pattern(extra ? "row_of_cap_minus_1" : "rows_of_cap_minus_2", A, {NO, extra ? NO : YES, extra ? NO : YES, NO});
+    }
+    { // 130000 rows, every hundredth with a diagonal entry: the 60000-row limit cuts the runs
+        Csr A;
+        for (int32_t r = 0; r < 130000; ++r) A.row(r % 100 == 0 ? span(r, 1) : std::vector<int32_t>());
+        spmv_pattern("mostly_empty", A, {NO, YES, YES, YES});
+    }
+    spmv_pattern("zero_rows", Csr(), {NO, YES, NO, YES});
+    return true;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 2) { fprintf(stderr, "usage: %s <mesh directory> [case]\n", argv[0]); return 2; }
@@ -510,6 +724,10 @@ int main(int argc, char **argv)
             if (!load(dir, fd.mesh, fd.kind, 3, M)) return 2;
             case_gather(M, fd.part, fd.applies);
         }
+    }
+    if (only.empty() || only == "spmv") {
+        g_case = "spmv";
+        if (!case_spmv(dir)) return 2;
     }
     if (only.empty() || only == "refusals") { // return codes only
         g_case = "refusals";

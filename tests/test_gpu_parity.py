@@ -2895,6 +2895,59 @@ def test_index_compressed_spmv_is_bit_identical_to_the_csr_kernel(tb, device):
     assert abs(out["sig"][3] - xh @ ref) <= 1e-11 * abs(xh @ ref) and abs(out["sig"][3] - out["csr"][3]) <= 1e-12 * abs(out["csr"][3])
 
 
+def test_an_unplanned_product_inside_a_capture_is_refused(tb, device):
+    """A pattern's product plans are host work with blocking uploads, built at its first product.  Inside tb_graph_begin … tb_graph_end that first
+    product — tb_spmv_csr or tb_spmv_csr_dot — returns TB_ERR_BAD_ARG, names the capture and enqueues nothing (it used to launch the lanes-per-row
+    kernel into the capture and report success); the capture stays valid.  Outside, the same product equals scipy, and a capture of the now planned
+    product replays the bits of the direct call."""
+    import ctypes as C
+    import scipy.sparse as ssp
+    from thunderbolt_jl_amd import _lib as L
+    lib = tb.lib()
+    g = tb.generate_mesh(tb.Hexahedron, (6, 5, 4), perturb=0.2)
+    dh = tb.DofHandler(g)
+    sp = tb.allocate_matrix(dh)
+    n = dh.ndofs
+    dm = tb.DeviceMesh(device, dh)
+    pat, pat_dot = tb.DevicePattern(dm, sp), tb.DevicePattern(dm, sp)            # fresh: neither has multiplied yet
+    rng = np.random.default_rng(23)
+    vals, xh = rng.normal(size=sp.nnz), rng.normal(size=n)
+    A, x = device.to_device(vals), device.to_device(xh)
+    y, y_dot, d = device.to_device(np.full(n, 7.0)), device.to_device(np.full(n, 7.0)), device.zeros(1)
+    tb.check(lib.tb_graph_begin(device.h))
+    rc = lib.tb_spmv_csr(pat.h, A.ptr, x.ptr, 1.0, 0.0, y.ptr)
+    msg = lib.tb_last_error_string()
+    rc_dot = lib.tb_spmv_csr_dot(pat_dot.h, A.ptr, x.ptr, y_dot.ptr, d.ptr)
+    msg_dot = lib.tb_last_error_string()
+    h = C.c_void_p()
+    tb.check(lib.tb_graph_end(device.h, C.byref(h)))                              # the capture survived both refusals
+    nodes = C.c_int(-1)
+    if h:
+        tb.check(lib.tb_graph_node_count(h, C.byref(nodes)))
+        lib.tb_graph_destroy(h)
+    assert rc == L.TB_ERR_BAD_ARG and b"graph capture is open" in msg, (rc, msg)
+    assert rc_dot == L.TB_ERR_BAD_ARG and b"graph capture is open" in msg_dot, (rc_dot, msg_dot)
+    assert nodes.value == 0                                                        # nothing was enqueued
+    np.testing.assert_array_equal(y.to_host(), 7.0)
+    np.testing.assert_array_equal(y_dot.to_host(), 7.0)
+    assert d.to_host()[0] == 0.0
+    # the same products outside the capture
+    ref = ssp.csr_matrix((vals, sp.colidx, sp.rowptr), shape=(n, n)) @ xh
+    tb.check(lib.tb_spmv_csr(pat.h, A.ptr, x.ptr, 1.0, 0.0, y.ptr))
+    tb.check(lib.tb_spmv_csr_dot(pat_dot.h, A.ptr, x.ptr, y_dot.ptr, d.ptr))
+    direct = y.to_host()
+    assert rel_err(direct, ref) < TOL and rel_err(y_dot.to_host(), ref) < TOL
+    assert abs(d.to_host()[0] - xh @ ref) <= 1e-11 * abs(xh @ ref)
+    # planned now: the capture takes the product and replays the bits of the direct call
+    y.copy_from_host(np.full(n, 7.0))
+    gr = device.capture(lambda: tb.check(lib.tb_spmv_csr(pat.h, A.ptr, x.ptr, 1.0, 0.0, y.ptr)))
+    assert gr.nodes >= 1
+    np.testing.assert_array_equal(y.to_host(), 7.0)                                # captured, not run
+    gr.launch()
+    np.testing.assert_array_equal(y.to_host(), direct)
+    gr.close()
+
+
 @pytest.mark.parametrize("order", [1, 2])
 def test_block_spmv_of_vector_field_patterns(tb, device, order):
     """Patterns of 3-dof-per-node fields are CSRs of 3×3 blocks and take the block SpMV (one column index per block); a pattern that breaks the

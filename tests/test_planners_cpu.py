@@ -1,8 +1,8 @@
-"""The host planners (thunderbolt.jl_amd/csrc/tb_planners.cpp) without a GPU: tests/planner_driver.cpp, a stand-alone program linked with the planners
+"""The host planners (thunderbolt.jl_amd/csrc/tb_planners.cpp, tb_spmv_planners.cpp) without a GPU: tests/planner_driver.cpp, a stand-alone program linked with the planners
 and the host generators only, plans every case, checks the invariants of each plan itself and prints a digest of every plan array.  The digests are
 compared with tests/golden/plan_digests.json, recorded from the plan builders before they were split into planners and an upload tail (every array that
 reaches the device is byte for byte what it was; gather_nodes: from the three host functions of tb_mechanics.hip before they moved behind the same
-seam), at 1 and at 4 OpenMP threads.  A change that alters a plan on purpose re-records the file from the
+seam; spmv: from the five plan functions of tb_spmv.hip before their host halves moved there), at 1 and at 4 OpenMP threads.  A change that alters a plan on purpose re-records the file from the
 driver's output; the invariants hold either way."""
 import json
 import os
@@ -16,7 +16,7 @@ from helpers import hex_to_tets, pentagon_prism_mesh
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "thunderbolt.jl_amd", "csrc")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "plan_digests.json")
-CASES = ["box", "box_two_blocks", "shuffled_box", "ring", "ideal_lv", "thin_wall", "tets", "long_rows", "colouring", "refusals", "gather_nodes"]
+CASES = ["box", "box_two_blocks", "shuffled_box", "ring", "ideal_lv", "thin_wall", "tets", "long_rows", "colouring", "refusals", "gather_nodes", "spmv"]
 
 
 def write_meshes(tb, out):
@@ -54,7 +54,7 @@ def write_meshes(tb, out):
 
 def build_driver(exe, extra=()):
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-fopenmp", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include", "-I", CSRC,
-                           *extra, os.path.join(ROOT, "tests", "planner_driver.cpp"), os.path.join(CSRC, "tb_planners.cpp"), os.path.join(CSRC, "tb_hostgen.cpp"), "-o", exe])
+                           *extra, os.path.join(ROOT, "tests", "planner_driver.cpp"), os.path.join(CSRC, "tb_planners.cpp"), os.path.join(CSRC, "tb_spmv_planners.cpp"), os.path.join(CSRC, "tb_hostgen.cpp"), "-o", exe])
 
 
 @pytest.fixture(scope="module")
@@ -67,8 +67,9 @@ def driver(tb, tmp_path_factory):
 
 
 def test_the_planners_need_no_hip_header(tmp_path):
-    """tb_planners.cpp compiles with nothing but the standard library on the include path"""
-    subprocess.check_call(["g++", "-std=c++17", "-fopenmp", "-Wall", "-Werror", "-c", os.path.join(CSRC, "tb_planners.cpp"), "-o", str(tmp_path / "tb_planners.o")])
+    """tb_planners.cpp and tb_spmv_planners.cpp compile with nothing but the standard library on the include path"""
+    for name in ("tb_planners", "tb_spmv_planners"):
+        subprocess.check_call(["g++", "-std=c++17", "-fopenmp", "-Wall", "-Werror", "-c", os.path.join(CSRC, name + ".cpp"), "-o", str(tmp_path / (name + ".o"))])
 
 
 @pytest.mark.parametrize("threads", [1, 4])

@@ -450,7 +450,7 @@ int tb_pattern_destroy(tb_pattern *p)
 {
     if (!p) return TB_OK;
     { std::lock_guard<std::mutex> lock(g_mirrored_mutex); g_mirrored.erase(std::remove(g_mirrored.begin(), g_mirrored.end(), p), g_mirrored.end()); }
-    hipFree(p->d_rowptr); hipFree(p->d_colidx); hipFree(p->d_blkrow); hipFree(p->d_blkrec); hipFree(p->d_rowsig); hipFree(p->d_sigoff); hipFree(p->d_wrunrec); for (double *q : p->d_mir) hipFree(q); hipFree(p->d_mir_base); hipFree(p->d_mir_off); hipFree(p->d_bcol); hipFree(p->d_diagpos); hipFree(p->d_emap); hipFree(p->d_blockpos); hipFree(p->d_krylov_ws); hipFree(p->d_q2pos); hipFree(p->d_q2pos_t); hipFree(p->d_kebuf); hipFree(p->d_qpbuf); hipFree(p->d_gnodes); hipFree(p->d_stage_d);
+    hipFree(p->d_rowptr); hipFree(p->d_colidx); hipFree(p->d_blkrec); hipFree(p->d_rowsig); hipFree(p->d_sigoff); for (double *q : p->d_mir) hipFree(q); hipFree(p->d_mir_base); hipFree(p->d_mir_off); hipFree(p->d_bcol); hipFree(p->d_diagpos); hipFree(p->d_emap); hipFree(p->d_blockpos); hipFree(p->d_krylov_ws); hipFree(p->d_q2pos); hipFree(p->d_q2pos_t); hipFree(p->d_kebuf); hipFree(p->d_qpbuf); hipFree(p->d_gnodes); hipFree(p->d_stage_d);
     free_patch_mat_plan(p);
     free_patch_fused_plan(p);
     delete p;

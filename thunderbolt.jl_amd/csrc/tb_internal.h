@@ -247,8 +247,7 @@ struct tb_pattern {
                                     // 2 = fused general kernel (TB_NEWMARK_STAGE=rows), 3 = composition (vector kernel, SpMV, axpy) with d_stage_d
     double *d_stage_d = nullptr;    // u − ũ of the composition path (n_rows doubles)
     int64_t *d_diagpos = nullptr;   // nz index of each row's diagonal entry (−1 if absent), built at the first Jacobi-preconditioned solve
-    int32_t *d_blkrow = nullptr;    // stream SpMV: first row of each workgroup's run of rows (n_blk + 1 entries)
-    uint32_t *d_blkrec = nullptr;   // the same runs as 16-byte records {first row, rows | entries << 16, first nz low, high} (k_spmv_stream_rec)
+    uint32_t *d_blkrec = nullptr;   // stream SpMV: each workgroup's run of rows as a 16-byte record {first row, rows | entries << 16, first nz low, high}
     int64_t n_blk = 0;              // 0 = not planned yet, −1 = a row exceeds the capacity (lanes-per-row kernel)
     // index-compressed stream SpMV: rows that hold the same column offsets (colidx[k] − row) share one signature; a row then needs 4 B (the
     // position of its signature in the table) instead of 4 B per non-zero
@@ -267,8 +266,6 @@ struct tb_pattern {
     int64_t mir_entries = 0;
     const double *mir_nz[MIRRORS] = {nullptr, nullptr}; // the value array each mirror currently reflects (products with this pointer use it); NULL = unbound
     uint64_t mir_stamp[MIRRORS] = {0, 0}, mir_clock = 0; // bind / refresh order: a new binding evicts the slot bound or refreshed longest ago (true LRU, what api.py keeps alive)
-    uint32_t *d_wrunrec = nullptr;  // wave-private SpMV (TB_SPMV_KERNEL=wave): runs of ≤ 21 rows as 16-byte records
-    int64_t n_wrun = 0;
     uint16_t *d_q2pos = nullptr;    // scalar Q2 forms: position of col dof(j) in row dof(i), per cell and pair (built by the first scattering assembly)
     uint16_t *d_q2pos_t = nullptr;  // the same in the order of the stored element matrices (tensor order, k_matrix_q2_sf; built by the first element-strategy assembly)
     double *d_kebuf = nullptr;      // element-matrix buffer of the ElementAssemblyStrategy (vector fields: tb_mechanics.hip; scalar Q2 forms: tb_assembly_q2.hip)
@@ -416,7 +413,8 @@ int spmv_plans(tb_pattern *p); // builds the plans tb_spmv_csr would build on it
 int launch_spmv(tb_pattern *p, const double *nz, const double *x, double alpha, double beta, double *y);
 int launch_spmv_dot(tb_pattern *pat, const double *A, const double *x, double *y, double *d_dot);        // y = A x, *d_dot += xᵀy
 int launch_spmv_dot_slots(tb_pattern *pat, const double *A, const double *x, double *y, double *group);  // the same with the sum left in a slot group: the
-                                                                                                         // one place that picks the product kernel of every CG form
+                                                                                                         // product of every CG form
+// (all three plan at the pattern's first product and choose the kernel through one selector; an unplanned product inside a graph capture is refused)
 int launch_spmv_rows(tb_pattern *p, const double *nz, const double *x, int64_t n, const int32_t *rows, double *out);
 int launch_mirror_bind(tb_pattern *p, const double *nz); // tb_spmv_mirror
 int launch_extract_diagonal(tb_pattern *p, const double *nz, double *diag);
