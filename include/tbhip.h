@@ -99,6 +99,7 @@ enum {
     TB_FORM_DIFFUSION = 1, /* Kₑ[i,j] -= ∇Nⱼ·D·∇Nᵢ dΩ       src/modeling/core/diffusion.jl:28-50  */
     TB_FORM_SOURCE = 2,    /* bₑ[j]  += f(x_q,t) Nⱼ dΩ      src/modeling/core/analytical_coefficient.jl:80-101 */
     TB_FORM_FACET = 4,       /* weak boundary conditions on hexahedron / tetrahedron facets   src/modeling/core/weak_boundary_conditions.jl */
+    TB_FORM_INTERFACE = 6,   /* diffusion across zero-thickness interface elements (tb_interface_form_create)   src/modeling/core/diffusion.jl:76-157 */
     TB_FORM_CHAMBER = 5,     /* 3D–0D chamber coupling on hexahedron facets (tb_chamber_form_create)   src/modeling/coupler/fsi.jl:118-185 */
     TB_FORM_HYPERELASTIC = 3 /* rₑ[i] += ∇δuᵢ⊡P dΩ, Kₑ[i,j] += (∇δuᵢ⊡𝔸)⊡∇δuⱼ dΩ   src/modeling/solid/elements.jl:177-313 */
 };
@@ -389,6 +390,27 @@ int tb_facet_form_create(tb_mesh *mesh, int bc_kind, double param, int facet_qpo
 int tb_facet_form_set_param(tb_form *form, double param);
 int tb_facet_assemble(tb_form *form, tb_pattern *pat, const double *d_u, double t, double *d_nzval, double *d_r);
 int tb_host_material_eval(const tb_material *material, const double *F, double *psi, double *P, double *A);
+
+/* Diffusion across the interface between two subdomains (InterfaceDiffusionModel / BilinearInterfaceDiffusionIntegrator,
+ * src/modeling/core/diffusion.jl:76-157): zero-thickness interface elements on a first-order scalar field over TB_HEX8 or TB_QUAD4 cells whose
+ * interface nodes have been duplicated (the two sides share no node).  Added after ABI revision 10 without moving it: additions only.
+ *   records  n × 4: (cell_a, local_facet_a, cell_b, local_facet_b) — local facets as Ferrite.reference_facets: hexahedra as listed for the
+ *            weak boundary conditions, quadrilaterals the edges (0,1), (1,2), (2,3), (3,0)
+ *   pairing  n × nf (nf = 4 on hexahedra, 2 on quadrilaterals): for the k-th node of a's facet in Ferrite's facet-node order, the local vertex of
+ *            cell_b that is its copy.  It must lie on local_facet_b and coincide in space with a's node (TB_ERR_BAD_ARG otherwise)
+ *   facet_qpoints  1…3 Gauss points per facet direction; 0 selects 2 = max(2p − 1, 2)
+ *   G, G_per_element  the conductance: one value, or n host values (NULL: G)
+ * The interface element's dofs are a's facet dofs, then their copies on b; with F = G ∫ N_i N_j dΓ over the first-order facet shape functions
+ *   Kₑ[a_i, a_j] −= F[i][j]   Kₑ[b_i, b_j] −= F[i][j]   Kₑ[a_i, b_j] += F[i][j]   Kₑ[b_i, a_j] += F[i][j]
+ * (the jump–jump product; the sign of K is TB_FORM_DIFFUSION's).  dΓ is the average of the two sides' facet measures at the paired point
+ * (getdetJdV_average): |∂x/∂s × ∂x/∂t| of the bilinear facet, or the edge length element.
+ * tb_interface_assemble ADDS to d_nzval (call it after the bulk diffusion assembly, like tb_facet_assemble).  The pattern must hold all couplings
+ * among the 2·nf dofs of every interface element (TB_ERR_PATTERN otherwise).  The sum is ordered — per non-zero: ascending interface element, then
+ * local entry — without floating-point atomics: two assemblies give identical bits.  A non-positive or non-finite facet measure raises the status
+ * block (TB_ERR_NEG_DETJ, naming cell_a).  The form is released by tb_form_destroy. */
+int tb_interface_form_create(tb_mesh *mesh, const int32_t *records, const int32_t *pairing, int64_t n, int facet_qpoints, double G,
+                             const double *G_per_element, int index_base, tb_form **out);
+int tb_interface_assemble(tb_form *form, tb_pattern *pat, double *d_nzval);
 
 /* 3D–0D chamber coupling of Regazzoni et al. 2022: the chamber pressure p is an unknown tied to the cavity volume by a Lagrange-multiplier row
  * (Pressure3D0DVolumeCouplerIntegrator, src/modeling/coupler/fsi.jl:118-185).  Volume integrands V(x, d, F, n₀):

@@ -783,6 +783,25 @@ facet_set_param!(form::Ptr{Cvoid}, param::Real) = check(ccall((:tb_facet_form_se
 facet_set_field!(form::Ptr{Cvoid}, field::Vector{Float64}) = check(ccall((:tb_facet_form_set_field, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), form, field, length(field)))
 facet_assemble!(form::Ptr{Cvoid}, A::HIPSparseMatrixCSR{Float64}, u::HIPVector{Float64}, r::HIPVector{Float64}, t::Real) =
     check(ccall((:tb_facet_assemble, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Float64}), form, A.ddh.pattern, u.ptr, t, A.nzval.ptr, r.ptr))
+# Diffusion across the interface between two subdomains (InterfaceDiffusionModel / BilinearInterfaceDiffusionIntegrator, src/modeling/core/diffusion.jl:76-157).
+# `records` holds (cell_a, local_facet_a, cell_b, local_facet_b) per interface element and `pairing` the local vertex of cell_b that copies the k-th
+# facet node of a (both 1-based, column-major 4 × n and nf × n); G is one conductance or one per interface element.  interface_assemble! ADDS the
+# jump–jump term to the values of a matrix whose pattern holds the couplings among every interface element's dofs: call it after the bulk diffusion
+# assembly (update_operator!), like facet_assemble!.  The sum is ordered: two assemblies give the same bits.
+struct HIPInterfaceForm
+    form::Ptr{Cvoid}
+    n::Int
+end
+function HIPInterfaceForm(ddh::DeviceDofHandler, records::Matrix{Int32}, pairing::Matrix{Int32}, G::Union{Real, Vector{Float64}}; facet_qpoints = 0)
+    form = Ref{Ptr{Cvoid}}(C_NULL)
+    n = size(records, 2)
+    per = G isa Vector{Float64} ? G : Ptr{Float64}(C_NULL)
+    check(ccall((:tb_interface_form_create, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Int64, Cint, Cdouble, Ptr{Float64}, Cint, Ref{Ptr{Cvoid}}),
+        ddh.mesh, records, pairing, n, facet_qpoints, G isa Real ? Float64(G) : 0.0, per, 1, form))
+    return HIPInterfaceForm(form[], n)
+end
+interface_assemble!(f::HIPInterfaceForm, A::HIPSparseMatrixCSR{Float64}) =
+    check(ccall((:tb_interface_assemble, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}), f.form, A.ddh.pattern, A.nzval.ptr))
 # 3D–0D chamber coupling (src/modeling/coupler/fsi.jl:118-185, src/modeling/rsafdq2022.jl:22-85): one form per chamber surface; chamber_assemble! ADDS the
 # follower-load tangent / residual at pressure p, the J_dp column, the J_pd row and the chamber volume (one device double).  Every output is optional:
 # `nothing` passes C_NULL and the library skips it (chamber_assemble!(form, nothing, u, 0.0; volume = v) is compute_chamber_volume)

@@ -27,3 +27,7 @@ from .ecg import (Plonsey1964ECGGaussCache, PoissonECGReconstructionCache, Gesel
                   get_closest_vertex, cellset_coefficient, lead_right_hand_sides, vertex_dofs, scrub_scale)
 from . import dynamics  # noqa: F401
 from .dynamics import ElastodynamicsModel, NewmarkSolver, NewmarkStageOperator, NewmarkIntegrator, Dirichlet, LinearMaxwellMaterial  # noqa: F401
+from . import multidomain  # noqa: F401
+from .multidomain import (insert_interfaces, InterfaceRecords, interface_dofs, extract_subgrid, NoStimulationProtocol, MonodomainModel,  # noqa: F401
+                          InterfaceDiffusionModel, ReactionDiffusionSplit, InterfaceDiffusionForm, PointwiseMultiODEFunction, MultiSolverCache,
+                          MultiDomainFunction, plan_ep, semidiscretize_ep, MultiDomainHeatStage, MultiDomainLieTrotterGodunov, heat_dofrange_of, QUAD_FACETS)

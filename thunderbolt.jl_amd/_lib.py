@@ -13,6 +13,7 @@ TB_ERR_BAD_ARG, TB_ERR_HIP, TB_ERR_NEG_DETJ, TB_ERR_PATTERN, TB_ERR_UNSUPPORTED,
 TB_QUAD4, TB_HEX8, TB_TET4, TB_HEX27, TB_TET10 = 2, 3, 4, 5, 6
 TB_STRATEGY_ATOMIC, TB_STRATEGY_PER_COLOR, TB_STRATEGY_ELEMENT, TB_STRATEGY_PATCH = 0, 1, 2, 3
 TB_FORM_MASS, TB_FORM_DIFFUSION, TB_FORM_SOURCE, TB_FORM_HYPERELASTIC = 0, 1, 2, 3
+TB_FORM_INTERFACE = 6
 TB_MATERIAL_HOLZAPFEL_OGDEN_2009 = 0
 TB_BC_ROBIN, TB_BC_NORMAL_SPRING, TB_BC_PRESSURE, TB_BC_BENDING_SPRING, TB_BC_PRESSURE_FIELD = 0, 1, 2, 3, 4
 TB_VOLUME_RSAFDQ2022, TB_VOLUME_HIRSCHVOGEL2017 = 0, 1
@@ -119,6 +120,8 @@ SIGNATURES = {
     "tb_facet_form_set_field": (C.c_int, [vp, c_dp, C.c_int64]),
     "tb_facet_form_set_param": (C.c_int, [vp, C.c_double]),
     "tb_facet_assemble": (C.c_int, [vp, vp, vp, C.c_double, vp, vp]),
+    "tb_interface_form_create": (C.c_int, [vp, c_i32p, c_i32p, C.c_int64, C.c_int, C.c_double, c_dp, C.c_int, C.POINTER(vp)]),
+    "tb_interface_assemble": (C.c_int, [vp, vp, vp]),
     "tb_chamber_form_create": (C.c_int, [vp, C.c_int, c_dp, C.c_int, c_i32p, C.c_int64, C.c_int, C.POINTER(vp)]),
     "tb_chamber_assemble": (C.c_int, [vp, vp, vp, C.c_double, vp, vp, vp, vp, vp]),
     "tb_locator_create": (C.c_int, [vp, C.c_int64, vp, C.c_double, C.POINTER(vp)]),

@@ -509,9 +509,14 @@ class SparsityPattern:
         return int(self.rowptr[-1])
 
 
-def allocate_matrix(dh):
-    """Sparsity pattern of allocate_matrix(dh), as CSR (create_system_matrix, src/solver/interface.jl:162-168)."""
+def allocate_matrix(dh, interfaces=None):
+    """Sparsity pattern of allocate_matrix(dh), as CSR (create_system_matrix, src/solver/interface.jl:162-168).  `interfaces`: the records of
+    insert_interfaces (multidomain.py) — the pattern is then the union of the cell couplings and, per interface element, all couplings among its
+    2·nf dofs (an interface element has as many dofs as a cell of its mesh, so its rows are appended to the cell table)."""
     cd = dh.cell_dofs
+    if interfaces is not None and len(interfaces):
+        from .multidomain import interface_dofs
+        cd = np.ascontiguousarray(np.vstack([cd, interface_dofs(dh, interfaces)]), dtype=np.int32)
     rowptr = np.empty(dh.ndofs + 1, dtype=np.int64)
     nnz = lib().tb_host_build_pattern(cd.shape[0], cd.shape[1], cd.ctypes.data_as(L.c_i32p), dh.ndofs,
                                       rowptr.ctypes.data_as(L.c_i64p), None)
@@ -959,6 +964,8 @@ class PointwiseODEFunction:
 
 
 def solution_size(f):
+    if hasattr(f, "functions"):                # PointwiseMultiODEFunction (multidomain.py): the sum over its children
+        return sum(solution_size(c) for c in f.functions)
     return f.npoints * f.ode.nstates
 
 
@@ -1003,6 +1010,8 @@ class PointwiseSolverCache:
 
 
 def setup_solver_cache(f, solver, t0=0.0, u=None, keep_du=True):
+    if hasattr(f, "functions"):                # PointwiseMultiODEFunction (multidomain.py): one cache per child on its view of the packed state
+        return f.setup_solver_cache(solver, u=u, keep_du=keep_du)
     return PointwiseSolverCache(f, solver, u=u, keep_du=keep_du)
 
 
@@ -1211,6 +1220,12 @@ class ReactionTangentController:
 
     def step(self, t, dt):
         """One LTG step of length dt; returns (ok, next dt)."""
+        if hasattr(self.ltg, "step_with_reaction_tangent"):                        # MultiDomainLieTrotterGodunov: R = the maximum over its children
+            ok, R = self.ltg.step_with_reaction_tangent(t, dt)
+            if not ok:
+                return False, dt
+            self.R = R
+            return ok, self.stepsize(self.R)
         ok = self.ltg.heat.perform_step(self.ltg.phi, t, dt)
         if not ok:
             return False, dt

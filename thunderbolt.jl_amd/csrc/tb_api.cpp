@@ -1,6 +1,7 @@
 // tb_api.cpp — C-ABI entry points (include/tbhip.h): objects, memory, argument checking, error strings.
 // No arithmetic of the path lives here; kernels are in tb_assembly.hip / tb_reaction.hip / tb_algebra.hip / tb_spmv.hip / tb_krylov.hip.
 #include <algorithm>
+#include <atomic>
 #include <mutex>
 #include <cmath>
 #include <cstdarg>
@@ -411,6 +412,7 @@ int tb_pattern_create(tb_mesh *mesh, int64_t n_rows, const int64_t *rowptr, cons
     std::unique_ptr<tb_pattern, int (*)(tb_pattern *)> p(new tb_pattern, tb_pattern_destroy); // error returns free the device arrays too
     p->mesh = mesh;
     p->n_rows = n_rows;
+    { static std::atomic<uint64_t> serial{0}; p->serial = ++serial; }
     copy_rebased(p->h_rowptr, rowptr, (size_t)n_rows + 1, index_base);
     TB_REQUIRE(p->h_rowptr[0] == 0, "tb_pattern_create: rowptr does not start at index_base");
     p->nnz = p->h_rowptr[n_rows];
@@ -520,6 +522,7 @@ int tb_form_destroy(tb_form *f)
 {
     if (!f) return TB_OK;
     hipFree(f->d_field); hipFree(f->d_dtab); hipFree(f->d_gtab); hipFree(f->d_table); hipFree(f->d_facets); hipFree(f->d_act_field); hipFree(f->d_qp_buf); hipFree(f->d_cellset); if (f->set_colors) hipFree(f->set_colors->d_cells);
+    if (f->iface) free_interface_data(f->iface.get());
     delete f;
     return TB_OK;
 }

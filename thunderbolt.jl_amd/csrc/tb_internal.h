@@ -181,6 +181,24 @@ struct VecPatchPlan {
 // of a device live in tb_device::d_slots and are zero between uses.  Every user launches on the device's one stream, which is what orders them.
 constexpr int RED_SLOTS = 64, RED_STRIDE = 16, RED_GROUP = RED_SLOTS * RED_STRIDE; // doubles
 
+// Interface diffusion form (tb_interface.hip): the zero-thickness interface elements between two subdomains, their facet matrices and — per pattern —
+// the contribution list of the ordered gather (tb_interface_planners.hpp)
+struct InterfaceData {
+    int nf = 0, fq = 2;              // nodes per facet (2: quadrilateral edges, 4: hexahedron faces), Gauss points per facet direction
+    int64_t n = 0;                   // interface elements
+    double G = 0.0;
+    std::vector<int32_t> h_edofs;    // n × 2nf dofs: a's facet dofs in Ferrite's facet-node order, then their copies on b
+    int32_t *d_nodes = nullptr;      // n × 2nf grid nodes, the same order
+    int32_t *d_cell_a = nullptr;     // cell of side a (what an error report names)
+    double *d_G = nullptr;           // conductance per interface element, or NULL: G
+    double *d_fm = nullptr;          // n × nf² facet matrices G ∫ N_i N_j dΓ
+    uint64_t planned_for = 0;        // serial of the pattern the plan below was built for (0: none)
+    int64_t n_touched = 0;
+    int64_t *d_nz = nullptr, *d_ptr = nullptr;
+    uint32_t *d_src = nullptr;
+};
+void free_interface_data(InterfaceData *d); // tb_interface.hip
+
 } // namespace tb
 
 struct tb_pattern;
@@ -230,6 +248,7 @@ struct tb_mesh {
 struct tb_pattern {
     tb_mesh *mesh = nullptr;
     int64_t n_rows = 0, nnz = 0;
+    uint64_t serial = 0;            // unique per tb_pattern_create: what a plan cached outside the pattern (tb_interface.hip) is keyed by
     int64_t *d_rowptr = nullptr;
     int32_t *d_colidx = nullptr;
     std::vector<int64_t> h_rowptr;
@@ -325,6 +344,8 @@ struct tb_form {
     // chamber volume coupling (TB_FORM_CHAMBER): V = −J (H (x + d − b)) · F⁻ᵀ n₀
     int chamber_method = 0;
     double chamber_H[9] = {0}, chamber_b[3] = {0};
+    // interface diffusion between two subdomains (TB_FORM_INTERFACE)
+    std::unique_ptr<tb::InterfaceData> iface;
 };
 
 namespace tb {
