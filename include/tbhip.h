@@ -101,7 +101,8 @@ enum {
     TB_FORM_FACET = 4,       /* weak boundary conditions on hexahedron / tetrahedron facets   src/modeling/core/weak_boundary_conditions.jl */
     TB_FORM_INTERFACE = 6,   /* diffusion across zero-thickness interface elements (tb_interface_form_create)   src/modeling/core/diffusion.jl:76-157 */
     TB_FORM_CHAMBER = 5,     /* 3D–0D chamber coupling on hexahedron facets (tb_chamber_form_create)   src/modeling/coupler/fsi.jl:118-185 */
-    TB_FORM_HYPERELASTIC = 3 /* rₑ[i] += ∇δuᵢ⊡P dΩ, Kₑ[i,j] += (∇δuᵢ⊡𝔸)⊡∇δuⱼ dΩ   src/modeling/solid/elements.jl:177-313 */
+    TB_FORM_HYPERELASTIC = 3, /* rₑ[i] += ∇δuᵢ⊡P dΩ, Kₑ[i,j] += (∇δuᵢ⊡𝔸)⊡∇δuⱼ dΩ   src/modeling/solid/elements.jl:177-313 */
+    TB_FORM_VISCOELASTIC = 7  /* the same integrals with the LinearMaxwellMaterial stress and condensed tangent (tb_viscoelastic_create)   src/modeling/solid/materials.jl:1816-2008 */
 };
 
 /* coefficients (src/modeling/core/coefficients.jl, src/modeling/microstructure.jl).  Julia closures cannot
@@ -192,6 +193,8 @@ const char *tb_version(void);
  * the mass form of a 3-component field, which it used to refuse (scalar calls are unchanged).
  * Added under 10, purely additive: tb_mg_set_p_transfer, tb_mg_level_plan, tb_mg_galerkin (p-multigrid); tb_mg_set_level accepts a TB_HEX27 field, which it used
  * to refuse (first-order calls are unchanged).
+ * Added under 10, purely additive: tb_viscoelastic_create, tb_host_maxwell_eval (LinearMaxwellMaterial); the entries listed with tb_viscoelastic_create accept
+ * the new form kind, which did not exist before.
  * A host binding compares tb_abi_revision() with the
  * TB_ABI_REVISION it was written against and refuses to run on a mismatch (julia/ThunderboltHIPBackend.jl does, in __init__) */
 #define TB_ABI_REVISION 10
@@ -368,6 +371,32 @@ int tb_hyperelastic_set_internal_state(tb_form *form, double *d_state, const dou
  * gains ∂P/∂Ḟ/Δt and the non-symmetric term ∂P/∂Q · ∂Q/∂λ̇ ⊗ (∂²λ/∂F² : Ḟ): use a general linear solver (tb_gmres_solve). */
 int tb_hyperelastic_set_previous_solution(tb_form *form, const double *d_u_prev);
 int tb_hyperelastic_local_solve_report(tb_form *form, int64_t *n_failed, int32_t *status_host, int64_t len);
+
+/* Quasi-static small-strain viscoelasticity: LinearMaxwellMaterial (src/modeling/solid/materials.jl:1816-2008; the reference's test sets
+ * "Viscoelasticity" and "Internal variables are stored per cell", test/integration/test_solid_mechanics.jl:768-848).  ε = sym(F − I),
+ * ℂ = λ̃ I⊗I + 2μ̃ 𝕀ˢʸᵐ with λ̃ = ν/((1+ν)(1−2ν)), 2μ̃ = 1/(1+ν):
+ *   stress (:1960-1967)                          σ = E₀ ℂ:ε + E₁ ℂ:(ε − εᵛ₁), used as P in rₑ[i] += ∇δuᵢ ⊡ σ dΩ
+ *   local problem, backward Euler (:1854-1879)   (𝕀/Δt + (E₁/η₁)ℂ) : εᵛ₁ = εᵛ₀/Δt + (E₁/η₁)ℂ : ε, re-solved in every assembly from the accepted εᵛ₀
+ *   tangent with the condensation term (:1881-1936, :1976-1985)   ∂σ/∂ε = (E₀+E₁)ℂ − E₁ ℂ : (𝕀/Δt + (E₁/η₁)ℂ)⁻¹ : (E₁/η₁)ℂ
+ * evaluated in closed form on the spherical / deviatoric split (csrc/tb_maxwell.hpp).  params = {E₀, E₁, μ, η₁, ν}, n_params = 5 (μ is carried and
+ * unused, as in the reference).  TB_ERR_BAD_ARG for non-finite values, η₁ ≤ 0, E₀ < 0, E₁ < 0, ν ≤ −1, ν ≥ 0.5 and scalar fields; E₁ = 0 is the
+ * purely elastic material (εᵛ₁ = εᵛ₀).  Field kinds TB_HEX8 (2×2×2 Gauss), TB_HEX27 (3×3×3), TB_TET4 (4-point rule), TB_TET10 (Keast 8-point) —
+ * the rules of tb_hyperelastic_create for qorder = 0; qorder takes 0 or that rule's own number (2 for first-order, 3 for second-order fields).
+ * The form has its own kind (TB_FORM_VISCOELASTIC) and is accepted by tb_residual, tb_linearize, tb_hyperelastic_n_quadrature_points,
+ * tb_hyperelastic_set_internal_state, tb_hyperelastic_local_solve_report (the local problem is linear: always 0 failures, every status
+ * TB_LOCAL_SUCCESS), tb_form_set_cellset, tb_form_clear_cellset, tb_form_set_accumulate and tb_form_destroy; every other entry that takes a form
+ * refuses it with TB_ERR_BAD_ARG.  Assembling without a state or with Δt ≤ 0 fails with TB_ERR_BAD_ARG like the sarcomere path.
+ * State layout: SIX values per quadrature point in the convention above — state-major, point-fastest, point = cell · n_qp + q, i.e. component s of
+ * point p at d_state[s · n_points + p] — the components in the order of the reference's SymmetricTensor{2,3}.data: (11, 21, 31, 22, 32, 33).
+ * Every assembly (tb_residual too: solve_local_constraint_state_only) writes εᵛ₁ of the cells it visits into d_state; the points of cells outside a
+ * cell set are neither read nor written.  Strategies: hexahedra as the hyperelastic forms (ELEMENT / PATCH: stored Kₑ / rₑ and the ordered gather,
+ * two assemblies give identical bits; PER_COLOR; ATOMIC); tetrahedra: ELEMENT and PER_COLOR the coloured ordered sweep, ATOMIC, PATCH the one
+ * measured faster (atomics, for both fields).  Subdomain and accumulating forms: PER_COLOR or ATOMIC.  tb_last_kernel_name: "k_viscoelastic<Q1|Q2|P1|P2,K+r|K|r>(…)". */
+int tb_viscoelastic_create(tb_mesh *mesh, int qorder, const double *params, int n_params, tb_form **out);
+/* the point routine of the viscoelastic kernels on the host: F row-major F[3i+j], Qknown6 / Q6 in the component order above (Qknown6 NULL: zero),
+ * P = σ (3 × 3, row-major), A[9(3i+j)+3k+l] = ∂σ_ij/∂F_kl with the condensation term (minor symmetries: σ depends on sym(F − I) only).
+ * Q6, P, A may be NULL. */
+int tb_host_maxwell_eval(const double *params, int n_params, const double *F, const double *Qknown6, double dt, double *Q6, double *P, double *A);
 
 /* Weak boundary conditions of a quasi-static problem (src/modeling/core/weak_boundary_conditions.jl): RobinBC
  * Ψ = α u·u (:102-198), NormalSpringBC Ψ = ½ kₛ (u·N)² (:200-300), ConstantPressureBC follower load p·J·F⁻ᵀ·n₀ with its

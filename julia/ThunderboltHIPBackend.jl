@@ -614,7 +614,7 @@ end
 # ---------------------------------------------------------------- round 6: the rest of the boundary the hot path's rows of SURVEY §8 use, bound the same way
 # (device queue and events; pattern accessors; Rush–Larsen and RTC reaction steps; the other Krylov entries; cell sets and accumulation of a form; facet
 # forms; sarcomere steps and the condensed-mechanics setters).  The host generators (tb_host_generate_grid_*, tb_host_close_dofs, tb_host_build_pattern,
-# tb_host_perturb_nodes) and the host-side evaluators (tb_host_material_eval*, tb_host_sarcomere_*) stay unbound: Ferrite and the reference's own Julia
+# tb_host_perturb_nodes) and the host-side evaluators (tb_host_material_eval*, tb_host_sarcomere_*; tb_host_maxwell_eval is bound) stay unbound: Ferrite and the reference's own Julia
 # routines are the host side of those.
 libtbhip_version() = unsafe_string(ccall((:tb_version, libtbhip), Cstring, ()))
 # the library's kernels on a queue the host framework owns (its own stream, or the legacy default stream) — ordering with the host's device work then needs no events
@@ -937,6 +937,21 @@ function local_solve_report(form::Ptr{Cvoid})
     nf = Ref{Int64}(0)
     check(ccall((:tb_hyperelastic_local_solve_report, libtbhip), Cint, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int32}, Int64), form, nf, C_NULL, 0))
     return Int(nf[])
+end
+# LinearMaxwellMaterial (src/modeling/solid/materials.jl:1816-2008): a form of its own kind over the same entries as the condensed sarcomere path —
+# set_internal_state! (six values per quadrature point, SymmetricTensor{2,3}.data order), n_quadrature_points, local_solve_report, linearize / residual
+function viscoelastic_form(mesh::Ptr{Cvoid}, E₀::Real, E₁::Real, μ::Real, η₁::Real, ν::Real)
+    form = Ref{Ptr{Cvoid}}(C_NULL)
+    p = Float64[E₀, E₁, μ, η₁, ν]
+    check(ccall((:tb_viscoelastic_create, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Cint, Ref{Ptr{Cvoid}}), mesh, 0, p, length(p), form))
+    return form[]
+end
+# the kernels' point routine on the host: (εᵛ₁, σ, ∂σ/∂F) of one local backward-Euler step from Qknown; F and σ row-major
+function host_maxwell_eval(p::Vector{Float64}, F::Vector{Float64}, Qknown::Vector{Float64}, Δt::Real)
+    Q = zeros(6); P = zeros(9); A = zeros(81)
+    check(ccall((:tb_host_maxwell_eval, libtbhip), Cint, (Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        p, length(p), F, Qknown, Δt, Q, P, A))
+    return Q, P, A
 end
 function comm_rank_size(c::HIPComm)
     r = Ref{Cint}(0); n = Ref{Cint}(0)

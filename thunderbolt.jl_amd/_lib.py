@@ -14,6 +14,7 @@ TB_QUAD4, TB_HEX8, TB_TET4, TB_HEX27, TB_TET10 = 2, 3, 4, 5, 6
 TB_STRATEGY_ATOMIC, TB_STRATEGY_PER_COLOR, TB_STRATEGY_ELEMENT, TB_STRATEGY_PATCH = 0, 1, 2, 3
 TB_FORM_MASS, TB_FORM_DIFFUSION, TB_FORM_SOURCE, TB_FORM_HYPERELASTIC = 0, 1, 2, 3
 TB_FORM_INTERFACE = 6
+TB_FORM_VISCOELASTIC = 7
 TB_MATERIAL_HOLZAPFEL_OGDEN_2009 = 0
 TB_BC_ROBIN, TB_BC_NORMAL_SPRING, TB_BC_PRESSURE, TB_BC_BENDING_SPRING, TB_BC_PRESSURE_FIELD = 0, 1, 2, 3, 4
 TB_VOLUME_RSAFDQ2022, TB_VOLUME_HIRSCHVOGEL2017 = 0, 1
@@ -114,6 +115,8 @@ SIGNATURES = {
     "tb_hyperelastic_n_quadrature_points": (C.c_int, [vp, C.POINTER(C.c_int64)]),
     "tb_hyperelastic_set_internal_state": (C.c_int, [vp, vp, vp, C.c_double]),
     "tb_hyperelastic_local_solve_report": (C.c_int, [vp, C.POINTER(C.c_int64), vp, C.c_int64]),
+    "tb_viscoelastic_create": (C.c_int, [vp, C.c_int, c_dp, C.c_int, C.POINTER(vp)]),
+    "tb_host_maxwell_eval": (C.c_int, [c_dp, C.c_int, c_dp, c_dp, C.c_double, c_dp, c_dp, c_dp]),
     "tb_hyperelastic_set_hill": (C.c_int, [vp, vp]),
     "tb_host_material_eval_hill": (C.c_int, [vp, vp, C.c_double, c_dp, c_dp, c_dp, c_dp]),
     "tb_facet_form_create": (C.c_int, [vp, C.c_int, C.c_double, C.c_int, c_i32p, C.c_int64, C.c_int, C.POINTER(vp)]),

@@ -964,6 +964,8 @@ class PointwiseODEFunction:
 
 
 def solution_size(f):
+    if isinstance(f, NonlinearOperator):       # quasi-static operator (solid.py): the displacement dofs plus the condensed internal variables of every
+        return f.dh.ndofs + (0 if f.internal is None else f.internal.n_states * f.internal.n_points)   # quadrature point (test_solid_mechanics.jl:788)
     if hasattr(f, "functions"):                # PointwiseMultiODEFunction (multidomain.py): the sum over its children
         return sum(solution_size(c) for c in f.functions)
     return f.npoints * f.ode.nstates

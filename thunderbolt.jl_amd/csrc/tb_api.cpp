@@ -659,7 +659,7 @@ int tb_hyperelastic_set_prestress(tb_form *form, const double *F0inv)
 
 int tb_form_set_cellset(tb_form *form, const int32_t *cells, int64_t n_cells, int index_base)
 {
-    TB_REQUIRE(form && form->kind == TB_FORM_HYPERELASTIC, "tb_form_set_cellset: subdomains are implemented for hyperelastic forms");
+    TB_REQUIRE(form && (form->kind == TB_FORM_HYPERELASTIC || form->kind == TB_FORM_VISCOELASTIC), "tb_form_set_cellset: subdomains are implemented for hyperelastic forms");
     TB_REQUIRE(index_base == 0 || index_base == 1, "tb_form_set_cellset: index_base must be 0 or 1");
     TB_REQUIRE(n_cells >= 0 && (cells || n_cells == 0), "tb_form_set_cellset: bad cell list");
     hipFree(form->d_cellset); form->d_cellset = nullptr;
@@ -694,7 +694,7 @@ int tb_form_clear_cellset(tb_form *form)
 
 int tb_form_set_accumulate(tb_form *form, int accumulate)
 {
-    TB_REQUIRE(form && form->kind == TB_FORM_HYPERELASTIC, "tb_form_set_accumulate: implemented for hyperelastic forms");
+    TB_REQUIRE(form && (form->kind == TB_FORM_HYPERELASTIC || form->kind == TB_FORM_VISCOELASTIC), "tb_form_set_accumulate: implemented for hyperelastic forms");
     form->accumulate = accumulate != 0;
     return TB_OK;
 }
@@ -717,7 +717,7 @@ int tb_hyperelastic_set_condensation(tb_form *form, int sarcomere_model, const d
 
 int tb_hyperelastic_n_quadrature_points(tb_form *form, int64_t *n_points)
 {
-    TB_REQUIRE(form && form->kind == TB_FORM_HYPERELASTIC && n_points, "tb_hyperelastic_n_quadrature_points: bad argument");
+    TB_REQUIRE(form && (form->kind == TB_FORM_HYPERELASTIC || form->kind == TB_FORM_VISCOELASTIC) && n_points, "tb_hyperelastic_n_quadrature_points: bad argument");
     const int nq = form->mesh->field_kind == TB_TET4 ? 4 : form->mesh->field_kind == TB_TET10 ? 8 : form->qorder * form->qorder * form->qorder;
     *n_points = form->mesh->n_cells * nq;
     return TB_OK;
@@ -725,8 +725,8 @@ int tb_hyperelastic_n_quadrature_points(tb_form *form, int64_t *n_points)
 
 int tb_hyperelastic_set_internal_state(tb_form *form, double *d_state, const double *d_state_known, double dt)
 {
-    TB_REQUIRE(form && form->kind == TB_FORM_HYPERELASTIC, "tb_hyperelastic_set_internal_state: not a hyperelastic form");
-    TB_REQUIRE(form->cond_model, "tb_hyperelastic_set_internal_state: the form has no condensed internal variable (tb_hyperelastic_set_condensation)");
+    TB_REQUIRE(form && (form->kind == TB_FORM_HYPERELASTIC || form->kind == TB_FORM_VISCOELASTIC), "tb_hyperelastic_set_internal_state: not a hyperelastic form");
+    TB_REQUIRE(form->cond_model || form->kind == TB_FORM_VISCOELASTIC, "tb_hyperelastic_set_internal_state: the form has no condensed internal variable (tb_hyperelastic_set_condensation)");
     TB_REQUIRE(d_state && d_state_known, "tb_hyperelastic_set_internal_state: NULL state");
     TB_REQUIRE(dt > 0.0, "tb_hyperelastic_set_internal_state: the time step must be positive (got %g)", dt);
     form->d_Q = d_state; form->d_Qknown = d_state_known; form->cond_dt = dt;
@@ -743,6 +743,16 @@ int tb_hyperelastic_set_previous_solution(tb_form *form, const double *d_u_prev)
 
 int tb_hyperelastic_local_solve_report(tb_form *form, int64_t *n_failed, int32_t *status_host, int64_t len)
 {
+    if (form && form->kind == TB_FORM_VISCOELASTIC) { // the local problem is linear and solved in closed form: it cannot fail
+        if (n_failed) *n_failed = 0;
+        if (status_host) {
+            int64_t npts = 0;
+            tb_hyperelastic_n_quadrature_points(form, &npts);
+            TB_REQUIRE(len == npts, "tb_hyperelastic_local_solve_report: status buffer has %lld entries, expected %lld", (long long)len, (long long)npts);
+            for (int64_t i = 0; i < npts; ++i) status_host[i] = TB_LOCAL_SUCCESS;
+        }
+        return TB_OK;
+    }
     TB_REQUIRE(form && form->kind == TB_FORM_HYPERELASTIC && form->cond_model, "tb_hyperelastic_local_solve_report: the form has no condensed internal variable");
     if (n_failed) *n_failed = form->cond_n_failed;
     if (status_host) {
@@ -805,12 +815,13 @@ int tb_residual(tb_form *form, int strategy, const double *d_u, double t, double
 {
     (void)t;
     TB_REQUIRE(form && d_u && d_r, "tb_residual: NULL argument");
-    TB_REQUIRE(form->kind == TB_FORM_HYPERELASTIC, "tb_residual: form is not nonlinear");
+    TB_REQUIRE(form->kind == TB_FORM_HYPERELASTIC || form->kind == TB_FORM_VISCOELASTIC, "tb_residual: form is not nonlinear");
     TB_HIP(hipSetDevice(form->mesh->dev->id));
     if (form->mesh->n_cells == 0) {
         TB_HIP(hipMemsetAsync(d_r, 0, sizeof(double) * (size_t)form->mesh->ndofs, form->mesh->dev->stream));
         return TB_OK;
     }
+    if (form->kind == TB_FORM_VISCOELASTIC) return launch_viscoelastic(form, nullptr, strategy, d_u, nullptr, d_r);
     return launch_hyperelastic(form, nullptr, strategy, d_u, nullptr, d_r);
 }
 
@@ -818,7 +829,7 @@ int tb_linearize(tb_form *form, tb_pattern *pat, int strategy, const double *d_u
 {
     (void)t;
     TB_REQUIRE(form && pat && d_u && (d_nzval || pat->nnz == 0), "tb_linearize: NULL argument");
-    TB_REQUIRE(form->kind == TB_FORM_HYPERELASTIC, "tb_linearize: form is not nonlinear");
+    TB_REQUIRE(form->kind == TB_FORM_HYPERELASTIC || form->kind == TB_FORM_VISCOELASTIC, "tb_linearize: form is not nonlinear");
     TB_REQUIRE(form->mesh == pat->mesh, "tb_linearize: form and pattern belong to different meshes");
     TB_HIP(hipSetDevice(form->mesh->dev->id));
     if (form->mesh->n_cells == 0) {
@@ -826,7 +837,47 @@ int tb_linearize(tb_form *form, tb_pattern *pat, int strategy, const double *d_u
         if (d_r) TB_HIP(hipMemsetAsync(d_r, 0, sizeof(double) * (size_t)form->mesh->ndofs, form->mesh->dev->stream));
         return TB_OK;
     }
+    if (form->kind == TB_FORM_VISCOELASTIC) return launch_viscoelastic(form, pat, strategy, d_u, d_nzval, d_r);
     return launch_hyperelastic(form, pat, strategy, d_u, d_nzval, d_r);
+}
+
+// ------------------------------------------------------------------ quasi-static viscoelasticity (LinearMaxwellMaterial)
+static int validate_maxwell(const char *who, const double *params, int n_params)
+{
+    TB_REQUIRE(params && n_params == 5, "%s: LinearMaxwellMaterial takes 5 parameters {E0, E1, mu, eta1, nu}", who);
+    for (int i = 0; i < 5; ++i) TB_REQUIRE(std::isfinite(params[i]), "%s: parameter %d is not finite", who, i);
+    TB_REQUIRE(params[3] > 0.0, "%s: the viscosity eta1 must be positive (got %g)", who, params[3]);
+    TB_REQUIRE(params[0] >= 0.0 && params[1] >= 0.0, "%s: the moduli E0, E1 must not be negative (got %g, %g)", who, params[0], params[1]);
+    TB_REQUIRE(params[4] > -1.0 && params[4] < 0.5, "%s: Poisson's ratio must lie in (-1, 0.5) (got %g)", who, params[4]);
+    return TB_OK;
+}
+
+int tb_viscoelastic_create(tb_mesh *mesh, int qorder, const double *params, int n_params, tb_form **out)
+{
+    TB_REQUIRE(mesh && out, "tb_viscoelastic_create: NULL argument");
+    *out = nullptr;
+    TB_TRY(validate_maxwell("tb_viscoelastic_create", params, n_params));
+    TB_REQUIRE(mesh->ncomp == 3 && (mesh->geom_kind == TB_HEX8 || mesh->geom_kind == TB_TET4), "tb_viscoelastic_create: needs a 3-component field on hexahedra or tetrahedra");
+    // the kernels address a node's three dofs as consecutive ids (Ferrite: node-major, component-minor, io.jl:233-238)
+    for (int64_t i = 0; i < mesh->n_cells * mesh->nb; ++i) {
+        const int32_t *d = &mesh->h_cell_dofs[3 * i];
+        TB_REQUIRE(d[1] == d[0] + 1 && d[2] == d[0] + 2, "tb_viscoelastic_create: dofs of a node are not consecutive (cell %lld)", (long long)(i / mesh->nb));
+    }
+    const int rule = std::max(2 * kind_order(mesh->field_kind) - 1, 2);
+    TB_REQUIRE(qorder == 0 || qorder == rule, "tb_viscoelastic_create: quadrature order %d (this field takes 0 or %d)", qorder, rule);
+    auto f = std::make_unique<tb_form>();
+    f->mesh = mesh; f->kind = TB_FORM_VISCOELASTIC; f->qorder = rule;
+    for (int i = 0; i < 5; ++i) f->vis_p[i] = params[i];
+    *out = f.release();
+    return TB_OK;
+}
+
+int tb_host_maxwell_eval(const double *params, int n_params, const double *F, const double *Qknown6, double dt, double *Q6, double *P, double *A)
+{
+    TB_TRY(validate_maxwell("tb_host_maxwell_eval", params, n_params));
+    TB_REQUIRE(F, "tb_host_maxwell_eval: NULL argument");
+    TB_REQUIRE(dt > 0.0, "tb_host_maxwell_eval: the time step must be positive (got %g)", dt);
+    return host_maxwell_eval(params, F, Qknown6, dt, Q6, P, A);
 }
 
 int tb_facet_form_create(tb_mesh *mesh, int bc_kind, double param, int facet_qpoints, const int32_t *facets, int64_t n_facets,

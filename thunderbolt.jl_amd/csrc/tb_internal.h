@@ -330,6 +330,8 @@ struct tb_form {
     const double *d_u_prev = nullptr; // rate-coupled local problem: previous displacement (NULL: rate-free)
     double *d_qp_buf = nullptr, *d_qp_act = nullptr; // λ | Ca | (a, b) | status per quadrature point
     int64_t cond_n_failed = 0;
+    // LinearMaxwellMaterial (TB_FORM_VISCOELASTIC): {E₀, E₁, μ, η₁, ν}; the viscous strain lives in d_Q / d_Qknown (six per point), Δt in cond_dt
+    double vis_p[5] = {0};
     // PrestressedMechanicalModel: F₀⁻¹ (tb_hyperelastic_set_prestress)
     int prestressed = 0;
     double prestress_G[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
@@ -391,6 +393,10 @@ int launch_facets(tb_form *f, tb_pattern *p, const double *d_u, double *d_nz, do
 int ensure_blockpos(tb_pattern *p);
 int launch_hyperelastic_tet(tb_form *f, tb_pattern *p, int strategy, const double *d_u, double *d_nz, double *d_r);
 int launch_facets_tet(tb_form *f, tb_pattern *p, const double *d_u, double *d_nz, double *d_r);
+// tb_viscoelastic.hip
+int launch_viscoelastic(tb_form *f, tb_pattern *p, int strategy, const double *d_u, double *d_nz, double *d_r);
+int host_maxwell_eval(const double *params, const double *F, const double *Qknown6, double dt, double *Q6, double *P, double *A);
+// tb_chamber.hip
 int launch_chamber(tb_form *f, tb_pattern *p, const double *d_u, double pressure, double *d_nz, double *d_r, double *d_col, double *d_row, double *d_volume);
 // tb_newmark.hip
 int launch_assemble_vector_mass(tb_form *f, tb_pattern *p, int strategy, double *d_nz); // TB_FORM_MASS on a 3-component field

@@ -18,23 +18,16 @@ displacement d, the velocity v and the acceleration a are THREE device vectors i
 there is no combined vector and no mapping.
 
 Not in this module (NotImplementedError): condensed internal variables under Newmark (an ActiveStressModel over a sarcomere model with state —
-hence also the rate-coupled local problem, which needs the velocity anchor of newmark.jl:535-549), LinearMaxwellMaterial, and adaptive stepping
+hence also the rate-coupled local problem, which needs the velocity anchor of newmark.jl:535-549), LinearMaxwellMaterial under Newmark (its
+quasi-static form is solid.py's), and adaptive stepping
 (the Zienkiewicz–Xie error estimate, PIDController and the rollback of the acceleration, newmark.jl:606-698)."""
 import numpy as np
 
 from ._lib import check, lib
 from .api import (BilinearMassIntegrator, BilinearOperator, ConstantCoefficient, DeviceVector, FieldCoefficient, Hexahedron, _ptr, pcg_solve,
                   solve_converged)
-from .solid import (ActiveStressModel, ConstraintHandler, DisplacementSystem, NewtonRaphsonSolver, NonlinearOperator, PrestressedMechanicalModel,
+from .solid import (ActiveStressModel, ConstraintHandler, DisplacementSystem, LinearMaxwellMaterial, NewtonRaphsonSolver, NonlinearOperator, PrestressedMechanicalModel,
                     QuasiStaticModel, apply_zero, dot, nlsolve, residual, update_linearization)
-
-
-class LinearMaxwellMaterial:
-    """LinearMaxwellMaterial(E₀, E₁, μ, η₁, ν) of the reference: a viscoelastic material with a condensed viscous strain.  Held as a record only —
-    there is no device form of it; an ElastodynamicsModel over it is refused."""
-
-    def __init__(self, E0=70e3, E1=20e3, mu=1e3, eta1=1e3, nu=0.3):
-        self.E0, self.E1, self.mu, self.eta1, self.nu = E0, E1, mu, eta1, nu
 
 
 class Dirichlet:

@@ -390,6 +390,33 @@ class PressureFieldBC:
             self.param, self.field = 1.0, np.ascontiguousarray(pc.data, dtype=np.float64)
 
 
+class LinearMaxwellMaterial:
+    """LinearMaxwellMaterial(E₀, E₁, μ, η₁, ν) (src/modeling/solid/materials.jl:1816-2008): small-strain viscoelasticity, a spring E₀ℂ beside a
+    Maxwell branch E₁ℂ / η₁ whose viscous strain εᵛ is a condensed internal variable — a symmetric tensor per quadrature point, six values in
+    the order of the reference's SymmetricTensor{2,3}.data (11, 21, 31, 22, 32, 33).  μ is carried and unused, as in the reference.  Built on
+    the device for quasi-static problems (NonlinearOperator over a QuasiStaticModel, hexahedra and tetrahedra, first and second order); not
+    built under Newmark: an ElastodynamicsModel over it is refused."""
+
+    def __init__(self, E0=70e3, E1=20e3, mu=1e3, eta1=1e3, nu=0.3):
+        self.E0, self.E1, self.mu, self.eta1, self.nu = E0, E1, mu, eta1, nu
+
+    def params(self):
+        return np.array([self.E0, self.E1, self.mu, self.eta1, self.nu], dtype=np.float64)
+
+
+class ViscousStrainState:
+    """Viscous strains of a LinearMaxwellMaterial at n_points quadrature points on the device, (6, n_points), point-fastest; zero in the undeformed
+    reference state (default_initial_state!, materials.jl:1828)."""
+    n_states = 6
+
+    def __init__(self, device, n_points):
+        self.device, self.n_points = device, int(n_points)
+        self.u = device.zeros(6 * self.n_points)
+
+    def to_host(self):
+        return self.u.to_host().reshape(6, self.n_points)
+
+
 class QuasiStaticModel:
     """QuasiStaticModel(:u, constitutive_model, facet_models) (test/test_elements.jl:99-125, fem.jl:597-623)."""
 
@@ -397,9 +424,20 @@ class QuasiStaticModel:
         self.sym, self.constitutive_model, self.facet_models = sym, constitutive_model, tuple(facet_models)
 
 
-def material_routine(model, F, t=0.0):
-    """Host evaluation of the device material routine: (Ψ, P, 𝔸) with 𝔸[3i+j, 3k+l] = ∂P_ij/∂F_kl."""
+def material_routine(model, F, t=0.0, Qknown=None, dt=None):
+    """Host evaluation of the device material routine: (Ψ, P, 𝔸) with 𝔸[3i+j, 3k+l] = ∂P_ij/∂F_kl.  For a LinearMaxwellMaterial (which has no
+    energy): (εᵛ₁, σ, ∂σ/∂F) — the local backward-Euler step of length `dt` from the accepted viscous strain `Qknown` (six components, default
+    zero), the stress and the condensed tangent."""
     F = np.ascontiguousarray(F, dtype=np.float64)
+    if isinstance(model, LinearMaxwellMaterial):
+        if dt is None:
+            raise ValueError("material_routine(LinearMaxwellMaterial, F, Qknown=..., dt=...): the local problem needs the time step")
+        pp = model.params()
+        Q0 = np.zeros(6) if Qknown is None else np.ascontiguousarray(Qknown, dtype=np.float64).reshape(6)
+        Q1, P, A = np.zeros(6), np.zeros((3, 3)), np.zeros((9, 9))
+        check(lib().tb_host_maxwell_eval(pp.ctypes.data_as(L.c_dp), len(pp), F.ctypes.data_as(L.c_dp), Q0.ctypes.data_as(L.c_dp), float(dt),
+                                         Q1.ctypes.data_as(L.c_dp), P.ctypes.data_as(L.c_dp), A.ctypes.data_as(L.c_dp)))
+        return Q1, P, A
     psi = C.c_double()
     P = np.zeros((3, 3))
     A = np.zeros((9, 9))
@@ -430,11 +468,16 @@ class NonlinearOperator:
             raise ValueError("multi-domain operators accumulate: use PerColorAssemblyStrategy or AtomicAssemblyStrategy")
         for k, (name, qm) in enumerate(domains):
             cm = qm.constitutive_model
-            mat = cm.lower()
             form = C.c_void_p()
-            check(lib().tb_hyperelastic_create(self.dmesh.h, qorder, C.byref(mat), C.byref(form)))
-            self.forms.append((form, cm))
-            self._keep.append(mat)
+            if isinstance(cm, LinearMaxwellMaterial):
+                pp = cm.params()
+                check(lib().tb_viscoelastic_create(self.dmesh.h, qorder, pp.ctypes.data_as(L.c_dp), len(pp), C.byref(form)))
+                self.forms.append((form, cm))
+            else:
+                mat = cm.lower()
+                check(lib().tb_hyperelastic_create(self.dmesh.h, qorder, C.byref(mat), C.byref(form)))
+                self.forms.append((form, cm))
+                self._keep.append(mat)
             if name is not None:
                 cells = np.ascontiguousarray(dh.grid.getcellset(name), dtype=np.int32)
                 check(lib().tb_form_set_cellset(form, cells.ctypes.data_as(L.c_i32p), len(cells), 0))
@@ -466,6 +509,16 @@ class NonlinearOperator:
                 if not sm.rate_independent:      # rate-coupled local problem (QuasiStaticCondensedDAEElementCache): Ḟ from the previous displacement
                     self.u_prev = strategy.device.zeros(dh.ndofs)
                     check(lib().tb_hyperelastic_set_previous_solution(form, self.u_prev.ptr))
+            if isinstance(cm, LinearMaxwellMaterial):    # the second shape of condensed variable: a symmetric tensor per quadrature point
+                if self.internal is not None:
+                    raise NotImplementedError("one subdomain with condensed internal variables per operator")
+                self.internal_form = form
+                npts = C.c_int64()
+                check(lib().tb_hyperelastic_n_quadrature_points(form, C.byref(npts)))
+                self.internal = ViscousStrainState(strategy.device, npts.value)        # εᵛ of the current iterate / solution
+                self.internal_known = ViscousStrainState(strategy.device, npts.value)  # accepted εᵛ of the previous step
+                self.dt = None
+                self.u_prev = None
             # surface terms: one facet form per weak boundary condition (setup_boundary_cache, weak_boundary_conditions.jl:1-7)
             for bc in getattr(qm, "facet_models", ()):
                 fs = bc.boundary_name if not isinstance(bc.boundary_name, str) else dh.grid.facetset(bc.boundary_name)
@@ -504,6 +557,16 @@ def accept_internal_state(op):
 def reject_internal_state(op):
     """the time step was rejected: Q ← Q_known (initial guess of the retry)"""
     check(lib().tb_memcpy_d2d(op.strategy.device.h, op.internal.u.ptr, op.internal_known.u.ptr, op.internal.u.nbytes))
+
+
+def internal_variables(op):
+    """The condensed internal variables on the host as [cell][q][component] — the reference's per-cell block order in its solution vector
+    (test_solid_mechanics.jl:788-848 index it that way)."""
+    if op.internal is None:
+        raise ValueError("internal_variables: the operator has no condensed internal variables")
+    Q = op.internal.to_host()
+    ns = Q.shape[0]
+    return np.ascontiguousarray(Q.reshape(ns, op.dh.grid.n_cells, -1).transpose(1, 2, 0))
 
 
 def local_solve_failures(op):
