@@ -49,6 +49,7 @@ typedef struct tb_pattern tb_pattern;
 typedef struct tb_form tb_form;
 typedef struct tb_locator tb_locator;
 typedef struct tb_ecg tb_ecg;
+typedef struct tb_bidomain tb_bidomain;
 
 enum {
     TB_OK = 0,
@@ -195,6 +196,7 @@ const char *tb_version(void);
  * to refuse (first-order calls are unchanged).
  * Added under 10, purely additive: tb_viscoelastic_create, tb_host_maxwell_eval (LinearMaxwellMaterial); the entries listed with tb_viscoelastic_create accept
  * the new form kind, which did not exist before.
+ * Added under 10, purely additive: tb_bidomain_* (parabolic-elliptic bidomain block system: fused product, grounded block-Jacobi PCG).
  * A host binding compares tb_abi_revision() with the
  * TB_ABI_REVISION it was written against and refuses to run on a mismatch (julia/ThunderboltHIPBackend.jl does, in __init__) */
 #define TB_ABI_REVISION 10
@@ -906,6 +908,36 @@ int tb_mg_galerkin(tb_mg *mg, int fine_level);
 int tb_mg_destroy(tb_mg *mg);
 int tb_pcg_solve_mg(tb_pattern *pat, const double *d_Anz, const double *d_b, double *d_x, double rtol, double atol, int maxiter, tb_mg *mg, int *iters,
                     double *resnorm);
+
+/* ------------------------------------------------------------------ parabolic-elliptic bidomain block system (tb_bidomain.hip)
+ * ParabolicEllipticBidomainModel (src/modeling/electrophysiology.jl:305-326, declared "Not implemented yet" there).  Backward Euler on the transformed
+ * system, over the scalar first-order pattern `pat` that M, Kᵢ and Kₑ share (K as tb_assemble_matrix leaves a diffusion form: negative semidefinite):
+ *   [ M − Δt Kᵢ      −Δt Kᵢ        ] [φₘ⁺]   [ M φₘ + source_m ]
+ *   [ −Δt Kᵢ         −Δt (Kᵢ + Kₑ) ] [φₑ⁺] = [ source_e        ]
+ * Vectors of the block system are NODE-INTERLEAVED: 2n doubles, (φₘ,ⱼ, φₑ,ⱼ) at [2j, 2j + 1], 16-byte aligned (else TB_ERR_BAD_ARG).
+ *   tb_bidomain_create        the slice table of the pattern and every buffer the other entries use (they allocate nothing).  TB_ERR_UNSUPPORTED for a
+ *                             vector or second-order field.  The pattern must outlive the handle.
+ *   tb_bidomain_set_matrices  one pass over the three value arrays (device, nnz doubles each, of `pat` — a pattern other than the one given to
+ *                             tb_bidomain_create is refused): the per-non-zero triple (M − ΔtKᵢ, −ΔtKᵢ, −Δt(Kᵢ + Kₑ)), the column stream, and the inverse
+ *                             of every node's 2 × 2 diagonal block.  d_ground: one byte per node (device; copied); the φₑ row and column of a flagged
+ *                             node are eliminated, `ground_diag` > 0 on the diagonal (pass Δt·(tb_meandiag(Kᵢ) + tb_meandiag(Kₑ)), the mean diagonal of
+ *                             the φₑφₑ block, as Ferrite's apply_zero! would, or 1).  At least one node must be grounded for the matrix to be definite:
+ *                             its null vector is otherwise (0, 1).  dt must be finite and > 0 (TB_ERR_BAD_ARG).  Enqueues only.
+ *   tb_bidomain_apply         y = A x, all four blocks in one pass over the index stream.  No floating-point atomics: a row is summed by one lane in
+ *                             stored entry order, two calls give the same bits.  Enqueues only (fits inside tb_graph_begin / tb_graph_end).  x ≠ y.
+ *   tb_bidomain_solve         A x = b by conjugate gradients preconditioned with the inverse diagonal blocks, x the initial guess: the stopping rule
+ *                             ‖r‖₂ ≤ atol + rtol·‖r₀‖₂, tb_solver_last_tolerance (of `pat`), the looks (every iteration up to the 64th, every 4th from
+ *                             there) and the not-positive-definite report (TB_ERR_BAD_ARG) of tb_pcg_solve.  Reads scalars back: refused inside a capture.
+ *   tb_bidomain_pack          d_out = (d_m, d_e) interleaved; d_e = NULL: zeros; zero_ground != 0: the φₑ entry of a grounded node is 0 (a right-hand side)
+ *   tb_bidomain_unpack        the reverse; either output may be NULL */
+int tb_bidomain_create(tb_pattern *pat, tb_bidomain **out);
+int tb_bidomain_destroy(tb_bidomain *bd);
+int tb_bidomain_set_matrices(tb_bidomain *bd, tb_pattern *pat, const double *d_M, const double *d_Ki, const double *d_Ke, double dt, const uint8_t *d_ground,
+                             double ground_diag);
+int tb_bidomain_apply(tb_bidomain *bd, const double *d_x, double *d_y);
+int tb_bidomain_solve(tb_bidomain *bd, const double *d_b, double *d_x, double rtol, double atol, int maxiter, int *iters, double *resnorm);
+int tb_bidomain_pack(tb_bidomain *bd, const double *d_m, const double *d_e, int zero_ground, double *d_out);
+int tb_bidomain_unpack(tb_bidomain *bd, const double *d_in, double *d_m, double *d_e);
 
 /* ------------------------------------------------------------------ host-side generators (no GPU needed)
  * Ferrite-convention synthetic inputs for benchmarks and tests: generate_grid (src/mesh/generators.jl:942),

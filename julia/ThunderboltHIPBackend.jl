@@ -879,6 +879,39 @@ evaluate_leads!(out::HIPVector{Float64}, Z::HIPVector{Float64}, nleads::Integer,
 # κ∇φₘ_t[isnan.(κ∇φₘ_t)] .= 0.0; κ∇φₘ_t .*= α (ecg.jl:345-347, 612) in one pass
 scrub_scale!(x::HIPVector{Float64}, α::Real) = check(ccall((:tb_scrub_scale, libtbhip), Cint, (Ptr{Cvoid}, Int64, Cdouble, Ptr{Float64}), x.dev.handle, x.n, α, x.ptr))
 
+# ---------------------------------------------------------------- parabolic-elliptic bidomain block system (src/modeling/electrophysiology.jl:305-326)
+# The 2 × 2 block operator [M − ΔtKᵢ, −ΔtKᵢ; −ΔtKᵢ, −Δt(Kᵢ + Kₑ)] over the scalar pattern, φₑ grounded at flagged nodes.  Block vectors are
+# node-interleaved (2n values: φₘ,ⱼ, φₑ,ⱼ); pack! / unpack! move between them and the host's two vectors.
+mutable struct HIPBidomainSystem
+    handle::Ptr{Cvoid}
+    ddh::DeviceDofHandler   # keeps the pattern alive
+end
+function HIPBidomainSystem(ddh::DeviceDofHandler)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:tb_bidomain_create, libtbhip), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), ddh.pattern, h))
+    sys = HIPBidomainSystem(h[], ddh)
+    finalizer(s -> (ccall((:tb_bidomain_destroy, libtbhip), Cint, (Ptr{Cvoid},), s.handle); s.handle = C_NULL), sys)
+    return sys
+end
+# ground_flags: one byte per node; ground_diag: the diagonal of the eliminated φₑ rows (Δt·(meandiag(Kᵢ) + meandiag(Kₑ)) or 1)
+update_system_matrix!(sys::HIPBidomainSystem, M::HIPSparseMatrixCSR{Float64}, Kᵢ::HIPSparseMatrixCSR{Float64}, Kₑ::HIPSparseMatrixCSR{Float64}, Δt::Real,
+                      ground_flags::HIPVector{UInt8}, ground_diag::Real) =
+    check(ccall((:tb_bidomain_set_matrices, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{UInt8}, Cdouble),
+        sys.handle, M.ddh.pattern, M.nzval.ptr, Kᵢ.nzval.ptr, Kₑ.nzval.ptr, Δt, ground_flags.ptr, ground_diag))
+bidomain_mul!(y::HIPVector{Float64}, sys::HIPBidomainSystem, x::HIPVector{Float64}) =
+    check(ccall((:tb_bidomain_apply, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), sys.handle, x.ptr, y.ptr))
+function bidomain_solve!(x::HIPVector{Float64}, sys::HIPBidomainSystem, b::HIPVector{Float64}; rtol::Real = 1e-5, atol::Real = 1e-6, maxiter::Integer = 1000)
+    iters, res = Ref{Cint}(0), Ref{Cdouble}(0.0)
+    check(ccall((:tb_bidomain_solve, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Cint, Ref{Cint}, Ref{Cdouble}),
+        sys.handle, b.ptr, x.ptr, rtol, atol, maxiter, iters, res))
+    return Int(iters[]), res[]
+end
+pack!(out::HIPVector{Float64}, sys::HIPBidomainSystem, φₘ::HIPVector{Float64}, φₑ::Union{HIPVector{Float64}, Nothing}; zero_ground::Bool = false) =
+    check(ccall((:tb_bidomain_pack, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}), sys.handle, φₘ.ptr,
+        φₑ === nothing ? Ptr{Float64}(C_NULL) : φₑ.ptr, zero_ground ? 1 : 0, out.ptr))
+unpack!(φₘ::HIPVector{Float64}, φₑ::HIPVector{Float64}, sys::HIPBidomainSystem, x::HIPVector{Float64}) =
+    check(ccall((:tb_bidomain_unpack, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), sys.handle, x.ptr, φₘ.ptr, φₑ.ptr))
+
 # ---------------------------------------------------------------- Newmark-β elastodynamics (src/solver/time/newmark.jl)
 # The mass operator of the displacement field is an ordinary HIPBilinearOperator: tb_assemble_matrix accepts BilinearMassIntegrator on ncomp = 3.
 # ũ = uₙ + Δt vₙ + (½−β)Δt² aₙ, ṽ = vₙ + (1−γ)Δt aₙ (newmark.jl:580-581)

@@ -31,3 +31,5 @@ from . import multidomain  # noqa: F401
 from .multidomain import (insert_interfaces, InterfaceRecords, interface_dofs, extract_subgrid, NoStimulationProtocol, MonodomainModel,  # noqa: F401
                           InterfaceDiffusionModel, ReactionDiffusionSplit, InterfaceDiffusionForm, PointwiseMultiODEFunction, MultiSolverCache,
                           MultiDomainFunction, plan_ep, semidiscretize_ep, MultiDomainHeatStage, MultiDomainLieTrotterGodunov, heat_dofrange_of, QUAD_FACETS)
+from . import bidomain  # noqa: F401
+from .bidomain import ParabolicEllipticBidomainModel, BidomainBackwardEulerStage, BidomainSystem  # noqa: F401

@@ -226,6 +226,13 @@ SIGNATURES = {
     "tb_mg_galerkin": (C.c_int, [vp, C.c_int]),
     "tb_mg_destroy": (C.c_int, [vp]),
     "tb_pcg_solve_mg": (C.c_int, [vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "tb_bidomain_create": (C.c_int, [vp, C.POINTER(vp)]),
+    "tb_bidomain_destroy": (C.c_int, [vp]),
+    "tb_bidomain_set_matrices": (C.c_int, [vp, vp, vp, vp, vp, C.c_double, vp, C.c_double]),
+    "tb_bidomain_apply": (C.c_int, [vp, vp, vp]),
+    "tb_bidomain_solve": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "tb_bidomain_pack": (C.c_int, [vp, vp, vp, C.c_int, vp]),
+    "tb_bidomain_unpack": (C.c_int, [vp, vp, vp, vp]),
     "tb_host_generate_grid_hex": (C.c_int, [C.c_int, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_i32p]),
     "tb_host_generate_grid_tet": (C.c_int, [C.c_int, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_i32p]),
     "tb_host_generate_grid_quad": (C.c_int, [C.c_int, C.c_int, c_dp, c_dp, c_dp, c_i32p]),

@@ -6,6 +6,7 @@
 #include <ctime>
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -470,6 +471,14 @@ int launch_cg1_update(tb_device *dev, int64_t n, const double *wt, const double 
                       double *u, double *d_S);
 int launch_cg1_fold(tb_device *dev, double *d_S);
 int launch_cg1_iteration(tb_pattern *pat, const double *A, const double *dinv, double *x, double *r, double *u, double *p, double *s, double *w, double *d_S);
+
+// Stopping tolerance atol + rtol·‖r₀‖ of every Krylov solver (tb_krylov.hip, tb_bidomain.hip; tb_solver_last_tolerance).  A non-finite ‖r₀‖ — a NaN or ±∞ in A, b or x₀ — gives NaN, which
+// no residual compares ≤ to: with atol + rtol·∞ = ∞ a solve on such data would return ‖r‖ = ∞ ≤ ∞ at once, "converged".  The loops below are
+// `while (rnorm > tol …)`, so they are not entered either: the call returns TB_OK with zero iterations and the residual norm it found.
+inline double stopping_tolerance(double atol, double rtol, double rnorm0)
+{
+    return std::isfinite(rnorm0) ? atol + rtol * rnorm0 : __builtin_nan("");
+}
 
 // ---- status block and host readback (tb_api.cpp) ----
 int read_status_public(tb_device *dev); // status block → host, synchronises the stream (what check_status does when the status is not deferred)

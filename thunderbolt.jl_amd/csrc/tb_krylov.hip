@@ -30,13 +30,7 @@ double *krylov_ws(tb_pattern *pat, size_t doubles)
     return pat->d_krylov_ws;
 }
 
-// Stopping tolerance atol + rtol·‖r₀‖ of every solver here (tb_solver_last_tolerance).  A non-finite ‖r₀‖ — a NaN or ±∞ in A, b or x₀ — gives NaN, which
-// no residual compares ≤ to: with atol + rtol·∞ = ∞ a solve on such data would return ‖r‖ = ∞ ≤ ∞ at once, "converged".  The loops below are
-// `while (rnorm > tol …)`, so they are not entered either: the call returns TB_OK with zero iterations and the residual norm it found.
-static inline double stopping_tolerance(double atol, double rtol, double rnorm0)
-{
-    return std::isfinite(rnorm0) ? atol + rtol * rnorm0 : __builtin_nan("");
-}
+// (stopping_tolerance, the stopping rule of every solver here and of tb_bidomain.hip, is in tb_internal.h)
 
 } // namespace tb
 
