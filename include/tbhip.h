@@ -50,6 +50,7 @@ typedef struct tb_form tb_form;
 typedef struct tb_locator tb_locator;
 typedef struct tb_ecg tb_ecg;
 typedef struct tb_bidomain tb_bidomain;
+typedef struct tb_bidomain_mg tb_bidomain_mg;
 
 enum {
     TB_OK = 0,
@@ -197,6 +198,7 @@ const char *tb_version(void);
  * Added under 10, purely additive: tb_viscoelastic_create, tb_host_maxwell_eval (LinearMaxwellMaterial); the entries listed with tb_viscoelastic_create accept
  * the new form kind, which did not exist before.
  * Added under 10, purely additive: tb_bidomain_* (parabolic-elliptic bidomain block system: fused product, grounded block-Jacobi PCG).
+ * Added under 10, purely additive: tb_bidomain_mg_* (geometric multigrid preconditioner of the bidomain block system: block V-cycle, preconditioned CG).
  * A host binding compares tb_abi_revision() with the
  * TB_ABI_REVISION it was written against and refuses to run on a mismatch (julia/ThunderboltHIPBackend.jl does, in __init__) */
 #define TB_ABI_REVISION 10
@@ -938,6 +940,52 @@ int tb_bidomain_apply(tb_bidomain *bd, const double *d_x, double *d_y);
 int tb_bidomain_solve(tb_bidomain *bd, const double *d_b, double *d_x, double rtol, double atol, int maxiter, int *iters, double *resnorm);
 int tb_bidomain_pack(tb_bidomain *bd, const double *d_m, const double *d_e, int zero_ground, double *d_out);
 int tb_bidomain_unpack(tb_bidomain *bd, const double *d_in, double *d_m, double *d_e);
+
+/* ------------------------------------------------------------------ multigrid preconditioner of the bidomain block system (tb_bidomain_mg.hip)
+ * One V(degree, degree) cycle on the node pairs (φₘ, φₑ) of a tb_bidomain over the nested hexahedral grids of a tb_mg, and the conjugate gradients it
+ * preconditions.  Levels 0 … L−1 are the tb_mg's; a coarse node is grounded iff the fine node it coincides with is (the rule of tb_mg_set_prescribed).
+ * Block transfer 𝒫 = diag(P, G_f P G_c): P the scalar nodal transfer of tb_mg_set_transfer, G the 0/1 diagonal of a level's free nodes — φₘ interpolates
+ * everywhere, φₑ neither into a grounded fine node nor from a grounded coarse node.  Coarse operators 𝒜_c = 𝒫ᵀ𝒜_f𝒫, the eliminated φₑφₑ diagonal entries set
+ * to the mean |diagonal| of the level's free φₑφₑ entries.  A ground vertex need not be a coarse vertex.  The coarse φₘφₑ block is then not symmetric, so
+ * coarse levels store four planes (a₁₁, a₁₂, a₂₁, a₂₂) per non-zero with the elimination baked in; the fine level stays the block system's own storage.
+ * Smoother: Chebyshev on B⁻¹𝒜 over [λmax/interval_ratio, λmax], B the 2 × 2 node diagonal blocks, one pass over the matrix per step; λmax per level: the
+ * largest Ritz value of 24 Lanczos steps in the B inner product, inflated by 5 %.  Coarsest level: dense inverse, at most 512 nodes.  z_e = 0 at grounded
+ * nodes.  No floating-point atomics in the set-up or in the cycle, and one recorded order for every sum of either (the Galerkin products, the fill, the
+ * three scalars of a Lanczos step: per-workgroup partials folded in a fixed order), at every size: two set-ups give the same level planes and the same λmax,
+ * two applications the same bits.  The SOLVE keeps its scalars in the slot groups of tb_bidomain_solve, pᵀ𝒜p fused into the product: its sums have one order
+ * while a launch has at most 64 workgroups (about 16 000 nodes), beyond that two solves may differ in the last bits, as two tb_bidomain_solve calls may.
+ *   tb_bidomain_mg_create     from a block system and a tb_mg whose levels (tb_mg_set_level) and h-transfers (tb_mg_set_transfer) are set, the finest level
+ *                             the block system's pattern, no prescribed dofs (tb_mg_set_prescribed) — the ground comes from tb_bidomain_set_matrices.  The
+ *                             caller need not call tb_mg_setup: the symbolic phase of the tb_mg (transfers, unflagged per-dof Galerkin term lists) runs
+ *                             here if it has not yet, and is reused, not rebuilt.  Allocates everything the other entries use.  TB_ERR_BAD_ARG when the
+ *                             hierarchy's finest pattern is not the block system's; TB_ERR_UNSUPPORTED for a coarsest level of more than 512 nodes ("add
+ *                             a level") and for levels that are not scalar first-order fields on hexahedra.  bd and mg must outlive the handle, and the
+ *                             tb_mg must not be given new levels, transfers or flags afterwards.
+ *   tb_bidomain_mg_setup      the numeric phase, after tb_bidomain_set_matrices (refused before it): reads what that call stored — the value arrays need
+ *                             not be passed again.  Galerkin chain (the masked planes of a level through the scalar plan, once per plane), block inverses,
+ *                             λmax per level, coarsest inverse.  Reads scalars back: refused inside a capture.  A later tb_bidomain_set_matrices
+ *                             invalidates it: apply, solve and the read-outs refuse until the next set-up.
+ *   tb_bidomain_mg_apply      z = ℳ⁻¹ r, one cycle from z = 0.  Enqueues only (fits inside tb_graph_begin / tb_graph_end).  r ≠ z, both node-interleaved
+ *                             and 16-byte aligned.
+ *   tb_bidomain_mg_solve      𝒜 x = b by conjugate gradients with z = ℳ⁻¹ r, x the initial guess: the stopping rule, tb_solver_last_tolerance (of the
+ *                             block system's pattern), the looks (every iteration up to the 64th, every 4th from there), the not-positive-definite report
+ *                             (TB_ERR_BAD_ARG) and the non-finite behaviour of tb_bidomain_solve and tb_pcg_solve_mg; pᵀ𝒜p stays fused into the product.
+ *                             Refused inside a capture.  b ≠ x.
+ *   tb_bidomain_mg_n_levels / _level_planes / _level_lambda_max   what the cycle is made of, for tests: the four planes of a level as one device array of
+ *                             4 · nnz doubles (a₁₁ | a₁₂ | a₂₁ | a₂₂, each in the CSR order of that level's scalar pattern; valid until the next set-up),
+ *                             λmax of a level ≥ 1
+ *   tb_bidomain_mg_cycle_below   MEASUREMENT HOOK, not part of any solve: the cycle from `level` (below the finest) down, on that level's own residual and
+ *                             correction buffers, whatever the latest application left in them — its result means nothing, its duration is the coarse
+ *                             tail of a cycle (scripts/bench_bidomain_mg.py).  Enqueues only. */
+int tb_bidomain_mg_create(tb_bidomain *bd, tb_mg *mg, tb_bidomain_mg **out);
+int tb_bidomain_mg_destroy(tb_bidomain_mg *h);
+int tb_bidomain_mg_setup(tb_bidomain_mg *h, int degree, double interval_ratio);
+int tb_bidomain_mg_apply(tb_bidomain_mg *h, const double *d_r, double *d_z);
+int tb_bidomain_mg_solve(tb_bidomain_mg *h, const double *d_b, double *d_x, double rtol, double atol, int maxiter, int *iters, double *resnorm);
+int tb_bidomain_mg_n_levels(tb_bidomain_mg *h, int *n_levels);
+int tb_bidomain_mg_level_planes(tb_bidomain_mg *h, int level, const double **d_planes, int64_t *nnz);
+int tb_bidomain_mg_level_lambda_max(tb_bidomain_mg *h, int level, double *lmax);
+int tb_bidomain_mg_cycle_below(tb_bidomain_mg *h, int level);
 
 /* ------------------------------------------------------------------ host-side generators (no GPU needed)
  * Ferrite-convention synthetic inputs for benchmarks and tests: generate_grid (src/mesh/generators.jl:942),

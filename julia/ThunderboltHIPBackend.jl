@@ -912,6 +912,50 @@ pack!(out::HIPVector{Float64}, sys::HIPBidomainSystem, φₘ::HIPVector{Float64}
 unpack!(φₘ::HIPVector{Float64}, φₑ::HIPVector{Float64}, sys::HIPBidomainSystem, x::HIPVector{Float64}) =
     check(ccall((:tb_bidomain_unpack, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), sys.handle, x.ptr, φₘ.ptr, φₑ.ptr))
 
+# Geometric multigrid preconditioner of the block system (tb_bidomain_mg_*): one V(degree, degree) cycle on the node pairs over the levels of a
+# HIPGMGPrecon built WITHOUT prescribed dofs (the ground comes from update_system_matrix!) whose finest pattern is the system's; setup! follows every
+# update_system_matrix!, and need not be preceded by setup!(::HIPGMGPrecon, A).
+mutable struct HIPBidomainMultigrid
+    handle::Ptr{Cvoid}
+    sys::HIPBidomainSystem   # both outlive the handle
+    mg::HIPGMGPrecon
+end
+function HIPBidomainMultigrid(sys::HIPBidomainSystem, mg::HIPGMGPrecon)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:tb_bidomain_mg_create, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), sys.handle, mg.handle, h))
+    bmg = HIPBidomainMultigrid(h[], sys, mg)
+    finalizer(m -> (ccall((:tb_bidomain_mg_destroy, libtbhip), Cint, (Ptr{Cvoid},), m.handle); m.handle = C_NULL), bmg)
+    return bmg
+end
+setup!(bmg::HIPBidomainMultigrid) =
+    check(ccall((:tb_bidomain_mg_setup, libtbhip), Cint, (Ptr{Cvoid}, Cint, Cdouble), bmg.handle, bmg.mg.degree, bmg.mg.interval_ratio))
+mg_apply!(z::HIPVector{Float64}, bmg::HIPBidomainMultigrid, r::HIPVector{Float64}) =
+    check(ccall((:tb_bidomain_mg_apply, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), bmg.handle, r.ptr, z.ptr))
+function bidomain_solve!(x::HIPVector{Float64}, bmg::HIPBidomainMultigrid, b::HIPVector{Float64}; rtol::Real = 1e-5, atol::Real = 1e-6, maxiter::Integer = 1000)
+    iters, res = Ref{Cint}(0), Ref{Cdouble}(0.0)
+    check(ccall((:tb_bidomain_mg_solve, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Cint, Ref{Cint}, Ref{Cdouble}),
+        bmg.handle, b.ptr, x.ptr, rtol, atol, maxiter, iters, res))
+    return Int(iters[]), res[]
+end
+function n_levels(bmg::HIPBidomainMultigrid)
+    n = Ref{Cint}(0)
+    check(ccall((:tb_bidomain_mg_n_levels, libtbhip), Cint, (Ptr{Cvoid}, Ref{Cint}), bmg.handle, n))
+    return Int(n[])
+end
+# the four planes (a₁₁ | a₁₂ | a₂₁ | a₂₂) of a level, each in the CSR order of that level's scalar pattern: (device pointer, nnz)
+function mg_level_planes(bmg::HIPBidomainMultigrid, level::Integer)
+    p, nnz = Ref{Ptr{Float64}}(C_NULL), Ref{Int64}(0)
+    check(ccall((:tb_bidomain_mg_level_planes, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ref{Ptr{Float64}}, Ref{Int64}), bmg.handle, level, p, nnz))
+    return p[], nnz[]
+end
+function mg_level_lambda_max(bmg::HIPBidomainMultigrid, level::Integer)
+    λ = Ref{Cdouble}(0.0)
+    check(ccall((:tb_bidomain_mg_level_lambda_max, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ref{Cdouble}), bmg.handle, level, λ))
+    return λ[]
+end
+# measurement hook: the coarse tail of a cycle on whatever the level's buffers hold; only its duration means something
+mg_cycle_below!(bmg::HIPBidomainMultigrid, level::Integer) = check(ccall((:tb_bidomain_mg_cycle_below, libtbhip), Cint, (Ptr{Cvoid}, Cint), bmg.handle, level))
+
 # ---------------------------------------------------------------- Newmark-β elastodynamics (src/solver/time/newmark.jl)
 # The mass operator of the displacement field is an ordinary HIPBilinearOperator: tb_assemble_matrix accepts BilinearMassIntegrator on ncomp = 3.
 # ũ = uₙ + Δt vₙ + (½−β)Δt² aₙ, ṽ = vₙ + (1−γ)Δt aₙ (newmark.jl:580-581)

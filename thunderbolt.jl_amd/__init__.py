@@ -32,4 +32,4 @@ from .multidomain import (insert_interfaces, InterfaceRecords, interface_dofs, e
                           InterfaceDiffusionModel, ReactionDiffusionSplit, InterfaceDiffusionForm, PointwiseMultiODEFunction, MultiSolverCache,
                           MultiDomainFunction, plan_ep, semidiscretize_ep, MultiDomainHeatStage, MultiDomainLieTrotterGodunov, heat_dofrange_of, QUAD_FACETS)
 from . import bidomain  # noqa: F401
-from .bidomain import ParabolicEllipticBidomainModel, BidomainBackwardEulerStage, BidomainSystem  # noqa: F401
+from .bidomain import ParabolicEllipticBidomainModel, BidomainBackwardEulerStage, BidomainSystem, BidomainMultigrid  # noqa: F401

@@ -233,6 +233,15 @@ SIGNATURES = {
     "tb_bidomain_solve": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "tb_bidomain_pack": (C.c_int, [vp, vp, vp, C.c_int, vp]),
     "tb_bidomain_unpack": (C.c_int, [vp, vp, vp, vp]),
+    "tb_bidomain_mg_create": (C.c_int, [vp, vp, C.POINTER(vp)]),
+    "tb_bidomain_mg_destroy": (C.c_int, [vp]),
+    "tb_bidomain_mg_setup": (C.c_int, [vp, C.c_int, C.c_double]),
+    "tb_bidomain_mg_apply": (C.c_int, [vp, vp, vp]),
+    "tb_bidomain_mg_solve": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "tb_bidomain_mg_n_levels": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "tb_bidomain_mg_level_planes": (C.c_int, [vp, C.c_int, C.POINTER(vp), c_i64p]),
+    "tb_bidomain_mg_level_lambda_max": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double)]),
+    "tb_bidomain_mg_cycle_below": (C.c_int, [vp, C.c_int]),
     "tb_host_generate_grid_hex": (C.c_int, [C.c_int, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_i32p]),
     "tb_host_generate_grid_tet": (C.c_int, [C.c_int, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_i32p]),
     "tb_host_generate_grid_quad": (C.c_int, [C.c_int, C.c_int, c_dp, c_dp, c_dp, c_i32p]),

@@ -11,16 +11,19 @@ matrix is symmetric positive semidefinite with null vector (0, 1); φₑ is fixe
 those dofs are eliminated, the mean diagonal of the φₑφₑ block goes on the eliminated rows, the right-hand side is zeroed there.
 
 The coupled solve runs in csrc/tb_bidomain.hip (tb_bidomain_*): one fused product for all four blocks over a node-interleaved unknown, and conjugate
-gradients preconditioned with the inverse 2 × 2 diagonal blocks.  BidomainBackwardEulerStage has the interface of BackwardEulerStage, so it goes into
-LieTrotterGodunov and ReactionTangentController unchanged."""
+gradients preconditioned with the inverse 2 × 2 diagonal blocks — or, with `precond=GMGPrecon(gh)`, with one geometric multigrid V-cycle on the node
+pairs (csrc/tb_bidomain_mg.hip, tb_bidomain_mg_*: BidomainMultigrid), whose iteration count does not grow with the mesh.  BidomainBackwardEulerStage has
+the interface of BackwardEulerStage, so it goes into LieTrotterGodunov and ReactionTangentController unchanged."""
 import ctypes as C
 
 import numpy as np
 
+from . import _lib as L
 from ._lib import check, lib
-from .api import (BilinearDiffusionIntegrator, BilinearMassIntegrator, ConductivityToDiffusivityCoefficient, ConstantCoefficient, DeviceVector,
-                  LinearIntegrator, _ptr, allocate_matrix, needs_update, setup_operator, solve_converged, update_operator)
+from .api import (BilinearDiffusionIntegrator, BilinearMassIntegrator, ConductivityToDiffusivityCoefficient, ConstantCoefficient, DeviceVector, DofHandler,
+                  LagrangeCollection, LinearIntegrator, _ptr, allocate_matrix, needs_update, setup_operator, solve_converged, update_operator)
 from .ecg import _vertex_ids, vertex_dofs
+from .multigrid import ChainedMGPrecon, GMGPrecon, PMGPrecon, check_supported
 from .solid import meandiag
 
 
@@ -64,9 +67,18 @@ class BidomainSystem:
     def apply(self, x, y):
         check(lib().tb_bidomain_apply(self.h, _ptr(x), _ptr(y)))
 
-    def solve(self, b, x, rtol=1e-5, atol=1e-6, maxiter=1000):
+    def solve(self, b, x, rtol=1e-5, atol=1e-6, maxiter=1000, precond=None):
+        """(iterations, residual norm).  precond None: block-Jacobi PCG (tb_bidomain_solve); a BidomainMultigrid of this system, set up for the current
+        matrices: CG preconditioned by one V-cycle (tb_bidomain_mg_solve)"""
         it, res = C.c_int(), C.c_double()
-        check(lib().tb_bidomain_solve(self.h, _ptr(b), _ptr(x), float(rtol), float(atol), int(maxiter), C.byref(it), C.byref(res)))
+        if precond is None:
+            check(lib().tb_bidomain_solve(self.h, _ptr(b), _ptr(x), float(rtol), float(atol), int(maxiter), C.byref(it), C.byref(res)))
+        elif isinstance(precond, BidomainMultigrid):
+            if precond.system is not self:
+                raise ValueError("BidomainSystem.solve: the multigrid hierarchy was materialised for another block system")
+            check(lib().tb_bidomain_mg_solve(precond.h, _ptr(b), _ptr(x), float(rtol), float(atol), int(maxiter), C.byref(it), C.byref(res)))
+        else:
+            raise TypeError("BidomainSystem.solve: precond is None (block-Jacobi) or a BidomainMultigrid")
         return it.value, res.value
 
     def pack(self, m, e, out, zero_ground=False):
@@ -84,16 +96,97 @@ class BidomainSystem:
             pass
 
 
+class BidomainMultigrid:
+    """BidomainMultigrid(system, gh, degree=2, interval_ratio=4.0): the materialised multigrid hierarchy of one BidomainSystem (tb_bidomain_mg_*),
+    modelled on MultigridHierarchy — per-level scalar first-order DofHandlers and patterns on the grids of `gh` (finest: the system's own), the tb_mg
+    that holds the transfers and the Galerkin term lists (owned here; its numeric phase is never run), and the block hierarchy on top.  `setup()`
+    follows every `system.set_matrices`; `apply(r, z)` is one V(degree, degree) cycle on node-interleaved vectors."""
+
+    def __init__(self, system, gh, degree=2, interval_ratio=4.0):
+        if not isinstance(system, BidomainSystem):
+            raise TypeError("BidomainMultigrid: pass the BidomainSystem the hierarchy preconditions")
+        pattern = system.pattern
+        dh, device = pattern.dmesh.dh, pattern.dmesh.device
+        check_supported(gh, dh)
+        self.system, self.gh, self.device, self.degree, self.interval_ratio = system, gh, device, int(degree), float(interval_ratio)
+        grids = list(gh.grids)
+        self.dhs = [DofHandler(g, LagrangeCollection(1, 1)) for g in grids[:-1]] + [dh]
+        self.sps = [allocate_matrix(d) for d in self.dhs[:-1]] + [pattern.sp]
+        self.patterns = [d.device_mesh(device).pattern(sp) for d, sp in zip(self.dhs[:-1], self.sps[:-1])] + [pattern]
+        self.mg, self.h = C.c_void_p(), C.c_void_p()
+        check(lib().tb_mg_create(device.h, len(grids), C.byref(self.mg)))
+        for l, p in enumerate(self.patterns):
+            check(lib().tb_mg_set_level(self.mg, l, p.h))
+        for l in range(1, len(grids)):
+            pptr, pidx = gh.parents[l - 1]
+            pptr, pidx = np.ascontiguousarray(pptr, dtype=np.int64), np.ascontiguousarray(pidx, dtype=np.int32)
+            check(lib().tb_mg_set_transfer(self.mg, l, grids[l].n_nodes, pptr.ctypes.data_as(L.c_i64p), pidx.ctypes.data_as(L.c_i32p)))
+        check(lib().tb_bidomain_mg_create(system.h, self.mg, C.byref(self.h)))
+
+    @property
+    def n_levels(self):
+        return len(self.patterns)
+
+    def setup(self):
+        """the numeric phase for the matrices of the latest system.set_matrices: Galerkin chain, block inverses, λmax per level, coarsest inverse"""
+        check(lib().tb_bidomain_mg_setup(self.h, self.degree, self.interval_ratio))
+        return self
+
+    def apply(self, r, z):
+        check(lib().tb_bidomain_mg_apply(self.h, _ptr(r), _ptr(z)))
+        return z
+
+    def level_blocks(self, level):
+        """(a₁₁, a₁₂, a₂₁, a₂₂) of the level's operator: CSR values on self.sps[level], host arrays"""
+        p, nnz = C.c_void_p(), C.c_int64()
+        check(lib().tb_bidomain_mg_level_planes(self.h, level, C.byref(p), C.byref(nnz)))
+        out = np.empty((4, nnz.value))
+        check(lib().tb_memcpy_d2h(self.device.h, out.ctypes.data_as(C.c_void_p), p, out.nbytes))
+        return tuple(out)
+
+    def lambda_max(self, level):
+        out = C.c_double()
+        check(lib().tb_bidomain_mg_level_lambda_max(self.h, level, C.byref(out)))
+        return out.value
+
+    def cycle_below(self, level):
+        """measurement hook: the cycle from `level` (below the finest) down on that level's own buffers, whatever they hold (enqueues only) — its
+        duration is the coarse tail of a cycle, its result means nothing"""
+        check(lib().tb_bidomain_mg_cycle_below(self.h, level))
+
+    def close(self):
+        if self.h:
+            lib().tb_bidomain_mg_destroy(self.h)
+            self.h = None
+        if self.mg:
+            lib().tb_mg_destroy(self.mg)
+            self.mg = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class BidomainBackwardEulerStage:
     """BackwardEulerStage for the bidomain block system: perform_step(φₘ, t, Δt) advances φₘ in place and the stage's own `phi_e` (n values, zero at
     the start, the initial guess of the next step).  `ground`: vertex ids (or positions), mandatory.  `source`: the transmembrane stimulus, a
     LinearIntegrator scaled as BackwardEulerStage scales its source.  `source_e`: the extracellular current Iₛₜᵢₘ,ₑ − Iₛₜᵢₘ,ᵢ, a LinearIntegrator or
     nodal currents by dof (array of n values); it has to sum to zero (checked whenever it is (re)assembled).  The combined operator is rebuilt only
-    when Δt changes (`generation` counts the rebuilds).  `solver.mirror` has no meaning here."""
+    when Δt changes (`generation` counts the rebuilds).  `solver.mirror` has no meaning here.  `precond` (keyword only): None — block-Jacobi PCG — or
+    GMGPrecon(gh) with gh's finest grid the stage's: the hierarchy is materialised here (`multigrid`, a BidomainMultigrid) and set up again with every
+    rebuild of the operator."""
 
-    def __init__(self, solver, strategy, dh, diffusion_i, diffusion_e, ground, source=None, source_e=None, pattern=None, t0=0.0):
+    def __init__(self, solver, strategy, dh, diffusion_i, diffusion_e, ground, source=None, source_e=None, pattern=None, t0=0.0, *, precond=None):
         if dh.ip.order != 1 or dh.ip.ncomp != 1:
             raise NotImplementedError("BidomainBackwardEulerStage: first-order scalar fields only (order %d, %d component(s))" % (dh.ip.order, dh.ip.ncomp))
+        if precond is not None:
+            if isinstance(precond, (PMGPrecon, ChainedMGPrecon)):
+                raise NotImplementedError("BidomainBackwardEulerStage: %s is out of scope - the block system is first order, pass GMGPrecon(gh)" % type(precond).__name__)
+            if not isinstance(precond, GMGPrecon):
+                raise NotImplementedError("BidomainBackwardEulerStage: precond is None (block-Jacobi) or GMGPrecon(gh); %r is out of scope" % (precond,))
+            precond.check(dh)
         if ground is None or len(ground) == 0:
             raise ValueError("BidomainBackwardEulerStage: `ground` is empty - without a grounded vertex φₑ is determined up to a constant only and the "
                              "block matrix is singular")
@@ -123,6 +216,7 @@ class BidomainBackwardEulerStage:
         else:
             self.source_e_b = None
         self.system = BidomainSystem(self.M.pattern)
+        self.multigrid = None if precond is None else BidomainMultigrid(self.system, precond.gh, precond.degree, precond.interval_ratio)
         # the mean diagonal of Kᵢ + Kₑ does not depend on Δt: read once (tb_meandiag is Ferrite's: the mean of |dᵢᵢ|, and K's diagonal is negative)
         self._kdiag = meandiag(self.Ki.pattern, self.Ki.A) + meandiag(self.Ke.pattern, self.Ke.A)
         self.phi_e = self.device.zeros(n)
@@ -140,6 +234,8 @@ class BidomainBackwardEulerStage:
         """One backward-Euler step of the block system: True on success."""
         if self.dt_last is None or abs(dt - self.dt_last) > 1e-14 * abs(dt):
             self.system.set_matrices(self.M.A, self.Ki.A, self.Ke.A, dt, self.ground_flags, self.ground_diag(dt))
+            if self.multigrid is not None:
+                self.multigrid.setup()
             self.dt_last = dt
             self.generation += 1
         check(lib().tb_spmv_csr(self.M.pattern.h, self.M.A.ptr, _ptr(phi), 1.0, 0.0, self.b.ptr))          # M φₘ
@@ -152,7 +248,7 @@ class BidomainBackwardEulerStage:
             check_balanced(self.source_e_b.to_host())
         self.system.pack(self.b, self.source_e_b, self.rhs, zero_ground=True)
         self.system.pack(phi, self.phi_e, self.x)
-        its, res = self.system.solve(self.rhs, self.x, self.solver.rtol, self.solver.atol, self.solver.maxiter)
+        its, res = self.system.solve(self.rhs, self.x, self.solver.rtol, self.solver.atol, self.solver.maxiter, precond=self.multigrid)
         self.system.unpack(self.x, phi, self.phi_e)
         self.last_iters, self.last_resnorm = its, res
         return solve_converged(self.M.pattern, res)

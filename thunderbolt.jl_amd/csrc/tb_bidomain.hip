@@ -17,25 +17,11 @@
 
 #include <cmath>
 
+#include "tb_bidomain_internal.hpp"
 #include "tb_internal.h"
 #include "tb_reduce.hpp"
 
-struct tb_bidomain {
-    tb_pattern *pat = nullptr;
-    int64_t n = 0, n_slices = 0, entries = 0; // rows, slices of 64 rows, value slots per plane (Σ 64 · width)
-    int64_t *d_base = nullptr;                // n_slices + 1: first slot of every slice (multiples of 64)
-    uint32_t *d_col = nullptr;                // entries: column | grounded << 31
-    double *d_val = nullptr;                  // 3 · entries: planes a₁₁, a₁₂ (= a₂₁ off the ground), a₂₂
-    double *d_binv = nullptr;                 // 3 n: inverse of every node's diagonal block (b₁₁, b₁₂, b₂₂)
-    uint8_t *d_ground = nullptr;              // n: the flags of the latest tb_bidomain_set_matrices
-    double *d_ws = nullptr;                   // r, p, Ap (2n each) and 8 scalars of the solve
-    double ground_diag = 1.0;
-    bool have_matrices = false;
-};
-
 namespace tb {
-
-constexpr uint32_t BD_GROUNDED = 0x80000000u;
 
 // The triple of one non-zero, every operation rounded on its own (no contraction into fused multiply-adds): the −Δt kᵢ inside a₁₁ is then the very
 // a₁₂, as the null vector (0, 1) of the ungrounded matrix wants it, and the stored operator is bit for bit the matrix a host forms from the same arrays
@@ -85,56 +71,6 @@ k_bd_fill(int64_t n, int64_t n_slices, const int64_t *__restrict__ base, int64_t
     binv[3 * row] = ok ? d22 / det : 1.0; binv[3 * row + 1] = ok ? -d12 / det : 0.0; binv[3 * row + 2] = ok ? d11 / det : 1.0;
 }
 
-// y = A x, one slice per wave, one row per lane, the entries of a row in their stored order.  DOT: the partials of xᵀy go to the slot group xy.
-template <bool DOT>
-__global__ void __launch_bounds__(256)
-k_bd_apply(int64_t n, int64_t n_slices, const int64_t *__restrict__ base, int64_t entries, const uint32_t *__restrict__ col, const double *__restrict__ val,
-           const uint8_t *__restrict__ ground, double gdiag, const double2 *__restrict__ x, double2 *__restrict__ y, double *__restrict__ xy)
-{
-    constexpr int U = 9; // entries in flight per lane: 4 · U loads, then U gathers (first-order rows: 9, 15, 27 entries)
-    const int lane = threadIdx.x & 63;
-    const int64_t wave0 = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
-    double acc = 0.0;
-    for (int64_t slice = wave0; slice < n_slices; slice += nwaves) {
-        const int64_t b0 = base[slice]; // wave-uniform: scalar loads
-        const int W = (int)((base[slice + 1] - b0) >> 6);
-        const int64_t row = slice * 64 + lane;
-        const bool ok = row < n;
-        const uint32_t *cs = col + b0 + lane;
-        const double *v11 = val + b0 + lane, *v12 = v11 + entries, *v22 = v12 + entries;
-        double ym = 0.0, ye = 0.0;
-        for (int k0 = 0; k0 < W; k0 += U) {
-            uint32_t c[U];
-            double a11[U], a12[U], a22[U];
-#pragma unroll
-            for (int j = 0; j < U; ++j) {
-                const bool on = k0 + j < W; // wave-uniform
-                const int64_t o = 64 * (int64_t)(on ? k0 + j : k0);
-                c[j] = cs[o];
-                a11[j] = on ? __builtin_nontemporal_load(v11 + o) : 0.0;
-                a12[j] = on ? __builtin_nontemporal_load(v12 + o) : 0.0;
-                a22[j] = on ? __builtin_nontemporal_load(v22 + o) : 0.0;
-            }
-            double2 xv[U];
-#pragma unroll
-            for (int j = 0; j < U; ++j) xv[j] = x[c[j] & ~BD_GROUNDED];
-#pragma unroll
-            for (int j = 0; j < U; ++j) {
-                const double xm = xv[j].x, xe = (c[j] & BD_GROUNDED) ? 0.0 : xv[j].y;
-                ym += a11[j] * xm; ym += a12[j] * xe;
-                ye += a12[j] * xm; ye += a22[j] * xe;
-            }
-        }
-        if (ok) {
-            const double2 xr = x[row];
-            if (ground[row]) ye = gdiag * xr.y; // an eliminated φₑ row: the diagonal alone
-            y[row] = make_double2(ym, ye);
-            if constexpr (DOT) acc += xr.x * ym + xr.y * ye;
-        }
-    }
-    if constexpr (DOT) block_sum_slots(acc, xy);
-}
-
 // out = (m, e) interleaved; e = NULL: zeros; zero_ground: the φₑ entry of a grounded node becomes 0 (the right-hand side of an eliminated row)
 __global__ void __launch_bounds__(256)
 k_bd_pack(int64_t n, const double *__restrict__ m, const double *__restrict__ e, const uint8_t *__restrict__ ground, int zero_ground, double2 *__restrict__ out)
@@ -146,13 +82,6 @@ __global__ void __launch_bounds__(256) k_bd_unpack(int64_t n, const double2 *__r
 {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) { const double2 v = in[i]; if (m) m[i] = v.x; if (e) e[i] = v.y; }
-}
-
-// z = B⁻¹ r of one node
-__device__ __forceinline__ double2 bd_precondition(const double *__restrict__ binv, int64_t i, double2 r)
-{
-    const double b11 = binv[3 * i], b12 = binv[3 * i + 1], b22 = binv[3 * i + 2];
-    return make_double2(b11 * r.x + b12 * r.y, b12 * r.x + b22 * r.y);
 }
 
 // the three vector kernels of launch_cg (tb_krylov.hip) on node pairs, B⁻¹ in the place of D⁻¹ — same scalars, same slot groups, same sticky flag
@@ -213,13 +142,6 @@ k_bd_direction(int64_t n, const double *__restrict__ rz, const double *__restric
     }
 }
 
-template <bool DOT>
-static void enqueue_apply(tb_bidomain *h, const double *x, double *y, double *xy)
-{
-    hipLaunchKernelGGL((k_bd_apply<DOT>), dim3((unsigned)((h->n_slices + 3) / 4)), dim3(256), 0, h->pat->mesh->dev->stream, h->n, h->n_slices, h->d_base, h->entries, h->d_col,
-                       h->d_val, h->d_ground, h->ground_diag, (const double2 *)x, (double2 *)y, xy);
-}
-
 static void free_bidomain(tb_bidomain *h)
 {
     if (!h) return;
@@ -275,9 +197,6 @@ static int bidomain_pcg(tb_bidomain *h, const double *b, double *x, double rtol,
 
 using namespace tb;
 
-// the interleaved vectors are read and written as 16-byte pairs
-#define BD_ALIGNED(ptr_, who_) TB_REQUIRE(((uintptr_t)(ptr_) & 15) == 0, who_ ": an interleaved vector must be 16-byte aligned")
-
 extern "C" {
 
 int tb_bidomain_create(tb_pattern *pat, tb_bidomain **out)
@@ -332,6 +251,7 @@ int tb_bidomain_set_matrices(tb_bidomain *h, tb_pattern *pat, const double *d_M,
                        d_M, d_Ki, d_Ke, dt, d_ground, ground_diag, h->d_col, h->d_val, h->d_binv, h->d_ground);
     TB_HIP(hipGetLastError());
     h->have_matrices = true;
+    ++h->generation;
     return TB_OK;
 }
 

@@ -6,6 +6,7 @@
 #include <ctime>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -478,6 +479,28 @@ int launch_cg1_iteration(tb_pattern *pat, const double *A, const double *dinv, d
 inline double stopping_tolerance(double atol, double rtol, double rnorm0)
 {
     return std::isfinite(rnorm0) ? atol + rtol * rnorm0 : __builtin_nan("");
+}
+
+// Largest eigenvalue of the symmetric tridiagonal with diagonal al[0 … k) and off-diagonals be[1 … k) (be[0] unused: 0), by bisection on the Sturm count:
+// the Ritz value of the Lanczos estimates of λmax (estimate_lambda_max in tb_krylov.hip, the block system's in tb_bidomain_mg.hip).
+inline double largest_tridiagonal_eigenvalue(const double *al, const double *be, int kdone)
+{
+    double hi = 0.0;
+    for (int k = 0; k < kdone; ++k) hi = std::max(hi, std::fabs(al[k]) + std::fabs(be[k]) + (k + 1 < kdone ? std::fabs(be[k + 1]) : 0.0));
+    double lo = 0.0;
+    for (int itb = 0; itb < 80; ++itb) {
+        const double x0 = 0.5 * (lo + hi);
+        int above = 0; // eigenvalues greater than x0 = number of positive pivots of T − x0 I
+        double q = al[0] - x0;
+        if (q > 0) ++above;
+        for (int k = 1; k < kdone; ++k) {
+            if (q == 0.0) q = 1e-300;
+            q = al[k] - x0 - be[k] * be[k] / q;
+            if (q > 0) ++above;
+        }
+        if (above > 0) lo = x0; else hi = x0;
+    }
+    return hi;
 }
 
 // ---- status block and host readback (tb_api.cpp) ----

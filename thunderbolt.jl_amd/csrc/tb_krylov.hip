@@ -618,22 +618,8 @@ int estimate_lambda_max(tb_pattern *pat, const double *A, const double *dinv, do
                 hipLaunchKernelGGL(k_scale_to, dim3(g), dim3(256), 0, dev->stream, n, 1.0 / be[k + 1], w, v);
             }
         }
-        if (kdone > 0) { // largest eigenvalue of the tridiagonal (α, β) by bisection on the Sturm count
-            double hi = 0.0;
-            for (int k = 0; k < kdone; ++k) hi = std::max(hi, std::fabs(al[k]) + std::fabs(be[k]) + (k + 1 < kdone ? std::fabs(be[k + 1]) : 0.0));
-            double lo = 0.0;
-            for (int itb = 0; itb < 80; ++itb) {
-                const double x0 = 0.5 * (lo + hi);
-                int above = 0; // eigenvalues greater than x0 = number of positive pivots of T − x0 I
-                double q = al[0] - x0;
-                if (q > 0) ++above;
-                for (int k = 1; k < kdone; ++k) {
-                    if (q == 0.0) q = 1e-300;
-                    q = al[k] - x0 - be[k] * be[k] / q;
-                    if (q > 0) ++above;
-                }
-                if (above > 0) lo = x0; else hi = x0;
-            }
+        if (kdone > 0) {
+            const double hi = largest_tridiagonal_eigenvalue(al, be, kdone);
             lmax = std::min(gersh, 1.05 * hi);
         }
     }

@@ -10,54 +10,13 @@
 #include <cstring>
 
 #include "tb_internal.h"
+#include "tb_mg_internal.hpp"
 #include "tb_mg_planners.hpp"
 #include "tb_reduce.hpp"
 
 namespace tb {
 
 static_assert(mgplan::ERR_BAD_ARG == TB_ERR_BAD_ARG && mgplan::ERR_PATTERN == TB_ERR_PATTERN && mgplan::ERR_UNSUPPORTED == TB_ERR_UNSUPPORTED, "planner codes");
-
-constexpr int MG_COARSEST_MAX = 1024; // dofs of the coarsest level: its inverse is dense
-
-struct MgLevel {
-    tb_pattern *pat = nullptr;
-    int64_t n = 0, nnz = 0;
-    double *d_A = nullptr;          // the level's operator: owned below the finest level
-    const double *A = nullptr;      // what the cycle reads (finest: the caller's array of the latest setup)
-    double *d_vec = nullptr;        // dinv | d | w | x | r (x, r: below the finest level) and, during setup, the Lanczos scratch
-    double *dinv = nullptr, *d = nullptr, *w = nullptr, *x = nullptr, *r = nullptr;
-    uint8_t *d_presc = nullptr;     // flags of the level's prescribed dofs (NULL: none)
-    std::vector<uint8_t> h_presc;
-    double lmax = 0.0;
-    // to the level below (levels ≥ 1)
-    std::vector<int64_t> parent_ptr;
-    std::vector<int32_t> parent_idx;
-    bool has_transfer = false, p_transfer = false; // p_transfer: the level below carries the first-order field on the same cells (tb_mg_set_p_transfer)
-    bool blocked = false;           // the Galerkin plan to the level below is per 3 × 3 block (k_mg_galerkin_b3)
-    int32_t *d_brow = nullptr;      // block row of every 3 × 3 block of the level's pattern (levels on either side of a blocked plan)
-    int64_t *d_pptr = nullptr, *d_rptr = nullptr, *d_gptr = nullptr, *d_cdiag = nullptr;
-    int32_t *d_pcol = nullptr, *d_rcol = nullptr;
-    uint8_t *d_pexp = nullptr, *d_rexp = nullptr;
-    uint32_t *d_gterms = nullptr;
-    int64_t n_terms = 0;
-};
-
-} // namespace tb
-
-struct tb_mg {
-    tb_device *dev = nullptr;
-    std::vector<tb::MgLevel> lv;
-    bool planned = false, ready = false;
-    int degree = 2;
-    double ratio = 4.0;
-    double *d_cinv = nullptr; // dense inverse of the coarsest operator
-    double *d_scal = nullptr; // two scalars of the λmax estimate
-};
-
-namespace tb {
-
-// 2^−e for e in 0…7 without a table: the exponent field of 1.0 lowered by e
-__device__ __forceinline__ double pow2_neg(unsigned e) { return __longlong_as_double((long long)(1023u - e) << 52); }
 
 // A_c[k] = Σ over the recorded terms of 2^−e · A_f[fine nz]: 16 lanes share a coarse non-zero (≈ 90 terms each on a scalar field: the term words
 // are read as 64-byte runs), lane sums in term order, then a fixed butterfly over the 16 lanes.
@@ -228,25 +187,7 @@ k_mg_dense_inverse(int n, const int64_t *__restrict__ rowptr, const int32_t *__r
     for (int i = wv; i < n; i += nw)
         for (int64_t k = rowptr[i] + lane; k < rowptr[i + 1]; k += 64) C[(size_t)i * n + colidx[k]] = nz[k];
     __syncthreads();
-    for (int k = 0; k < n; ++k) {
-        const double piv = 1.0 / C[(size_t)k * n + k];
-        for (int i = wv; i < n; i += nw) {
-            if (i == k) continue;
-            const double f = C[(size_t)i * n + k] * piv;
-            for (int j = lane; j < n; j += 64)
-                if (j != k) C[(size_t)i * n + j] -= f * C[(size_t)k * n + j];
-        }
-        __syncthreads();
-        for (int j = threadIdx.x; j < n; j += blockDim.x)
-            if (j != k) { C[(size_t)k * n + j] *= piv; C[(size_t)j * n + k] *= -piv; }
-        if (threadIdx.x == 0) C[(size_t)k * n + k] = piv;
-        __syncthreads();
-    }
-    for (int i = wv; i < n; i += nw)
-        for (int j = i + 1 + lane; j < n; j += 64) {
-            const double s = 0.5 * (C[(size_t)i * n + j] + C[(size_t)j * n + i]);
-            C[(size_t)i * n + j] = s; C[(size_t)j * n + i] = s;
-        }
+    mg_gauss_jordan(n, C);
 }
 
 // x = C r, dense: one wavefront per row
@@ -287,7 +228,7 @@ static mgplan::LevelView view_of(const tb_pattern *p)
 }
 
 // symbolic phase: transfers, Galerkin plans, level storage, the SpMV plan of every level
-static int build_plans(tb_mg *mg)
+int build_plans(tb_mg *mg)
 {
     tb_device *dev = mg->dev;
     TB_NO_CAPTURE(dev);
@@ -371,6 +312,17 @@ static void launch_galerkin(tb_mg *mg, int fine_level)
     } else
         hipLaunchKernelGGL(k_mg_galerkin, dim3(blocks_of(L.nnz * 16, 256)), dim3(256), 0, dev->stream, L.nnz, U.d_gptr, U.d_gterms, U.A, L.d_A);
     if (L.d_presc) hipLaunchKernelGGL(k_mg_fill_diag, dim3(1), dim3(1024), 0, dev->stream, L.n, U.d_cdiag, L.d_presc, L.d_A);
+}
+
+// (tb_mg_internal.hpp) one value plane through the per-dof plan of fine_level, and the dense product, for the block cycle of tb_bidomain_mg.hip
+void launch_galerkin_plane(tb_mg *mg, int fine_level, const double *Af, double *Ac)
+{
+    MgLevel &U = mg->lv[fine_level], &L = mg->lv[fine_level - 1];
+    hipLaunchKernelGGL(k_mg_galerkin, dim3(blocks_of(L.nnz * 16, 256)), dim3(256), 0, mg->dev->stream, L.nnz, U.d_gptr, U.d_gterms, Af, Ac);
+}
+void launch_dense_apply(tb_device *dev, int n, const double *C, const double *r, double *x)
+{
+    hipLaunchKernelGGL(k_mg_dense_apply, dim3(blocks_of((int64_t)n * 64, 256)), dim3(256), 0, dev->stream, n, C, r, x);
 }
 
 static int smooth(tb_mg *mg, int l, const double *r, double *x, bool from_zero)
