@@ -51,6 +51,7 @@ typedef struct tb_locator tb_locator;
 typedef struct tb_ecg tb_ecg;
 typedef struct tb_bidomain tb_bidomain;
 typedef struct tb_bidomain_mg tb_bidomain_mg;
+typedef struct tb_eikonal tb_eikonal;
 
 enum {
     TB_OK = 0,
@@ -199,6 +200,8 @@ const char *tb_version(void);
  * the new form kind, which did not exist before.
  * Added under 10, purely additive: tb_bidomain_* (parabolic-elliptic bidomain block system: fused product, grounded block-Jacobi PCG).
  * Added under 10, purely additive: tb_bidomain_mg_* (geometric multigrid preconditioner of the bidomain block system: block V-cycle, preconditioned CG).
+ * Added under 10, purely additive: tb_eikonal_* (create, destroy, solve, residual, last_counts, potential), tb_host_eikonal_local_solve (eikonal activation times: fast iterative method; potential from an action-potential
+ * template).
  * A host binding compares tb_abi_revision() with the
  * TB_ABI_REVISION it was written against and refuses to run on a mismatch (julia/ThunderboltHIPBackend.jl does, in __init__) */
 #define TB_ABI_REVISION 10
@@ -532,6 +535,49 @@ int tb_ecg_update(tb_ecg *ecg, const double *d_phi);            /* update_ecg! â
 int tb_ecg_evaluate(tb_ecg *ecg, int64_t n_electrodes, const double *d_x, double kappa_t, double *d_out); /* evaluate_ecg, ecg.jl:80-137 */
 int tb_ecg_leads(tb_device *dev, int64_t n_leads, int64_t n, const double *d_Z, int64_t ldz, const double *d_v, double alpha, double *d_out); /* evaluate_ecg(::Geselowitzâ€¦), ecg.jl:617-619 */
 int tb_scrub_scale(tb_device *dev, int64_t n, double alpha, double *d_x);  /* x = Î±Â·(isnan(x) ? 0 : x): ecg.jl:345-347, 612 */
+
+/* ------------------------------------------------------------------ eikonal activation times
+ * The reference lists a reaction-eikonal ECG as its next electrophysiology tutorial and has not written it (docs/src/literate-tutorials/ep05_eikonal.jl
+ * is a stub): there is no reference interface to cite.  Solved is  âˆš(âˆ‡Táµ€ G âˆ‡T) = 1  for the arrival time T at the nodes, T = tâ‚€ at source nodes,
+ * G the squared conduction velocity: the tensor of a TB_FORM_DIFFUSION form, so every TB_COEF_* kind and `wrap` work as in an assembly.  Per cell G
+ * is the form's constant tensor, or the arithmetic mean of its table over the cell's quadrature points (8 on hexahedra, 4 on tetrahedra); only the
+ * symmetric part enters; M = Gâ»Â¹ is stored, six doubles per cell.
+ * Nodes are the dofs of the form's scalar first-order field: d_T, d_res and source_nodes are in dof numbering (0-based), which is what the
+ * operators and tb_ecg_update take.
+ * Scheme: first order on tetrahedra.  A TB_TET4 mesh is used as it is.  A TB_HEX8 mesh is cut implicitly, every cell by its LOCAL vertex order into
+ * the six Kuhn tetrahedra listed at tb_host_generate_grid_tet (no tetrahedral mesh is materialised).  On an unstructured hexahedral mesh the face
+ * diagonals of two neighbouring cells need not agree; the scheme stays monotone and consistent all the same, because each tetrahedron's update is
+ * the length of an admissible path:  min over Î» in the unit simplex of  Î£ Î»áµ¢Táµ¢ + âˆš(e(Î»)áµ€ M e(Î»)),  e(Î») = xâ‚„ âˆ’ Î£ Î»áµ¢xáµ¢  (tb_host_eikonal_local_solve
+ * is that solver on the host: x4 3 doubles, x123 3 Ã— 3 row by row, T123 finite or +âˆž, M6 = xx, xy, xz, yy, yz, zz; lambda3 may be NULL).  A vertex
+ * with T = +âˆž drops out; the solver produces no NaN.
+ * Iteration: the fast iterative method as Jacobi sweeps on two buffers.  A node is active iff a neighbour changed in the previous sweep; an active
+ * node takes the minimum of its local solves in a fixed order (ascending cell, tetrahedron) and accepts it iff T_old = âˆž or T_old âˆ’ t > rtolÂ·t.
+ * The active set is a flag array and no floating-point atomic touches T: two solves, and two tb_eikonal objects of one form, give identical bits.
+ * The host reads the number of changed nodes every 16 sweeps and stops at the first sweep without a change, or after max_sweeps sweeps; values only
+ * decrease, each time by more than rtol, so the loop ends on its own and max_sweeps is the guard.  Nodes no source reaches keep T = +âˆž.
+ * tb_eikonal_create: scalar first-order field on a TB_HEX8 or TB_TET4 mesh, no cell set (else TB_ERR_UNSUPPORTED: TB_QUAD4 / 2-D, second-order
+ * fields, subdomains, several ranks and Float32 are out of scope, like eikonal-diffusion / -reaction variants, re-entry and repolarisation times).
+ * A tensor that is not positive definite: TB_ERR_BAD_ARG, the message names the cell.  Waits for the device: refused inside an open graph capture.
+ * The form and its mesh must outlive the object.
+ * tb_eikonal_solve: TB_OK whether or not it converged â€” *sweeps is the number of sweeps up to and including the first one without a change (or the
+ * number made), *converged 1 or 0.  Duplicate or out-of-range source nodes, a negative, infinite or NaN source time, rtol â‰¤ 0 (or â‰¥ 1) and
+ * max_sweeps < 1: TB_ERR_BAD_ARG.  Reads back: refused inside an open graph capture.
+ * tb_eikonal_residual: d_res[i] = d_T[i] âˆ’ min(local solves on d_T) for every node that was not a source of the latest solve (0 at the sources, 0
+ * where both are âˆž): the stopping criterion re-evaluated, |d_res[i]| â‰¤ rtolÂ·d_T[i] after a converged solve.  Enqueues only.
+ * tb_eikonal_last_counts: counts3 = {nodes evaluated, updates accepted, local solves made} of the latest solve (what a rate is quoted over).
+ * tb_eikonal_potential: d_phi[i] = U(t âˆ’ d_T[i]) with U tabulated at t0 + kÂ·dt, k < n_samples (device array), linear between the samples, held at
+ * the first sample before t0 and where d_T = âˆž, at the last one beyond the table.  Enqueues only â€” no allocation, no wait â€” so it fits a captured
+ * step beside tb_ecg_update; inside a capture t is read from the time slot tb_graph_launch writes. */
+int tb_eikonal_create(tb_form *diffusion, tb_eikonal **out);
+int tb_eikonal_destroy(tb_eikonal *e);
+int tb_eikonal_solve(tb_eikonal *e, int64_t n_sources, const int32_t *source_nodes, const double *source_times,
+                     double rtol, int max_sweeps, double *d_T, int *sweeps, int *converged);
+int tb_eikonal_residual(tb_eikonal *e, const double *d_T, double *d_res);
+int tb_eikonal_last_counts(const tb_eikonal *e, int64_t *counts3);
+int tb_eikonal_potential(tb_device *dev, int64_t n, const double *d_T, double t, int64_t n_samples, double t0, double dt,
+                         const double *d_template, double *d_phi);
+int tb_host_eikonal_local_solve(const double *x4, const double *x123, const double *T123, const double *M6,
+                                double *value, double *lambda3);
 
 /* ------------------------------------------------------------------ pointwise sarcomere dynamics
  * Sarcomere models with internal state (src/modeling/solid/contraction.jl:337-632).  TB_SARCOMERE_RDQ20MF: 20 states per point

@@ -614,7 +614,7 @@ end
 # ---------------------------------------------------------------- round 6: the rest of the boundary the hot path's rows of SURVEY §8 use, bound the same way
 # (device queue and events; pattern accessors; Rush–Larsen and RTC reaction steps; the other Krylov entries; cell sets and accumulation of a form; facet
 # forms; sarcomere steps and the condensed-mechanics setters).  The host generators (tb_host_generate_grid_*, tb_host_close_dofs, tb_host_build_pattern,
-# tb_host_perturb_nodes) and the host-side evaluators (tb_host_material_eval*, tb_host_sarcomere_*; tb_host_maxwell_eval is bound) stay unbound: Ferrite and the reference's own Julia
+# tb_host_perturb_nodes) and the host-side evaluators (tb_host_material_eval*, tb_host_sarcomere_*; tb_host_maxwell_eval and tb_host_eikonal_local_solve are bound) stay unbound: Ferrite and the reference's own Julia
 # routines are the host side of those.
 libtbhip_version() = unsafe_string(ccall((:tb_version, libtbhip), Cstring, ()))
 # the library's kernels on a queue the host framework owns (its own stream, or the legacy default stream) — ordering with the host's device work then needs no events
@@ -878,6 +878,52 @@ evaluate_leads!(out::HIPVector{Float64}, Z::HIPVector{Float64}, nleads::Integer,
     check(ccall((:tb_ecg_leads, libtbhip), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Cdouble, Ptr{Float64}), v.dev.handle, nleads, v.n, Z.ptr, ldz, v.ptr, α, out.ptr))
 # κ∇φₘ_t[isnan.(κ∇φₘ_t)] .= 0.0; κ∇φₘ_t .*= α (ecg.jl:345-347, 612) in one pass
 scrub_scale!(x::HIPVector{Float64}, α::Real) = check(ccall((:tb_scrub_scale, libtbhip), Cint, (Ptr{Cvoid}, Int64, Cdouble, Ptr{Float64}), x.dev.handle, x.n, α, x.ptr))
+
+# ---------------------------------------------------------------- eikonal activation times (the reference's planned ep05_eikonal tutorial; no reference code)
+# √(∇Tᵀ G ∇T) = 1 with G the tensor of a diffusion form: fast iterative method on the device (Jacobi sweeps on two buffers, flag-array active set, no
+# floating-point atomics on T: two solves give identical bits).  Nodes are the dofs of the scalar first-order field; hexahedra are cut implicitly
+# into Kuhn tetrahedra.  The potential φₘ = U(t − T) from a tabulated template goes to update_ecg! as it is.
+mutable struct HIPEikonalCache{Tv}
+    handle::Ptr{Cvoid}
+    op::HIPBilinearOperator{Tv}   # keeps the diffusion form (G) and its mesh alive
+    sweeps::Int
+    converged::Bool
+end
+function EikonalActivationCache(op::HIPBilinearOperator{Tv}) where {Tv}
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:tb_eikonal_create, libtbhip), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), op.form, h))
+    cache = HIPEikonalCache{Tv}(h[], op, 0, false)
+    finalizer(c -> (ccall((:tb_eikonal_destroy, libtbhip), Cint, (Ptr{Cvoid},), c.handle); c.handle = C_NULL), cache)
+    return cache
+end
+# source_dofs0: 0-based dofs of the source vertices, times ≥ 0; T: one entry per dof (+Inf where no source reaches)
+function solve_activation!(T::HIPVector{Float64}, cache::HIPEikonalCache, source_dofs0::Vector{Int32}, times::Vector{Float64}; rtol::Real = 1e-12,
+                           max_sweeps::Integer = T.n)
+    sweeps = Ref{Cint}(0); conv = Ref{Cint}(0)
+    check(ccall((:tb_eikonal_solve, libtbhip), Cint, (Ptr{Cvoid}, Int64, Ptr{Int32}, Ptr{Float64}, Cdouble, Cint, Ptr{Float64}, Ref{Cint}, Ref{Cint}),
+        cache.handle, length(source_dofs0), source_dofs0, times, rtol, max_sweeps, T.ptr, sweeps, conv))
+    cache.sweeps = Int(sweeps[]); cache.converged = conv[] != 0
+    return T
+end
+eikonal_residual!(res::HIPVector{Float64}, cache::HIPEikonalCache, T::HIPVector{Float64}) =
+    check(ccall((:tb_eikonal_residual, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), cache.handle, T.ptr, res.ptr))
+# (nodes evaluated, updates accepted, local solves made) of the latest solve
+function eikonal_last_counts(cache::HIPEikonalCache)
+    c = zeros(Int64, 3)
+    check(ccall((:tb_eikonal_last_counts, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Int64}), cache.handle, c))
+    return (c[1], c[2], c[3])
+end
+# φₘ = U(t − T): U sampled at t0 + k·dt on the device, clamped at both ends (the first sample where T = Inf)
+activation_potential!(φₘ::HIPVector{Float64}, T::HIPVector{Float64}, t::Real, template::HIPVector{Float64}, t0::Real, dt::Real) =
+    check(ccall((:tb_eikonal_potential, libtbhip), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Cdouble, Int64, Cdouble, Cdouble, Ptr{Float64}, Ptr{Float64}),
+        T.dev.handle, T.n, T.ptr, t, template.n, t0, dt, template.ptr, φₘ.ptr))
+# the local solver on the host (one tetrahedron): value and minimiser λ
+function eikonal_local_solve(x4::Vector{Float64}, x123::Vector{Float64}, T123::Vector{Float64}, M6::Vector{Float64})
+    value = Ref{Cdouble}(0.0); λ = zeros(3)
+    check(ccall((:tb_host_eikonal_local_solve, libtbhip), Cint, (Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Cdouble}, Ptr{Float64}),
+        x4, x123, T123, M6, value, λ))
+    return value[], λ
+end
 
 # ---------------------------------------------------------------- parabolic-elliptic bidomain block system (src/modeling/electrophysiology.jl:305-326)
 # The 2 × 2 block operator [M − ΔtKᵢ, −ΔtKᵢ; −ΔtKᵢ, −Δt(Kᵢ + Kₑ)] over the scalar pattern, φₑ grounded at flagged nodes.  Block vectors are

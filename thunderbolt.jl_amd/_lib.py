@@ -242,6 +242,13 @@ SIGNATURES = {
     "tb_bidomain_mg_level_planes": (C.c_int, [vp, C.c_int, C.POINTER(vp), c_i64p]),
     "tb_bidomain_mg_level_lambda_max": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double)]),
     "tb_bidomain_mg_cycle_below": (C.c_int, [vp, C.c_int]),
+    "tb_eikonal_create": (C.c_int, [vp, C.POINTER(vp)]),
+    "tb_eikonal_destroy": (C.c_int, [vp]),
+    "tb_eikonal_solve": (C.c_int, [vp, C.c_int64, c_i32p, c_dp, C.c_double, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "tb_eikonal_residual": (C.c_int, [vp, vp, vp]),
+    "tb_eikonal_last_counts": (C.c_int, [vp, c_i64p]),
+    "tb_eikonal_potential": (C.c_int, [vp, C.c_int64, vp, C.c_double, C.c_int64, C.c_double, C.c_double, vp, vp]),
+    "tb_host_eikonal_local_solve": (C.c_int, [c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "tb_host_generate_grid_hex": (C.c_int, [C.c_int, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_i32p]),
     "tb_host_generate_grid_tet": (C.c_int, [C.c_int, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_i32p]),
     "tb_host_generate_grid_quad": (C.c_int, [C.c_int, C.c_int, c_dp, c_dp, c_dp, c_i32p]),
