@@ -202,6 +202,7 @@ const char *tb_version(void);
  * Added under 10, purely additive: tb_bidomain_mg_* (geometric multigrid preconditioner of the bidomain block system: block V-cycle, preconditioned CG).
  * Added under 10, purely additive: tb_eikonal_* (create, destroy, solve, residual, last_counts, potential), tb_host_eikonal_local_solve (eikonal activation times: fast iterative method; potential from an action-potential
  * template).
+ * Added under 10, purely additive: tb_amg_*, tb_pcg_solve_amg, tb_mg_set_coarse_amg, tb_mg_coarse_amg (smoothed-aggregation algebraic multigrid).
  * A host binding compares tb_abi_revision() with the
  * TB_ABI_REVISION it was written against and refuses to run on a mismatch (julia/ThunderboltHIPBackend.jl does, in __init__) */
 #define TB_ABI_REVISION 10
@@ -956,6 +957,60 @@ int tb_mg_galerkin(tb_mg *mg, int fine_level);
 int tb_mg_destroy(tb_mg *mg);
 int tb_pcg_solve_mg(tb_pattern *pat, const double *d_Anz, const double *d_b, double *d_x, double rtol, double atol, int maxiter, tb_mg *mg, int *iters,
                     double *resnorm);
+
+/* ------------------------------------------------------------------ smoothed-aggregation algebraic multigrid (tb_amg.hip)
+ * SmoothedAggregationCoarseSolver(), the default pcoarse_solver of the reference's PMGPrecon (src/solver/linear/multigrid.jl:27; its how-to and extension
+ * import AlgebraicMultigrid for it): a multigrid that needs only the matrix — any mesh the readers load, tetrahedra included.  Level 0 is the caller's
+ * matrix, level l + 1 the Galerkin operator of the aggregates of level l (the reverse of tb_mg's numbering: the number of levels is a result).
+ * Method, per level, on a CSR with sorted columns and a structurally symmetric pattern, every dof carrying a component label c(i):
+ *   strength     mᵢ = max |aᵢⱼ| over j ≠ i with c(j) = c(i); (i, j), j ≠ i, c(i) = c(j), is strong from i iff mᵢ > 0 and |aᵢⱼ| ≥ θ·mᵢ; the graph S holds
+ *                (i, j) iff it is strong from i or from j.  Couplings between components are never strong (unknown-based AMG).  Device, one byte per non-zero.
+ *   aggregation  host, index order, flags only.  Pass 1: i ascending, i and all its S-neighbours free → a new aggregate.  Pass 2, against the state after
+ *                pass 1: a free i joins the aggregate of its lowest-numbered aggregated S-neighbour.  Pass 3: i ascending, a free i forms an aggregate
+ *                with its still-free S-neighbours.  A dof without S-neighbours (an eliminated Dirichlet row) stays outside: its row of P is empty, the
+ *                smoother alone handles it, and a zero residual there gives z = 0.
+ *   transfer     T(i, agg(i)) = 1/√|agg(i)|; P = T − ω D⁻¹ A T on the pattern of A·T (rows of outside dofs empty), ω = 4 / (3 λ), λ the level's estimate of
+ *                λmax(D⁻¹A) (Lanczos + Gershgorin, the rule of the Chebyshev preconditioner), which serves the smoother as well; R = Pᵀ stored explicitly.
+ *   coarse       A_c = R (A P), both products on planned patterns; D⁻¹ = 1/aᵢᵢ (0 where no diagonal is stored or it is zero).
+ *   recursion    stops at n ≤ max_coarse, at max_levels levels, or when aggregation no longer reduces n; the last level is inverted densely and may hold at
+ *                most 1 024 dofs (TB_ERR_UNSUPPORTED otherwise, with the condition named).
+ *   cycle        V(degree, degree) from zero with the Chebyshev–Jacobi smoother on [λ/interval_ratio, λ], the recurrence of tb_mg_apply.
+ * No floating-point atomics, every sum in one recorded order: two setups give the same bits in every level matrix and P, two applications the same z.
+ *   tb_amg_create       checks the pattern (TB_ERR_BAD_ARG names the offending row); comp_host: one label per dof (host; NULL: all 0).  theta in 0..1
+ *                       (0.25), max_coarse ≥ 1 (1 024), max_levels in 1..64 (16).  The pattern must outlive the hierarchy.
+ *   tb_amg_setup        the first call plans level by level (strength → download → host planner → upload → numeric); every later call keeps the
+ *                       aggregates and patterns and redoes the numeric phase only (smoothed P, Galerkin chain, D⁻¹, λ per level, last inverse): what a
+ *                       Newton iteration or a new Δt repeats.  d_Anz is read by tb_amg_apply as well.  Reads scalars back: not inside a graph capture.
+ *   tb_amg_replan       drops the plan: the next setup aggregates anew
+ *   tb_amg_apply        z = M⁻¹ r, one V cycle from z = 0; enqueues only (fits inside tb_graph_begin / tb_graph_end)
+ *   tb_pcg_solve_amg    tb_pcg_solve with z = M⁻¹ r by tb_amg_apply: stopping rule, tb_solver_last_tolerance and non-finite behaviour of tb_pcg_solve_mg
+ *   inspectors (host outputs, any array may be NULL; after one setup): tb_amg_n_levels; tb_amg_level_size (dofs, non-zeros, aggregates — 0 on the last
+ *                       level); tb_amg_level_csr (A_l: n + 1 row pointers, nnz columns and values); tb_amg_level_prolongator (P from level + 1 to level:
+ *                       its non-zero count, n + 1 row pointers, columns, values); tb_amg_level_aggregates (−1: outside); tb_amg_level_strength (one
+ *                       byte per non-zero of A_l); tb_amg_level_lambda_max.  The last four are refused on the last level.
+ *   tb_mg_set_coarse_amg  level 0 of a tb_mg hierarchy is solved by one AMG V-cycle instead of the dense inverse (ChainedMGPrecon(PMGPrecon(),
+ *                       SmoothedAggregationCoarseSolver()) of the reference); the 1 024-dof limit then applies to the AMG's own last level, the labels are
+ *                       the components of the level-0 field, degree and interval_ratio those of tb_mg_setup, which sets the AMG up after the Galerkin
+ *                       chain.  Call it before tb_mg_setup; without it tb_mg_* behaves bit for bit as before.
+ *   tb_mg_coarse_amg    that hierarchy, for the inspectors (after one tb_mg_setup; NULL without tb_mg_set_coarse_amg).  The tb_mg owns it: it is not to be
+ *                       set up, re-planned or destroyed by the caller, and a new plan of the tb_mg replaces it. */
+typedef struct tb_amg tb_amg;
+int tb_amg_create(tb_pattern *pat, const int8_t *comp_host, double theta, int max_coarse, int max_levels, tb_amg **out);
+int tb_amg_setup(tb_amg *amg, const double *d_Anz, int degree, double interval_ratio);
+int tb_amg_replan(tb_amg *amg);
+int tb_amg_apply(tb_amg *amg, const double *d_r, double *d_z);
+int tb_amg_destroy(tb_amg *amg);
+int tb_pcg_solve_amg(tb_pattern *pat, const double *d_Anz, const double *d_b, double *d_x, double rtol, double atol, int maxiter, tb_amg *amg, int *iters,
+                     double *resnorm);
+int tb_amg_n_levels(tb_amg *amg, int *n_levels);
+int tb_amg_level_size(tb_amg *amg, int level, int64_t *n, int64_t *nnz, int64_t *n_aggregates);
+int tb_amg_level_csr(tb_amg *amg, int level, int64_t *rowptr, int32_t *colidx, double *values);
+int tb_amg_level_prolongator(tb_amg *amg, int level, int64_t *nnz, int64_t *rowptr, int32_t *colidx, double *values);
+int tb_amg_level_aggregates(tb_amg *amg, int level, int32_t *aggregate);
+int tb_amg_level_strength(tb_amg *amg, int level, uint8_t *flags);
+int tb_amg_level_lambda_max(tb_amg *amg, int level, double *lmax);
+int tb_mg_set_coarse_amg(tb_mg *mg, double theta, int max_coarse, int max_levels);
+int tb_mg_coarse_amg(tb_mg *mg, tb_amg **out);
 
 /* ------------------------------------------------------------------ parabolic-elliptic bidomain block system (tb_bidomain.hip)
  * ParabolicEllipticBidomainModel (src/modeling/electrophysiology.jl:305-326, declared "Not implemented yet" there).  Backward Euler on the transformed

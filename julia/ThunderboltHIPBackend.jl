@@ -758,6 +758,87 @@ function pcg_mg!(x::HIPVector{Float64}, A::HIPSparseMatrixCSR{Float64}, b::HIPVe
         A.ddh.pattern, A.nzval.ptr, b.ptr, x.ptr, rtol, atol, maxiter, mg.handle, it, res))
     return Int(it[]), res[]
 end
+# Smoothed-aggregation algebraic multigrid (SmoothedAggregationCoarseSolver, the default pcoarse_solver of PMGPrecon: src/solver/linear/multigrid.jl:27).
+# `pattern`: the tb_pattern of the matrix; `components`: one Int8 label per dof (empty: one component).  Level 0 is the matrix, level l + 1 the Galerkin
+# operator of level l's aggregates.  The first `setup!` plans, every later one redoes the numeric phase on the same aggregates; `replan!` drops the plan.
+mutable struct HIPAMGPrecon
+    handle::Ptr{Cvoid}
+    degree::Int
+    interval_ratio::Float64
+end
+function HIPAMGPrecon(pattern::Ptr{Cvoid}; components::Vector{Int8} = Int8[], theta = 0.25, degree = 2, interval_ratio = 4.0, max_coarse = 1024, max_levels = 16)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:tb_amg_create, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Int8}, Cdouble, Cint, Cint, Ref{Ptr{Cvoid}}), pattern,
+        isempty(components) ? Ptr{Int8}(C_NULL) : pointer(components), theta, max_coarse, max_levels, h))
+    amg = HIPAMGPrecon(h[], degree, interval_ratio)
+    finalizer(a -> ccall((:tb_amg_destroy, libtbhip), Cint, (Ptr{Cvoid},), a.handle), amg)
+    return amg
+end
+setup!(amg::HIPAMGPrecon, A::HIPSparseMatrixCSR{Float64}) =
+    check(ccall((:tb_amg_setup, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint, Cdouble), amg.handle, A.nzval.ptr, amg.degree, amg.interval_ratio))
+replan!(amg::HIPAMGPrecon) = check(ccall((:tb_amg_replan, libtbhip), Cint, (Ptr{Cvoid},), amg.handle))
+amg_apply!(z::HIPVector{Float64}, amg::HIPAMGPrecon, r::HIPVector{Float64}) =
+    check(ccall((:tb_amg_apply, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), amg.handle, r.ptr, z.ptr))
+function amg_n_levels(amg::HIPAMGPrecon)
+    n = Ref{Cint}(0)
+    check(ccall((:tb_amg_n_levels, libtbhip), Cint, (Ptr{Cvoid}, Ref{Cint}), amg.handle, n))
+    return Int(n[])
+end
+# (dofs, non-zeros, aggregates) of a level (0-based; the last level has no aggregates)
+function amg_level_size(amg::HIPAMGPrecon, level::Integer)
+    n = Ref{Int64}(0); nnz = Ref{Int64}(0); na = Ref{Int64}(0)
+    check(ccall((:tb_amg_level_size, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ref{Int64}, Ref{Int64}, Ref{Int64}), amg.handle, level, n, nnz, na))
+    return n[], nnz[], na[]
+end
+# A_l as host arrays (rowptr, colidx 0-based, values)
+function amg_level_csr(amg::HIPAMGPrecon, level::Integer)
+    n, nnz, _ = amg_level_size(amg, level)
+    ptr = Vector{Int64}(undef, n + 1); col = Vector{Int32}(undef, nnz); val = Vector{Float64}(undef, nnz)
+    check(ccall((:tb_amg_level_csr, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}), amg.handle, level, ptr, col, val))
+    return ptr, col, val
+end
+# P from level + 1 to level as host arrays
+function amg_level_prolongator(amg::HIPAMGPrecon, level::Integer)
+    n, _, _ = amg_level_size(amg, level)
+    nnz = Ref{Int64}(0)
+    check(ccall((:tb_amg_level_prolongator, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ref{Int64}, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}), amg.handle, level, nnz,
+        Ptr{Int64}(C_NULL), Ptr{Int32}(C_NULL), Ptr{Float64}(C_NULL)))
+    ptr = Vector{Int64}(undef, n + 1); col = Vector{Int32}(undef, nnz[]); val = Vector{Float64}(undef, nnz[])
+    check(ccall((:tb_amg_level_prolongator, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ref{Int64}, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}), amg.handle, level, nnz, ptr, col, val))
+    return ptr, col, val
+end
+function amg_level_aggregates(amg::HIPAMGPrecon, level::Integer)
+    agg = Vector{Int32}(undef, amg_level_size(amg, level)[1])
+    check(ccall((:tb_amg_level_aggregates, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ptr{Int32}), amg.handle, level, agg))
+    return agg
+end
+function amg_level_strength(amg::HIPAMGPrecon, level::Integer)
+    s = Vector{UInt8}(undef, amg_level_size(amg, level)[2])
+    check(ccall((:tb_amg_level_strength, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ptr{UInt8}), amg.handle, level, s))
+    return s
+end
+function amg_lambda_max(amg::HIPAMGPrecon, level::Integer)
+    r = Ref{Cdouble}(0)
+    check(ccall((:tb_amg_level_lambda_max, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ref{Cdouble}), amg.handle, level, r))
+    return r[]
+end
+# KrylovMGSolver(CG, amg): rebuild the numeric phase from the matrix, then CG with one cycle per iteration
+function pcg_amg!(x::HIPVector{Float64}, A::HIPSparseMatrixCSR{Float64}, b::HIPVector{Float64}, amg::HIPAMGPrecon; rtol = 1e-5, atol = 1e-6, maxiter = 1000, setup = true)
+    setup && setup!(amg, A)
+    it = Ref{Cint}(0); res = Ref{Cdouble}(0)
+    check(ccall((:tb_pcg_solve_amg, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Cint, Ptr{Cvoid}, Ref{Cint}, Ref{Cdouble}),
+        A.ddh.pattern, A.nzval.ptr, b.ptr, x.ptr, rtol, atol, maxiter, amg.handle, it, res))
+    return Int(it[]), res[]
+end
+# the coarsest level of a geometric or p-hierarchy is solved by one AMG cycle instead of the dense inverse (call before the first setup!); afterwards
+# coarse_amg returns that hierarchy's handle for the amg_* inspectors (owned by the HIPGMGPrecon)
+set_coarse_amg!(mg::HIPGMGPrecon; theta = 0.25, max_coarse = 1024, max_levels = 16) =
+    check(ccall((:tb_mg_set_coarse_amg, libtbhip), Cint, (Ptr{Cvoid}, Cdouble, Cint, Cint), mg.handle, theta, max_coarse, max_levels))
+function coarse_amg(mg::HIPGMGPrecon)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:tb_mg_coarse_amg, libtbhip), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), mg.handle, h))
+    return h[]
+end
 function absmax(v::HIPVector{Float64}; stride = 1)
     r = Ref{Cdouble}(0)
     check(ccall((:tb_absmax, libtbhip), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ref{Cdouble}), v.dev.handle, v.n ÷ stride, v.ptr, stride, r))

@@ -13,6 +13,8 @@ from .coordinates import (compute_lv_coordinate_system, compute_midmyocardial_se
                           wrap_rotational, apicobasal_from_laplace)
 from .meshgen import generate_ring_mesh, generate_open_ring_mesh, generate_ideal_lv_mesh_hex, ideal_lv_microstructure, uniform_refinement  # noqa: F401
 from .meshgen import uniform_refinement_with_maps, GridHierarchy  # noqa: F401
+from . import amg  # noqa: F401
+from .amg import AMGPrecon, AlgebraicHierarchy  # noqa: F401
 from . import multigrid  # noqa: F401
 from .multigrid import GMGPrecon, PMGPrecon, ChainedMGPrecon, KrylovMGSolver, MultigridHierarchy  # noqa: F401
 from . import chamber  # noqa: F401

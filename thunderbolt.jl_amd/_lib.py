@@ -226,6 +226,21 @@ SIGNATURES = {
     "tb_mg_galerkin": (C.c_int, [vp, C.c_int]),
     "tb_mg_destroy": (C.c_int, [vp]),
     "tb_pcg_solve_mg": (C.c_int, [vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "tb_amg_create": (C.c_int, [vp, vp, C.c_double, C.c_int, C.c_int, C.POINTER(vp)]),
+    "tb_amg_setup": (C.c_int, [vp, vp, C.c_int, C.c_double]),
+    "tb_amg_replan": (C.c_int, [vp]),
+    "tb_amg_apply": (C.c_int, [vp, vp, vp]),
+    "tb_amg_destroy": (C.c_int, [vp]),
+    "tb_pcg_solve_amg": (C.c_int, [vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "tb_amg_n_levels": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "tb_amg_level_size": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tb_amg_level_csr": (C.c_int, [vp, C.c_int, c_i64p, c_i32p, c_dp]),
+    "tb_amg_level_prolongator": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int64), c_i64p, c_i32p, c_dp]),
+    "tb_amg_level_aggregates": (C.c_int, [vp, C.c_int, c_i32p]),
+    "tb_amg_level_strength": (C.c_int, [vp, C.c_int, vp]),
+    "tb_amg_level_lambda_max": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double)]),
+    "tb_mg_set_coarse_amg": (C.c_int, [vp, C.c_double, C.c_int, C.c_int]),
+    "tb_mg_coarse_amg": (C.c_int, [vp, C.POINTER(vp)]),
     "tb_bidomain_create": (C.c_int, [vp, C.POINTER(vp)]),
     "tb_bidomain_destroy": (C.c_int, [vp]),
     "tb_bidomain_set_matrices": (C.c_int, [vp, vp, vp, vp, vp, C.c_double, vp, C.c_double]),

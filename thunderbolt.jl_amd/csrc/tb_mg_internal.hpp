@@ -80,4 +80,9 @@ struct tb_mg {
     double ratio = 4.0;
     double *d_cinv = nullptr; // dense inverse of the coarsest operator
     double *d_scal = nullptr; // two scalars of the λmax estimate
+    // tb_mg_set_coarse_amg: level 0 is solved by one cycle of a smoothed-aggregation hierarchy (tb_amg.hip) instead of the dense inverse
+    bool coarse_amg = false;
+    double amg_theta = 0.25;
+    int amg_max_coarse = tb::MG_COARSEST_MAX, amg_max_levels = 16;
+    struct tb_amg *amg = nullptr;
 };

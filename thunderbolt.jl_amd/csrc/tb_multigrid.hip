@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "tb_amg_internal.hpp"
 #include "tb_internal.h"
 #include "tb_mg_internal.hpp"
 #include "tb_mg_planners.hpp"
@@ -218,7 +219,23 @@ static void free_plans(tb_mg *mg)
     }
     if (mg->d_cinv) (void)hipFree(mg->d_cinv);
     mg->d_cinv = nullptr;
+    if (mg->amg) (void)tb_amg_destroy(mg->amg);
+    mg->amg = nullptr;
     mg->planned = mg->ready = false;
+}
+
+// tb_mg_set_coarse_amg: the AMG hierarchy on the level-0 pattern, labelled by the components of its field
+static int create_coarse_amg(tb_mg *mg)
+{
+    tb_pattern *pat = mg->lv[0].pat;
+    const tb_mesh *m = pat->mesh;
+    std::vector<int8_t> comp;
+    if (m->ncomp > 1) {
+        comp.assign((size_t)m->ndofs, 0);
+        for (size_t q = 0; q < m->h_cell_dofs.size(); ++q) // local dof l of a cell carries component l mod ncomp, in any numbering
+            comp[(size_t)m->h_cell_dofs[q]] = (int8_t)((q % (size_t)m->ndpc) % (size_t)m->ncomp);
+    }
+    return tb_amg_create(pat, comp.empty() ? nullptr : comp.data(), mg->amg_theta, mg->amg_max_coarse, mg->amg_max_levels, &mg->amg);
 }
 
 static mgplan::LevelView view_of(const tb_pattern *p)
@@ -241,7 +258,7 @@ int build_plans(tb_mg *mg)
         else
             TB_REQUIRE(l == 0 || !mg->lv[l].p_transfer, "tb_mg_setup: level %d has a p-transfer below it but carries a first-order field", l);
     }
-    if (mg->lv[0].pat->n_rows > MG_COARSEST_MAX) {
+    if (!mg->coarse_amg && mg->lv[0].pat->n_rows > MG_COARSEST_MAX) {
         set_error("tb_mg_setup: the coarsest level has %lld dofs; its dense inverse takes at most %d - add a level%s", (long long)mg->lv[0].pat->n_rows, MG_COARSEST_MAX,
                   nl == 2 && mg->lv[1].p_transfer ? " (h-levels below the p-level: ChainedMGPrecon(PMGPrecon(), GMGPrecon(gh)))" : "");
         return TB_ERR_UNSUPPORTED;
@@ -290,7 +307,8 @@ int build_plans(tb_mg *mg)
         if (l < nl - 1) TB_HIP(hipMalloc((void **)&L.d_A, sizeof(double) * (size_t)std::max<int64_t>(L.nnz, 1)));
         TB_TRY(spmv_plans(L.pat));
     }
-    TB_HIP(hipMalloc((void **)&mg->d_cinv, sizeof(double) * (size_t)mg->lv[0].n * (size_t)mg->lv[0].n));
+    if (mg->coarse_amg) TB_TRY(create_coarse_amg(mg));
+    else TB_HIP(hipMalloc((void **)&mg->d_cinv, sizeof(double) * (size_t)mg->lv[0].n * (size_t)mg->lv[0].n));
     if (!mg->d_scal) TB_HIP(hipMalloc((void **)&mg->d_scal, 16 * sizeof(double)));
     mg->planned = true;
     return TB_OK;
@@ -353,6 +371,7 @@ static int cycle(tb_mg *mg, int l, const double *r, double *x)
     tb_device *dev = mg->dev;
     MgLevel &L = mg->lv[l];
     if (l == 0) {
+        if (mg->amg) return amg_apply_cb(mg->amg, r, x);
         hipLaunchKernelGGL(k_mg_dense_apply, dim3(blocks_of(L.n * 64, 256)), dim3(256), 0, dev->stream, (int)L.n, mg->d_cinv, r, x);
         return TB_OK;
     }
@@ -510,6 +529,30 @@ int tb_mg_set_prescribed(tb_mg *mg, const uint8_t *d_prescribed_fine)
     return TB_OK;
 }
 
+int tb_mg_set_coarse_amg(tb_mg *mg, double theta, int max_coarse, int max_levels)
+{
+    TB_REQUIRE(mg, "tb_mg_set_coarse_amg: NULL argument");
+    TB_REQUIRE(theta >= 0.0 && theta <= 1.0, "tb_mg_set_coarse_amg: theta must be in 0..1 (got %g)", theta);
+    TB_REQUIRE(max_coarse >= 1, "tb_mg_set_coarse_amg: max_coarse must be positive (got %d)", max_coarse);
+    TB_REQUIRE(max_levels >= 1 && max_levels <= 64, "tb_mg_set_coarse_amg: max_levels must be in 1..64 (got %d)", max_levels);
+    TB_NO_CAPTURE(mg->dev);
+    TB_HIP(hipSetDevice(mg->dev->id));
+    free_plans(mg);
+    mg->coarse_amg = true;
+    mg->amg_theta = theta;
+    mg->amg_max_coarse = max_coarse;
+    mg->amg_max_levels = max_levels;
+    return TB_OK;
+}
+
+int tb_mg_coarse_amg(tb_mg *mg, tb_amg **out)
+{
+    TB_REQUIRE(mg && out, "tb_mg_coarse_amg: NULL argument");
+    TB_REQUIRE(mg->ready, "tb_mg_coarse_amg: no numeric setup yet (tb_mg_setup)");
+    *out = mg->amg;
+    return TB_OK;
+}
+
 int tb_mg_setup(tb_mg *mg, const double *d_Anz_fine, int degree, double interval_ratio)
 {
     TB_REQUIRE(mg && d_Anz_fine, "tb_mg_setup: NULL argument");
@@ -542,7 +585,11 @@ int tb_mg_setup(tb_mg *mg, const double *d_Anz_fine, int degree, double interval
         TB_TRY(estimate_lambda_max(L.pat, L.A, L.dinv, L.w, L.d, L.x, L.r, L.r + L.n, mg->d_scal, &L.lmax));
     }
     MgLevel &C0 = mg->lv[0];
-    hipLaunchKernelGGL(k_mg_dense_inverse, dim3(1), dim3(1024), 0, dev->stream, (int)C0.n, C0.pat->d_rowptr, C0.pat->d_colidx, C0.A, mg->d_cinv);
+    if (mg->amg) { // the AMG below level 0: planned at its first setup, numeric phase only afterwards
+        const int rc = tb_amg_setup(mg->amg, C0.A, degree, interval_ratio);
+        if (rc) { free_plans(mg); return rc; }
+    } else
+        hipLaunchKernelGGL(k_mg_dense_inverse, dim3(1), dim3(1024), 0, dev->stream, (int)C0.n, C0.pat->d_rowptr, C0.pat->d_colidx, C0.A, mg->d_cinv);
     TB_HIP(hipGetLastError());
     mg->ready = true;
     return TB_OK;

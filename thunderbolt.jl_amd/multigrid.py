@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _lib as L
 from ._lib import check, lib
+from .amg import AlgebraicHierarchy, AMGPrecon
 from .api import DofHandler, Hexahedron, LagrangeCollection, _ptr, allocate_matrix
 from .meshgen import GridHierarchy
 
@@ -20,11 +21,12 @@ class GMGPrecon:
     polynomial and the ratio λmax/λmin of its interval.  `materialize(pattern, ch)` builds the device hierarchy for one matrix pattern; pcg_solve and
     the Newton solver do that themselves at their first solve."""
 
-    def __init__(self, gh, degree=2, interval_ratio=4.0, cycle="V", smoother="chebyshev"):
+    def __init__(self, gh, degree=2, interval_ratio=4.0, cycle="V", smoother="chebyshev", coarse=None):
         if not isinstance(gh, GridHierarchy):
             raise TypeError("GMGPrecon: pass a GridHierarchy")
         _check_cycle("GMGPrecon", cycle, smoother)
         self.gh, self.degree, self.interval_ratio = gh, int(degree), float(interval_ratio)
+        self.coarse = _check_coarse("GMGPrecon", coarse, self.degree, self.interval_ratio)   # AMGPrecon: one AMG cycle solves the coarsest grid
         self._materialized = {}
 
     def check(self, dh):
@@ -33,8 +35,20 @@ class GMGPrecon:
     def materialize(self, pattern, ch=None):
         key = (id(pattern), id(ch))
         if key not in self._materialized:
-            self._materialized[key] = (MultigridHierarchy(pattern, self.gh, self.degree, self.interval_ratio, ch), pattern, ch)   # (the key's objects stay alive)
+            self._materialized[key] = (MultigridHierarchy(pattern, self.gh, self.degree, self.interval_ratio, ch, coarse=self.coarse), pattern, ch)   # (the key's objects stay alive)
         return self._materialized[key][0]
+
+
+def _check_coarse(who, coarse, degree, interval_ratio):
+    """the coarse solver of a hierarchy: None (dense inverse) or an AMGPrecon of the hierarchy's degree and interval ratio (the cycle has one for all levels)"""
+    if coarse is None:
+        return None
+    if not isinstance(coarse, AMGPrecon):
+        raise TypeError("%s: coarse is None (dense inverse) or an AMGPrecon" % who)
+    if coarse.degree != degree or coarse.interval_ratio != interval_ratio:
+        raise ValueError("%s: the recipes disagree on degree or interval_ratio (%d, %g and %d, %g); the cycle has one for all levels"
+                         % (who, degree, interval_ratio, coarse.degree, coarse.interval_ratio))
+    return coarse
 
 
 def _check_cycle(who, cycle, smoother):
@@ -58,6 +72,7 @@ class PMGPrecon:
         self._materialized = {}
 
     gh = None      # no h-levels (ChainedMGPrecon sets the hierarchy of its GMGPrecon)
+    coarse = None  # dense inverse on the coarsest level (ChainedMGPrecon(PMGPrecon(), AMGPrecon()): one AMG cycle)
 
     def check(self, dh):
         check_supported(self.gh, dh, order=2, who=type(self).__name__)
@@ -65,7 +80,7 @@ class PMGPrecon:
     def materialize(self, pattern, ch=None):
         key = (id(pattern), id(ch))
         if key not in self._materialized:
-            self._materialized[key] = (MultigridHierarchy(pattern, self.gh, self.degree, self.interval_ratio, ch, p_level=True), pattern, ch)
+            self._materialized[key] = (MultigridHierarchy(pattern, self.gh, self.degree, self.interval_ratio, ch, p_level=True, coarse=self.coarse), pattern, ch)
         return self._materialized[key][0]
 
 
@@ -78,14 +93,22 @@ class ChainedMGPrecon(PMGPrecon):
             raise NotImplementedError("ChainedMGPrecon takes the two recipes it chains, not a grid hierarchy: ChainedMGPrecon(PMGPrecon(), GMGPrecon(gh)) "
                                       "(p-levels on top of the h-levels of gh)")
         pmg, gmg = args
+        if type(pmg) is PMGPrecon and isinstance(gmg, AMGPrecon):
+            # the reference's default pcoarse_solver (multigrid.jl:27): the first-order level is solved by one AMG cycle, no h-levels
+            self.pmg, self.gmg, self.gh = pmg, None, None
+            self.degree, self.interval_ratio = pmg.degree, pmg.interval_ratio
+            self.coarse = _check_coarse("ChainedMGPrecon", gmg, self.degree, self.interval_ratio)
+            self._materialized = {}
+            return
         if not (type(pmg) is PMGPrecon and isinstance(gmg, GMGPrecon)):
-            raise TypeError("ChainedMGPrecon(pmg, gmg): a PMGPrecon and a GMGPrecon, in this order")
+            raise TypeError("ChainedMGPrecon(pmg, gmg): a PMGPrecon and a GMGPrecon or an AMGPrecon, in this order")
         if pmg.degree != gmg.degree:
             raise ValueError("ChainedMGPrecon: the recipes disagree on degree (%d and %d); the cycle has one for all levels" % (pmg.degree, gmg.degree))
         if pmg.interval_ratio != gmg.interval_ratio:
             raise ValueError("ChainedMGPrecon: the recipes disagree on interval_ratio (%g and %g); the cycle has one for all levels" % (pmg.interval_ratio, gmg.interval_ratio))
         self.pmg, self.gmg, self.gh = pmg, gmg, gmg.gh
         self.degree, self.interval_ratio = pmg.degree, pmg.interval_ratio
+        self.coarse = gmg.coarse
         self._materialized = {}
 
 
@@ -112,7 +135,7 @@ class MultigridHierarchy:
     dofs).  p_level: the matrix's field is second order; the level below it is the first-order field on the same grid, the h-levels of `gh` (None: no
     h-levels) follow below that."""
 
-    def __init__(self, pattern, gh, degree=2, interval_ratio=4.0, ch=None, p_level=False):
+    def __init__(self, pattern, gh, degree=2, interval_ratio=4.0, ch=None, p_level=False, coarse=None):
         dh, device = pattern.dmesh.dh, pattern.dmesh.device
         check_supported(gh, dh, order=2 if p_level else 1, who="ChainedMGPrecon" if p_level and gh is not None else "PMGPrecon" if p_level else "GMGPrecon")
         self.device, self.gh, self.pattern, self.degree, self.interval_ratio = device, gh, pattern, int(degree), float(interval_ratio)
@@ -135,6 +158,9 @@ class MultigridHierarchy:
         self.ch = ch
         if ch is not None:
             check(lib().tb_mg_set_prescribed(self.h, ch.flags(device).ptr))
+        self.coarse = coarse
+        if coarse is not None:
+            check(lib().tb_mg_set_coarse_amg(self.h, coarse.theta, coarse.max_coarse, coarse.max_levels))
         self._A = None
 
     @property
@@ -150,6 +176,17 @@ class MultigridHierarchy:
     def apply(self, r, z):
         check(lib().tb_mg_apply(self.h, _ptr(r), _ptr(z)))
         return z
+
+    def coarse_hierarchy(self):
+        """the AMG hierarchy below level 0 (coarse=AMGPrecon(…), after one setup) as an AlgebraicHierarchy to inspect; this object keeps owning it"""
+        h = C.c_void_p()
+        check(lib().tb_mg_coarse_amg(self.h, C.byref(h)))
+        if not h:
+            return None
+        view = AlgebraicHierarchy.__new__(AlgebraicHierarchy)
+        view.device, view.pattern, view.degree, view.interval_ratio, view.h, view._A, view.owner = self.device, self.patterns[0], self.degree, self.interval_ratio, h, None, self
+        view.close = lambda: None
+        return view
 
     def level_matrix(self, level):
         """CSR values of the level's operator on self.sps[level], as a host array"""
@@ -225,8 +262,8 @@ class KrylovMGSolver:
     def __init__(self, krylov="cg", mg=None, maxiters=None, rtol=1e-8, atol=1e-14):
         if krylov != "cg":
             raise NotImplementedError("KrylovMGSolver(%r): the multigrid preconditions CG only (GMRES is out of scope)" % (krylov,))
-        if not isinstance(mg, (GMGPrecon, PMGPrecon, MultigridHierarchy)):
-            raise TypeError("KrylovMGSolver: mg must be a GMGPrecon, a PMGPrecon, a ChainedMGPrecon or a materialised MultigridHierarchy")
+        if not isinstance(mg, (GMGPrecon, PMGPrecon, MultigridHierarchy, AMGPrecon, AlgebraicHierarchy)):
+            raise TypeError("KrylovMGSolver: mg must be a GMGPrecon, a PMGPrecon, a ChainedMGPrecon, an AMGPrecon or a materialised hierarchy")
         self.mg, self.maxiters, self.rtol, self.atol = mg, maxiters, rtol, atol
 
     def solve(self, pattern, A, b, x, ch=None):
