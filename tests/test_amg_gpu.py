@@ -12,6 +12,7 @@ import scipy.sparse as sparse
 import amg_reference as ref
 import multigrid_reference as mref
 import pmultigrid_reference as pref
+from gmg_case import face_dofs, gmg_problem, heat_values
 
 pytestmark = pytest.mark.gpu
 
@@ -23,18 +24,6 @@ CASES = ["hex9", "hex17", "hex9_aniso", "tet", "elasticity"]
 def csr_of(sp, vals):
     n = len(sp.rowptr) - 1
     return sparse.csr_matrix((np.asarray(vals, dtype=np.float64), sp.colidx.astype(np.int32), sp.rowptr.astype(np.int64)), shape=(n, n))
-
-
-def face_dofs(tb, dh, axis=0, value=0.0):
-    return np.flatnonzero(np.abs(tb.dof_coordinates(dh)[:, axis] - value) < 1e-12)
-
-
-def heat_values(tb, device, dh, sp, D, dt=0.1):
-    """M − Δt·K on the host (K as the diffusion form leaves it: negative semidefinite) and the pattern"""
-    st = tb.PatchAssemblyStrategy(device)
-    K = tb.update_operator(tb.setup_operator(st, tb.BilinearDiffusionIntegrator(D), dh, sp), 0.0)
-    M = tb.update_operator(tb.setup_operator(st, tb.BilinearMassIntegrator(tb.ConstantCoefficient(1.0)), dh, sp), 0.0)
-    return M.A.to_host() - dt * K.A.to_host(), K.pattern
 
 
 class Case:
@@ -290,20 +279,6 @@ def test_p_level_over_amg(tb, device):
     Ad = mref.csr_to_dense(sp, dA.to_host())
     P, cpre = pref.dense_p_level(tb, dh, mg.dhs[0], flags)
     check_hierarchy_over_amg(tb, device, mg, dh, K.pattern, dA, ch, [mref.galerkin(P, Ad, cpre), Ad], [None, P], [cpre, flags])
-
-
-def gmg_problem(tb, device):
-    """the 8³-cell heat problem over a 4³-cell coarse grid (125 dofs: above max_coarse, below the dense inverse's limit) → (gh, dh, sp, pattern, dA, ch, b)"""
-    gh = tb.GridHierarchy(tb.generate_mesh(tb.Hexahedron, (4, 4, 4), (0, 0, 0), (1, 1, 1)), 1)
-    dh = tb.DofHandler(gh.grids[-1])
-    sp = tb.allocate_matrix(dh)
-    vals, pattern = heat_values(tb, device, dh, sp, tb.ConstantCoefficient(np.diag([9.0, 4.0, 4.0])))
-    ch = tb.ConstraintHandler(dh, face_dofs(tb, dh))
-    dA = device.to_device(vals)
-    tb.apply_zero(dA, None, ch, pattern=pattern)
-    b = np.random.default_rng(29).normal(size=dh.ndofs)
-    b[ch.prescribed_dofs] = 0.0
-    return gh, dh, sp, pattern, dA, ch, b
 
 
 def gmg_solution(tb, device, vals=None):

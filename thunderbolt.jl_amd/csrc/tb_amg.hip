@@ -1,8 +1,9 @@
 // tb_amg.hip — smoothed-aggregation algebraic multigrid (SmoothedAggregationCoarseSolver, the default pcoarse_solver of the reference's PMGPrecon:
 // src/solver/linear/multigrid.jl:27): a preconditioner that needs only the matrix.  Per level: strength of connection (device) → aggregates and
-// patterns (tb_amg_planners.cpp, host, flags only) → smoothed prolongator P = T − ω D⁻¹ A T, R = Pᵀ, A_c = R (A P) (device, on planned patterns) → the
-// Chebyshev–Jacobi V-cycle of tb_multigrid.hip with the dense inverse on the last level.  Level 0 is the caller's matrix on its tb_pattern (products by
-// launch_spmv); the levels below are bare CSRs owned here.
+// patterns (tb_amg_planners.cpp, host, flags only) → smoothed prolongator P = T − ω D⁻¹ A T, R = Pᵀ, A_c = R (A P) (device, on planned patterns) → a
+// V-cycle on the smoother, dense inverse, dense product and partial fold of tb_multigrid.hip (cheb_smooth, launch_dense_inverse, launch_dense_apply,
+// launch_fold_*: tb_mg_internal.hpp).  Level 0 is the caller's matrix on its tb_pattern (products by launch_spmv); the levels below are bare CSRs
+// owned here (k_amg_spmv).
 // Every sum has one recorded order and no kernel uses a floating-point atomic: two setups, and two applications, give the same bits.
 #include <hip/hip_runtime.h>
 
@@ -142,41 +143,8 @@ k_amg_spmv(int64_t n, const int64_t *__restrict__ rowptr, const int32_t *__restr
     if (sub == 0) { if (MODE == 2) y[i] += s; else y[i] = s; }
 }
 
-// the Chebyshev step of tb_multigrid.hip's smoother (k_mg_cheb), restated for the bare levels
-template <int MODE>
-__global__ void __launch_bounds__(256)
-k_amg_cheb(int64_t n, double c1, double c2, const double *__restrict__ dinv, const double *__restrict__ r, const double *__restrict__ w, double *__restrict__ d,
-           double *__restrict__ x)
-{
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        if (MODE == 0) {
-            const double di = c2 * dinv[i] * r[i];
-            d[i] = di; x[i] = di;
-        } else {
-            const double g = c2 * dinv[i] * (r[i] - w[i]);
-            const double di = MODE == 1 ? g : c1 * d[i] + g;
-            d[i] = di; x[i] += di;
-        }
-    }
-}
-
-// one workgroup: C = A⁻¹ of the last level (n ≤ 1024), dense, by the Gauss–Jordan elimination of the geometric multigrid
-__global__ void __launch_bounds__(1024)
-k_amg_dense_inverse(int n, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, const double *__restrict__ nz, double *__restrict__ C)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    for (int i = wv; i < n; i += nw)
-        for (int j = lane; j < n; j += 64) C[(size_t)i * n + j] = 0.0;
-    __syncthreads();
-    for (int i = wv; i < n; i += nw)
-        for (int64_t k = rowptr[i] + lane; k < rowptr[i + 1]; k += 64) C[(size_t)i * n + colidx[k]] = nz[k];
-    __syncthreads();
-    mg_gauss_jordan(n, C);
-}
-
 // ---- ordered reductions of the λmax estimate: a partial per workgroup (strided lane sums, wave butterflies, the waves in order), then one workgroup
-// folds the partials in a fixed tree.  The grid depends on n and the device only. ----
+// folds the partials in a fixed tree (launch_fold_sum, launch_fold_max).  The grid depends on n and the device only. ----
 constexpr int AMG_RED_BLOCKS = 256;
 template <bool MAX>
 __device__ __forceinline__ void amg_block_reduce(double v, double *__restrict__ partial)
@@ -187,18 +155,6 @@ __device__ __forceinline__ void amg_block_reduce(double v, double *__restrict__ 
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) partial[blockIdx.x] = MAX ? fmax(fmax(sm[0], sm[1]), fmax(sm[2], sm[3])) : ((sm[0] + sm[1]) + (sm[2] + sm[3]));
-}
-template <bool MAX>
-__global__ void __launch_bounds__(256) k_amg_fold(int nb, const double *__restrict__ partial, double *__restrict__ out)
-{
-    __shared__ double sm[256];
-    sm[threadIdx.x] = (int)threadIdx.x < nb ? partial[threadIdx.x] : 0.0; // (the maxima folded here are of absolute values)
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sm[threadIdx.x] = MAX ? fmax(sm[threadIdx.x], sm[threadIdx.x + o]) : sm[threadIdx.x] + sm[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = sm[0];
 }
 // Gershgorin row sums |d_i| Σ_j |a_ij| into g, their maximum into the partials
 __global__ void __launch_bounds__(256)
@@ -272,7 +228,6 @@ k_amg_lanczos_b(int64_t n, double alpha, const double *__restrict__ v, double *_
     amg_block_reduce<false>(a, partial);
 }
 
-static inline unsigned blocks_of(int64_t n, int bs) { return (unsigned)std::max<int64_t>(1, (n + bs - 1) / bs); }
 static inline unsigned red_blocks(int64_t n) { return (unsigned)std::min<int64_t>(AMG_RED_BLOCKS, std::max<int64_t>(1, (n + 255) / 256)); }
 
 template <class T>
@@ -284,7 +239,8 @@ static void free_dev(T *&p)
 
 static void free_level(AmgLevel &L)
 {
-    free_dev(L.d_rowptr); free_dev(L.d_colidx); free_dev(L.d_A); free_dev(L.d_comp); free_dev(L.d_diag); free_dev(L.d_vec); free_dev(L.d_strength);
+    L.release();
+    free_dev(L.d_rowptr); free_dev(L.d_colidx); free_dev(L.d_A); free_dev(L.d_comp); free_dev(L.d_diag); free_dev(L.d_strength);
     free_dev(L.d_agg); free_dev(L.d_tval); free_dev(L.d_pptr); free_dev(L.d_pcol); free_dev(L.d_prow); free_dev(L.d_P); free_dev(L.d_rptr); free_dev(L.d_rcol);
     free_dev(L.d_rperm); free_dev(L.d_R); free_dev(L.d_apptr); free_dev(L.d_apcol); free_dev(L.d_aprow); free_dev(L.d_AP); free_dev(L.d_crow);
 }
@@ -309,7 +265,7 @@ static int product(tb_amg *amg, int l, const double *x, double *y)
 template <bool MAX>
 static int reduce_read(tb_amg *amg, unsigned nb, double *host)
 {
-    hipLaunchKernelGGL(k_amg_fold<MAX>, dim3(1), dim3(256), 0, amg->dev->stream, (int)nb, amg->d_red, amg->d_red + AMG_RED_BLOCKS);
+    (MAX ? launch_fold_max : launch_fold_sum)(amg->dev, (int)nb, amg->d_red, amg->d_red + AMG_RED_BLOCKS);
     return read_back(amg->dev, host, amg->d_red + AMG_RED_BLOCKS, 1);
 }
 
@@ -360,13 +316,6 @@ static int level_lambda_max(tb_amg *amg, int l, double *lmax_out)
     return TB_OK;
 }
 
-static int alloc_vectors(AmgLevel &L)
-{
-    TB_HIP(hipMalloc((void **)&L.d_vec, sizeof(double) * 6 * (size_t)std::max<int64_t>(L.n, 1)));
-    L.dinv = L.d_vec; L.d = L.dinv + L.n; L.w = L.d + L.n; L.x = L.w + L.n; L.r = L.x + L.n;
-    return TB_OK;
-}
-
 // symbolic phase of level l (its matrix is in place): strength on the device, aggregates and patterns on the host, uploads, and the storage of level
 // l + 1.  *coarsened = false: aggregation does not reduce n, the level stays the last one.
 static int plan_level_below(tb_amg *amg, int l, bool *coarsened)
@@ -411,7 +360,7 @@ static int plan_level_below(tb_amg *amg, int l, bool *coarsened)
     TB_TRY(upload_all(dev, N.h_rowptr, &N.d_rowptr, N.h_colidx, &N.d_colidx, N.h_comp, &N.d_comp, p.c_diag, &N.d_diag));
     TB_HIP(hipMalloc((void **)&N.d_A, sizeof(double) * (size_t)std::max<int64_t>(N.nnz, 1)));
     N.rowptr = N.d_rowptr; N.colidx = N.d_colidx; N.A = N.d_A;
-    TB_TRY(alloc_vectors(N));
+    TB_TRY(N.alloc(N.n));
     // the host keeps what the inspectors return (aggregates, P's pattern, strength); the product patterns live on the device only
     std::vector<int32_t>().swap(p.ap_col); std::vector<int32_t>().swap(p.ap_row); std::vector<int64_t>().swap(p.ap_ptr);
     std::vector<int32_t>().swap(p.c_row); std::vector<int64_t>().swap(p.c_diag); std::vector<int64_t>().swap(p.r_perm);
@@ -435,28 +384,6 @@ static void launch_level_numeric(tb_amg *amg, int l)
                        (const int32_t *)L.d_rcol, (const double *)L.d_R, (const int64_t *)L.d_apptr, (const int32_t *)L.d_apcol, (const double *)L.d_AP, N.d_A);
 }
 
-static int smooth(tb_amg *amg, int l, const double *r, double *x, bool from_zero)
-{
-    AmgLevel &L = amg->lv[(size_t)l];
-    tb_device *dev = amg->dev;
-    const unsigned g = grid_for(dev, L.n, 256);
-    const double lmax = L.lmax, lmin = lmax / amg->ratio;
-    const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sigma1 = theta / delta;
-    double rho = 1.0 / sigma1;
-    if (from_zero) hipLaunchKernelGGL(k_amg_cheb<0>, dim3(g), dim3(256), 0, dev->stream, L.n, 0.0, 1.0 / theta, (const double *)L.dinv, r, (const double *)nullptr, L.d, x);
-    else {
-        TB_TRY(product(amg, l, x, L.w));
-        hipLaunchKernelGGL(k_amg_cheb<1>, dim3(g), dim3(256), 0, dev->stream, L.n, 0.0, 1.0 / theta, (const double *)L.dinv, r, (const double *)L.w, L.d, x);
-    }
-    for (int k = 1; k < amg->degree; ++k) {
-        TB_TRY(product(amg, l, x, L.w));
-        const double rho_new = 1.0 / (2.0 * sigma1 - rho);
-        hipLaunchKernelGGL(k_amg_cheb<2>, dim3(g), dim3(256), 0, dev->stream, L.n, rho_new * rho, 2.0 * rho_new / delta, (const double *)L.dinv, r, (const double *)L.w, L.d, x);
-        rho = rho_new;
-    }
-    return TB_OK;
-}
-
 // x = M_l⁻¹ r: V(degree, degree) from x = 0; enqueues only
 static int cycle(tb_amg *amg, int l, const double *r, double *x)
 {
@@ -467,15 +394,15 @@ static int cycle(tb_amg *amg, int l, const double *r, double *x)
         return TB_OK;
     }
     AmgLevel &N = amg->lv[(size_t)l + 1];
-    TB_TRY(smooth(amg, l, r, x, true));
-    TB_TRY(product(amg, l, x, L.w));
+    auto A = [&](const double *u, double *y) { return product(amg, l, u, y); };
+    TB_TRY(cheb_smooth(dev, L.n, L, L.lmax, amg->ratio, amg->degree, r, x, true, A));
+    TB_TRY(A(x, L.w));
     hipLaunchKernelGGL(k_amg_spmv<1>, dim3(blocks_of(N.n * 8, 256)), dim3(256), 0, dev->stream, N.n, (const int64_t *)L.d_rptr, (const int32_t *)L.d_rcol,
                        (const double *)L.d_R, r, (const double *)L.w, N.r);
     TB_TRY(cycle(amg, l + 1, N.r, N.x));
     hipLaunchKernelGGL(k_amg_spmv<2>, dim3(blocks_of(L.n * 8, 256)), dim3(256), 0, dev->stream, L.n, (const int64_t *)L.d_pptr, (const int32_t *)L.d_pcol,
                        (const double *)L.d_P, (const double *)N.x, (const double *)nullptr, x);
-    TB_TRY(smooth(amg, l, r, x, false));
-    return TB_OK;
+    return cheb_smooth(dev, L.n, L, L.lmax, amg->ratio, amg->degree, r, x, false, A);
 }
 
 int amg_apply_cb(void *ctx, const double *r, double *z)
@@ -510,7 +437,7 @@ static int setup_levels(tb_amg *amg)
                 return TB_ERR_UNSUPPORTED;
             }
             if (!amg->d_cinv) TB_HIP(hipMalloc((void **)&amg->d_cinv, sizeof(double) * (size_t)L.n * (size_t)L.n));
-            hipLaunchKernelGGL(k_amg_dense_inverse, dim3(1), dim3(1024), 0, dev->stream, (int)L.n, L.rowptr, L.colidx, L.A, amg->d_cinv);
+            launch_dense_inverse(dev, (int)L.n, L.rowptr, L.colidx, L.A, amg->d_cinv);
             break;
         }
         hipLaunchKernelGGL(k_amg_dinv, dim3(blocks_of(L.n, 256)), dim3(256), 0, dev->stream, L.n, (const int64_t *)L.d_diag, L.A, L.dinv);
@@ -534,9 +461,7 @@ int tb_amg_create(tb_pattern *pat, const int8_t *comp_host, double theta, int ma
 {
     TB_REQUIRE(pat && out, "tb_amg_create: NULL argument");
     *out = nullptr;
-    TB_REQUIRE(theta >= 0.0 && theta <= 1.0, "tb_amg_create: theta must be in 0..1 (got %g)", theta);
-    TB_REQUIRE(max_coarse >= 1, "tb_amg_create: max_coarse must be positive (got %d)", max_coarse);
-    TB_REQUIRE(max_levels >= 1 && max_levels <= 64, "tb_amg_create: max_levels must be in 1..64 (got %d)", max_levels);
+    TB_TRY(check_amg_args("tb_amg_create", theta, max_coarse, max_levels));
     std::string err;
     if (amgplan::check_pattern(pat->n_rows, pat->h_rowptr.data(), pat->h_colidx.data(), err)) {
         set_error("tb_amg_create: %s (the aggregation needs sorted columns and a structurally symmetric pattern)", err.c_str());
@@ -575,8 +500,7 @@ int tb_amg_replan(tb_amg *amg)
 int tb_amg_setup(tb_amg *amg, const double *d_Anz, int degree, double interval_ratio)
 {
     TB_REQUIRE(amg && d_Anz, "tb_amg_setup: NULL argument");
-    TB_REQUIRE(degree >= 1 && degree <= 64, "tb_amg_setup: smoother degree must be in 1..64 (got %d)", degree);
-    TB_REQUIRE(interval_ratio > 1.0 && std::isfinite(interval_ratio), "tb_amg_setup: interval_ratio must be a finite number above 1 (got %g)", interval_ratio);
+    TB_TRY(check_smoother_args("tb_amg_setup", degree, interval_ratio));
     tb_device *dev = amg->dev;
     TB_NO_CAPTURE(dev); // plans, reads strength flags and λmax back
     TB_HIP(hipSetDevice(dev->id));
@@ -596,7 +520,7 @@ int tb_amg_setup(tb_amg *amg, const double *d_Anz, int degree, double interval_r
         std::vector<int64_t> diag;
         amgplan::diagonal_positions(F.n, pat->h_rowptr.data(), pat->h_colidx.data(), diag);
         int rc = upload_all(dev, F.h_comp, &F.d_comp, diag, &F.d_diag);
-        if (!rc) rc = alloc_vectors(F);
+        if (!rc) rc = F.alloc(F.n);
         if (rc) { free_plan(amg); return rc; }
     }
     amg->lv[0].A = d_Anz;

@@ -6,10 +6,11 @@
 
 #include "tb_amg_planners.hpp"
 #include "tb_internal.h"
+#include "tb_mg_internal.hpp"
 
 namespace tb {
 
-struct AmgLevel {
+struct AmgLevel : MgVectors {
     int64_t n = 0, nnz = 0, nc = 0;      // dofs, non-zeros, aggregates (0 on the last level)
     // the level's operator: level 0 reads the caller's pattern and array, the levels below own theirs
     const int64_t *rowptr = nullptr;
@@ -23,8 +24,6 @@ struct AmgLevel {
     std::vector<int8_t> h_comp;          // component labels (empty: one component)
     int8_t *d_comp = nullptr;
     int64_t *d_diag = nullptr;           // position of every row's diagonal
-    double *d_vec = nullptr;             // dinv | d | w | x | r | one more (the Lanczos scratch of setup borrows d, w, x, r and the sixth)
-    double *dinv = nullptr, *d = nullptr, *w = nullptr, *x = nullptr, *r = nullptr;
     double lmax = 0.0;
     uint8_t *d_strength = nullptr;       // (lives during planning only)
     std::vector<uint8_t> h_strength;
@@ -44,7 +43,7 @@ struct tb_amg {
     tb_device *dev = nullptr;
     tb_pattern *pat = nullptr;
     double theta = 0.25;
-    int max_coarse = 1024, max_levels = 16;
+    int max_coarse = tb::MG_COARSEST_MAX, max_levels = 16;
     std::vector<int8_t> comp;
     std::vector<tb::AmgLevel> lv;        // lv[0]: the caller's matrix
     bool planned = false, ready = false;

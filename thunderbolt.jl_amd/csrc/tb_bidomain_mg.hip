@@ -3,7 +3,7 @@
 //   hierarchy   levels 0 … L−1 of the tb_mg (finest: the block system's pattern); ground flags g_l — a coarse node is grounded iff the fine node it
 //               coincides with is; block transfer 𝒫 = diag(P, G_f P G_c) with P the scalar nodal transfer and G the 0/1 diagonal of the free nodes: φₘ
 //               interpolates everywhere, φₑ neither into a grounded fine node nor from a grounded coarse node; 𝒜_c = 𝒫ᵀ𝒜_f𝒫, the eliminated φₑφₑ
-//               diagonal entries set to the mean |diagonal| of the level's free φₑφₑ entries (what k_mg_fill_diag does on a scalar level)
+//               diagonal entries set to the mean |diagonal| of the level's free φₑφₑ entries (k_mg_fill_diag, as on a scalar level)
 //   storage     the fine level is the block system's own (three planes, one a₁₂ for both off-diagonal blocks, ground flags in flight).  Pᵀ A₁₂ G_f P G_c
 //               is NOT a symmetric n × n matrix once a grounded fine node is no coarse node, so coarse levels keep full 2 × 2 blocks per non-zero
 //               (a₁₁, a₁₂, a₂₁, a₂₂) with the elimination baked in: k_bd_apply<·, true>.  Every level also keeps the four planes in CSR order: the
@@ -63,8 +63,6 @@ struct tb_bidomain_mg {
 
 namespace tb {
 
-static inline unsigned blocks_of(int64_t n, int bs) { return (unsigned)std::max<int64_t>(1, (n + bs - 1) / bs); }
-
 // g_c[I] = g_f[i] for the fine dof i that coincides with the coarse dof I: the one row of P with a single entry of weight 1 in column I
 __global__ void __launch_bounds__(256)
 k_bdmg_coarse_ground(int64_t nf, const int64_t *__restrict__ pptr, const int32_t *__restrict__ pcol, const uint8_t *__restrict__ pexp, const uint8_t *__restrict__ gf,
@@ -77,7 +75,7 @@ k_bdmg_coarse_ground(int64_t nf, const int64_t *__restrict__ pptr, const int32_t
 }
 
 // the fine level's sliced planes → CSR planes with the elimination baked in; the φₑφₑ diagonal of a grounded node stays 0 (the Galerkin product reads
-// G_f A₂₂ G_f) until k_bdmg_fill_diag
+// G_f A₂₂ G_f) until k_bdmg_set_ground_diag
 __global__ void __launch_bounds__(256)
 k_bdmg_csr_fine(int64_t n, const int64_t *__restrict__ base, int64_t entries, const uint32_t *__restrict__ col, const double *__restrict__ val,
                 const uint8_t *__restrict__ ground, const int64_t *__restrict__ rowptr, int64_t nnz, double *__restrict__ csr)
@@ -113,34 +111,8 @@ k_bdmg_mask_csr(int64_t n, const int64_t *__restrict__ rowptr, const int32_t *__
     }
 }
 
-// one workgroup, coarse levels (at most an eighth of the fine rows): the φₑφₑ diagonal of every grounded node becomes the mean |diagonal| of the free
-// nodes (fixed order: strided lane sums, LDS tree — the sum of k_mg_fill_diag)
-__global__ void __launch_bounds__(1024)
-k_bdmg_fill_diag(int64_t n, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, const uint8_t *__restrict__ ground, double *__restrict__ a22)
-{
-    __shared__ double ssum[1024];
-    __shared__ double scnt[1024];
-    double s = 0.0, c = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += 1024) {
-        if (ground[i]) continue;
-        for (int64_t k = rowptr[i]; k < rowptr[i + 1]; ++k)
-            if (colidx[k] == i) { s += fabs(a22[k]); c += 1.0; }
-    }
-    ssum[threadIdx.x] = s; scnt[threadIdx.x] = c;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { ssum[threadIdx.x] += ssum[threadIdx.x + o]; scnt[threadIdx.x] += scnt[threadIdx.x + o]; }
-        __syncthreads();
-    }
-    const double fill = scnt[0] > 0.0 ? ssum[0] / scnt[0] : 1.0;
-    for (int64_t i = threadIdx.x; i < n; i += 1024) {
-        if (!ground[i]) continue;
-        for (int64_t k = rowptr[i]; k < rowptr[i + 1]; ++k)
-            if (colidx[k] == i) a22[k] = fill;
-    }
-}
-
-// the fine level, whose fill is known (ground_diag): every grounded row finds its own diagonal
+// the fine level, whose fill is known (ground_diag): every grounded row finds its own diagonal (the scalar hierarchy holds no diagonal positions for its
+// finest level; the coarse levels go through launch_fill_diag with the positions of the Galerkin plan)
 __global__ void __launch_bounds__(256)
 k_bdmg_set_ground_diag(int64_t n, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, const uint8_t *__restrict__ ground, double fill, double *__restrict__ a22)
 {
@@ -284,7 +256,7 @@ k_bdmg_dense_inverse(int n, const int64_t *__restrict__ rowptr, const int32_t *_
 
 // ---- λmax(B⁻¹𝒜): Lanczos in the B inner product with B⁻¹ alone — v_k B-orthonormal, u_k = B v_k carried beside it
 // The three sums of a step are ORDERED at every size: a workgroup leaves its partial (xor tree in the wave, the four wave sums left to right) in its own
-// slot of a buffer, and one workgroup folds the buffer in a fixed order (k_bdmg_fold) — no atomic, so two set-ups give the same λmax and the same cycle.
+// slot of a buffer, and one workgroup folds the buffer in a fixed order (launch_fold_sum) — no atomic, so two set-ups give the same λmax and the same cycle.
 __device__ __forceinline__ void block_partial(double v, double *__restrict__ part)
 {
 #pragma unroll
@@ -293,20 +265,6 @@ __device__ __forceinline__ void block_partial(double v, double *__restrict__ par
     if ((threadIdx.x & 63) == 0) smp[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) part[blockIdx.x] = ((smp[0] + smp[1]) + smp[2]) + smp[3];
-}
-// one workgroup: *out = Σ part[0 … nb): strided lane sums, then an LDS tree
-__global__ void __launch_bounds__(256) k_bdmg_fold(int nb, const double *__restrict__ part, double *__restrict__ out)
-{
-    __shared__ double sf[256];
-    double v = 0.0;
-    for (int k = threadIdx.x; k < nb; k += 256) v += part[k];
-    sf[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sf[threadIdx.x] += sf[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = sf[0];
 }
 // part[workgroup] = Σ a·b over its node pairs (α = vᵀ𝒜v of a step)
 __global__ void __launch_bounds__(256) k_bdmg_dot_partial(int64_t n, const double2 *__restrict__ a, const double2 *__restrict__ b, double *__restrict__ part)
@@ -440,38 +398,32 @@ static void level_product(tb_bidomain_mg *h, int l, const double *x, double *y, 
                            L.d_val, (const uint8_t *)nullptr, 0.0, (const double2 *)x, (double2 *)y, xy, st);
 }
 
-// `degree` Chebyshev steps on B⁻¹𝒜_l for 𝒜_l x = r (Saad, Iterative Methods, Alg. 12.1; the recurrences of the scalar cycle's smooth()), from zero or
-// from *cur.  Fused: a step reads *cur and writes *other, then the two swap; split: product into w, vector kernel in place.
+// `degree` Chebyshev steps on B⁻¹𝒜_l for 𝒜_l x = r (the ChebSchedule of the scalar cycle's cheb_smooth), from zero or from *cur.  Fused: a step reads *cur and writes *other, then the two swap; split: product into w, vector kernel in place.
 static void smooth(tb_bidomain_mg *h, int l, const double *r, double *&cur, double *&other, bool from_zero)
 {
     BdMgLevel &L = h->lv[l];
     tb_device *dev = h->dev;
     const unsigned g = grid_for(dev, L.n, 256);
-    const double lmax = L.lmax, lmin = lmax / h->ratio;
-    const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sigma1 = theta / delta;
-    double rho = 1.0 / sigma1;
-    auto step = [&](bool first, double c1, double c2) {
+    ChebSchedule sched(L.lmax, h->ratio);
+    auto step = [&](bool first, ChebSchedule::Step c) {
         if (h->split) {
             level_product<false, 0>(h, l, cur, L.w, nullptr, BdStep());
-            if (first) hipLaunchKernelGGL(k_bdmg_cheb<1>, dim3(g), dim3(256), 0, dev->stream, L.n, c1, c2, L.d_binv, (const double2 *)r, (const double2 *)L.w, (double2 *)L.d, (double2 *)cur);
-            else hipLaunchKernelGGL(k_bdmg_cheb<2>, dim3(g), dim3(256), 0, dev->stream, L.n, c1, c2, L.d_binv, (const double2 *)r, (const double2 *)L.w, (double2 *)L.d, (double2 *)cur);
+            if (first) hipLaunchKernelGGL(k_bdmg_cheb<1>, dim3(g), dim3(256), 0, dev->stream, L.n, c.c1, c.c2, L.d_binv, (const double2 *)r, (const double2 *)L.w, (double2 *)L.d, (double2 *)cur);
+            else hipLaunchKernelGGL(k_bdmg_cheb<2>, dim3(g), dim3(256), 0, dev->stream, L.n, c.c1, c.c2, L.d_binv, (const double2 *)r, (const double2 *)L.w, (double2 *)L.d, (double2 *)cur);
             return;
         }
         BdStep st;
-        st.c1 = c1; st.c2 = c2; st.binv = L.d_binv; st.r = (const double2 *)r; st.d = (double2 *)L.d;
+        st.c1 = c.c1; st.c2 = c.c2; st.binv = L.d_binv; st.r = (const double2 *)r; st.d = (double2 *)L.d;
         if (first) level_product<false, 1>(h, l, cur, other, nullptr, st);
         else level_product<false, 2>(h, l, cur, other, nullptr, st);
         std::swap(cur, other);
     };
     if (from_zero)
-        hipLaunchKernelGGL(k_bdmg_cheb<0>, dim3(g), dim3(256), 0, dev->stream, L.n, 0.0, 1.0 / theta, L.d_binv, (const double2 *)r, (const double2 *)nullptr, (double2 *)L.d, (double2 *)cur);
+        hipLaunchKernelGGL(k_bdmg_cheb<0>, dim3(g), dim3(256), 0, dev->stream, L.n, sched.first().c1, sched.first().c2, L.d_binv, (const double2 *)r, (const double2 *)nullptr, (double2 *)L.d,
+                           (double2 *)cur);
     else
-        step(true, 0.0, 1.0 / theta);
-    for (int k = 1; k < h->degree; ++k) {
-        const double rho_new = 1.0 / (2.0 * sigma1 - rho);
-        step(false, rho_new * rho, 2.0 * rho_new / delta);
-        rho = rho_new;
-    }
+        step(true, sched.first());
+    for (int k = 1; k < h->degree; ++k) step(false, sched.next());
 }
 
 // x = ℳ_l⁻¹ r: V(degree, degree) from x = 0; enqueues only.  The fused smoother swaps its two buffers 2·degree − 1 times on a level, so it starts in the
@@ -508,7 +460,7 @@ static int lambda_max(tb_bidomain_mg *h, int l, double *out)
     const unsigned g = grid_for(dev, L.n, 256);
     double *v = L.d, *s = L.w, *t = L.xt, *u = L.x, *up = L.r, *S = h->d_scal, *part = h->d_part;
     double al[KL], be[KL + 1], hh[1];
-    auto fold = [&](double *out) { hipLaunchKernelGGL(k_bdmg_fold, dim3(1), dim3(256), 0, dev->stream, (int)g, (const double *)part, out); };
+    auto fold = [&](double *out) { launch_fold_sum(dev, (int)g, part, out); };
     hipLaunchKernelGGL(k_bdmg_lanczos_start, dim3(g), dim3(256), 0, dev->stream, L.n, L.d_binv, L.ground, (double2 *)s, (double2 *)t, part);
     fold(S);
     TB_TRY(read_back(dev, hh, S, 1));
@@ -685,8 +637,7 @@ int tb_bidomain_mg_destroy(tb_bidomain_mg *h)
 int tb_bidomain_mg_setup(tb_bidomain_mg *h, int degree, double interval_ratio)
 {
     TB_REQUIRE(h, "tb_bidomain_mg_setup: NULL argument");
-    TB_REQUIRE(degree >= 1 && degree <= 64, "tb_bidomain_mg_setup: smoother degree must be in 1..64 (got %d)", degree);
-    TB_REQUIRE(interval_ratio > 1.0 && std::isfinite(interval_ratio), "tb_bidomain_mg_setup: interval_ratio must be a finite number above 1 (got %g)", interval_ratio);
+    TB_TRY(check_smoother_args("tb_bidomain_mg_setup", degree, interval_ratio));
     tb_bidomain *bd = h->bd;
     tb_device *dev = h->dev;
     TB_NO_CAPTURE(dev); // reads λmax back
@@ -713,7 +664,7 @@ int tb_bidomain_mg_setup(tb_bidomain_mg *h, int degree, double interval_ratio)
         if (l == nl - 1)
             hipLaunchKernelGGL(k_bdmg_set_ground_diag, dim3(gn), dim3(256), 0, dev->stream, L.n, L.pat->d_rowptr, L.pat->d_colidx, L.ground, bd->ground_diag, L.d_csr + 3 * L.nnz);
         else
-            hipLaunchKernelGGL(k_bdmg_fill_diag, dim3(1), dim3(1024), 0, dev->stream, L.n, L.pat->d_rowptr, L.pat->d_colidx, L.ground, L.d_csr + 3 * L.nnz);
+            launch_fill_diag(dev, L.n, h->mg->lv[l + 1].d_cdiag, L.ground, L.d_csr + 3 * L.nnz);
         if (l == 0) break;
         if (l == nl - 1) hipLaunchKernelGGL(k_bdmg_binv_fine, dim3(gn), dim3(256), 0, dev->stream, L.n, bd->d_binv, L.ground, L.d_binv);
         else

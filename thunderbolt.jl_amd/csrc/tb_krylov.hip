@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "tb_internal.h"
+#include "tb_mg_internal.hpp"
 #include "tb_reduce.hpp"
 
 namespace tb {
@@ -481,24 +482,6 @@ k_gershgorin(int64_t n, const int64_t *__restrict__ rowptr, const double *__rest
     for (int64_t k = rowptr[r]; k < rowptr[r + 1]; ++k) s += fabs(nz[k]);
     out[r] = s * fabs(dinv[r]);
 }
-// d = c1·d + c2·D⁻¹(r − w);  z += d        (w = A z; first step: w = NULL, d = c2·D⁻¹ r, z = d)
-__global__ void __launch_bounds__(256)
-k_cheb_step(int64_t n, double c1, double c2, const double *__restrict__ dinv, const double *__restrict__ r, const double *__restrict__ w, double *__restrict__ d,
-            double *__restrict__ z)
-{
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        if (w) {
-            const double di = c1 * d[i] + c2 * dinv[i] * (r[i] - w[i]);
-            d[i] = di;
-            z[i] += di;
-        } else {
-            const double di = c2 * dinv[i] * r[i];
-            d[i] = di;
-            z[i] = di;
-        }
-    }
-}
 // Lanczos helpers: sq = √D⁻¹, v = a positive start vector (the Gershgorin row sums), v₋₁ = 0
 __global__ void __launch_bounds__(256)
 k_lanczos_init(int64_t n, const double *__restrict__ dinv, const double *__restrict__ start, double *__restrict__ sq, double *__restrict__ v, double *__restrict__ vp)
@@ -696,7 +679,6 @@ int launch_pcg_chebyshev(tb_pattern *pat, const double *A, const double *b, doub
     if (!r) return TB_ERR_HIP;
     pat->cg_dinv_of = nullptr; // the workspace no longer holds launch_cg's D⁻¹
     double *z = r + n, *p = z + n, *Ap = p + n, *dinv = Ap + n, *d = dinv + n, *w = d + n, *S = w + n; // S: rz | rz_new | pAp | rr | flag | power sums
-    const unsigned g = grid_for(dev, n, 256);
     int rc = launch_extract_inverse_diagonal(pat, A, dinv);
     if (rc) return rc;
     double lmax = 0.0;
@@ -704,19 +686,11 @@ int launch_pcg_chebyshev(tb_pattern *pat, const double *A, const double *b, doub
     if (rc) return rc;
     static const double ratio_env = tune_env("TB_CHEB_RATIO") ? atof(tune_env("TB_CHEB_RATIO")) : 0.0;
     const int m = degree < 1 ? 1 : degree;
-    const double lmin = lmax / (ratio_env > 1.0 ? ratio_env : std::max(4.0, 1.8 * m * m));
-    const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sigma1 = theta / delta;
-    auto precondition = [&]() -> int { // z = p_m(D⁻¹A) D⁻¹ r  (Saad, Iterative Methods, Alg. 12.1, started from zero)
-        double rho = 1.0 / sigma1;
-        hipLaunchKernelGGL(k_cheb_step, dim3(g), dim3(256), 0, dev->stream, n, 0.0, 1.0 / theta, dinv, r, (const double *)nullptr, d, z);
-        for (int k = 1; k < m; ++k) {
-            int rc2 = launch_spmv(pat, A, z, 1.0, 0.0, w);
-            if (rc2) return rc2;
-            const double rho_new = 1.0 / (2.0 * sigma1 - rho);
-            hipLaunchKernelGGL(k_cheb_step, dim3(g), dim3(256), 0, dev->stream, n, rho_new * rho, 2.0 * rho_new / delta, dinv, r, w, d, z);
-            rho = rho_new;
-        }
-        return TB_OK;
+    const double ratio = ratio_env > 1.0 ? ratio_env : std::max(4.0, 1.8 * m * m);
+    MgVectors v; // of the smoother: D⁻¹ and its two scratch vectors
+    v.dinv = dinv; v.d = d; v.w = w;
+    auto precondition = [&]() -> int { // z = p_m(D⁻¹A) D⁻¹ r: the multigrid smoother started from zero
+        return cheb_smooth(dev, n, v, lmax, ratio, m, r, z, true, [&](const double *x, double *y) { return launch_spmv(pat, A, x, 1.0, 0.0, y); });
     };
     return pcg_loop(pat, A, b, x, rtol, atol, maxiter, r, z, p, Ap, S, precondition, "Chebyshev preconditioner", iters, resnorm);
 }

@@ -1,9 +1,13 @@
-// tb_mg_internal.hpp — what tb_multigrid.hip shares with the units that build on its hierarchy (tb_bidomain_mg.hip: the block V-cycle of the bidomain
-// system reuses the scalar hierarchy's transfers and its unflagged per-dof Galerkin term lists): the level record, the hierarchy object, the symbolic
-// phase and the launchers of the kernels that work on a plan.  Nothing here changes what tb_mg_* computes.
+// tb_mg_internal.hpp — what tb_multigrid.hip shares with the units of the multigrid family.  tb_bidomain_mg.hip (the block V-cycle of the bidomain system)
+// reuses the scalar hierarchy's transfers and its unflagged per-dof Galerkin term lists: the level record, the hierarchy object, the symbolic phase
+// and the launchers of the kernels that work on a plan.  tb_amg.hip, tb_bidomain_mg.hip and the Chebyshev preconditioner of tb_krylov.hip share the
+// pieces that exist once: the Chebyshev schedule and the scalar smoother around k_mg_cheb, the level's vector block, the dense inverse, the diagonal
+// fill, the fold of per-workgroup partials and the argument checks.  The kernels live in tb_multigrid.hip behind the enqueue-only launchers below.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <vector>
 
@@ -13,13 +17,29 @@ namespace tb {
 
 constexpr int MG_COARSEST_MAX = 1024; // dofs of the coarsest level: its inverse is dense
 
-struct MgLevel {
+// the vectors of a scalar level in one allocation: dinv | d | w | x | r | a sixth (the λmax estimates of setup borrow d, w, x, r and the sixth: none
+// of them holds anything between applications)
+struct MgVectors {
+    double *d_vec = nullptr;
+    double *dinv = nullptr, *d = nullptr, *w = nullptr, *x = nullptr, *r = nullptr;
+    int alloc(int64_t n)
+    {
+        TB_HIP(hipMalloc((void **)&d_vec, sizeof(double) * 6 * (size_t)std::max<int64_t>(n, 1)));
+        dinv = d_vec; d = dinv + n; w = d + n; x = w + n; r = x + n;
+        return TB_OK;
+    }
+    void release()
+    {
+        if (d_vec) (void)hipFree(d_vec);
+        d_vec = dinv = d = w = x = r = nullptr;
+    }
+};
+
+struct MgLevel : MgVectors {
     tb_pattern *pat = nullptr;
     int64_t n = 0, nnz = 0;
     double *d_A = nullptr;          // the level's operator: owned below the finest level
     const double *A = nullptr;      // what the cycle reads (finest: the caller's array of the latest setup)
-    double *d_vec = nullptr;        // dinv | d | w | x | r (x, r: below the finest level) and, during setup, the Lanczos scratch
-    double *dinv = nullptr, *d = nullptr, *w = nullptr, *x = nullptr, *r = nullptr;
     uint8_t *d_presc = nullptr;     // flags of the level's prescribed dofs (NULL: none)
     std::vector<uint8_t> h_presc;
     double lmax = 0.0;
@@ -65,7 +85,67 @@ __device__ __forceinline__ void mg_gauss_jordan(int n, double *__restrict__ C)
         }
 }
 
-// tb_multigrid.hip
+// The coefficients of the Chebyshev iteration on [lmax / ratio, lmax] (Saad, Iterative Methods, Alg. 12.1), step by step: first() belongs to the step
+// that starts the recurrence (d = c2·D⁻¹(r − A x)), every next() to one further step (d = c1·d + c2·D⁻¹(r − A x)).
+struct ChebSchedule {
+    struct Step { double c1, c2; };
+    double theta, delta, sigma1, rho;
+    ChebSchedule(double lmax, double ratio)
+    {
+        const double lmin = lmax / ratio;
+        theta = 0.5 * (lmax + lmin); delta = 0.5 * (lmax - lmin); sigma1 = theta / delta;
+        rho = 1.0 / sigma1;
+    }
+    Step first() const { return Step{0.0, 1.0 / theta}; }
+    Step next()
+    {
+        const double rho_new = 1.0 / (2.0 * sigma1 - rho);
+        const Step s{rho_new * rho, 2.0 * rho_new / delta};
+        rho = rho_new;
+        return s;
+    }
+};
+
+// tb_multigrid.hip: enqueue-only launchers of the kernels the family shares
+void launch_cheb_step(tb_device *dev, int mode, int64_t n, ChebSchedule::Step c, const double *dinv, const double *r, const double *w, double *d, double *x); // k_mg_cheb<mode>
+void launch_dense_inverse(tb_device *dev, int n, const int64_t *rowptr, const int32_t *colidx, const double *nz, double *C); // C = A⁻¹ of a CSR with n ≤ MG_COARSEST_MAX rows
+void launch_fill_diag(tb_device *dev, int64_t n, const int64_t *diagpos, const uint8_t *flags, double *A); // flagged diagonals ← mean |diagonal| of the others
+void launch_fold_sum(tb_device *dev, int nb, const double *part, double *out);                              // *out = Σ part[0 … nb) in one fixed order
+void launch_fold_max(tb_device *dev, int nb, const double *part, double *out);                              // *out = max part[0 … nb), part ≥ 0
+
+// `degree` steps of the Chebyshev–Jacobi smoother for A x = r on the vectors v (dinv filled; d, w scratch) of n dofs, from x = 0 (no product before the
+// first step) or from the x given.  product(x, y) enqueues y = A x and returns a status.  Enqueues only.
+template <class Product>
+int cheb_smooth(tb_device *dev, int64_t n, const MgVectors &v, double lmax, double ratio, int degree, const double *r, double *x, bool from_zero, Product product)
+{
+    ChebSchedule s(lmax, ratio);
+    if (from_zero) launch_cheb_step(dev, 0, n, s.first(), v.dinv, r, nullptr, v.d, x);
+    else {
+        TB_TRY(product((const double *)x, v.w));
+        launch_cheb_step(dev, 1, n, s.first(), v.dinv, r, v.w, v.d, x);
+    }
+    for (int k = 1; k < degree; ++k) {
+        TB_TRY(product((const double *)x, v.w));
+        launch_cheb_step(dev, 2, n, s.next(), v.dinv, r, v.w, v.d, x);
+    }
+    return TB_OK;
+}
+
+// the argument checks of the set-up entries (`who`: the entry's name)
+inline int check_smoother_args(const char *who, int degree, double ratio)
+{
+    TB_REQUIRE(degree >= 1 && degree <= 64, "%s: smoother degree must be in 1..64 (got %d)", who, degree);
+    TB_REQUIRE(ratio > 1.0 && std::isfinite(ratio), "%s: interval_ratio must be a finite number above 1 (got %g)", who, ratio);
+    return TB_OK;
+}
+inline int check_amg_args(const char *who, double theta, int max_coarse, int max_levels)
+{
+    TB_REQUIRE(theta >= 0.0 && theta <= 1.0, "%s: theta must be in 0..1 (got %g)", who, theta);
+    TB_REQUIRE(max_coarse >= 1, "%s: max_coarse must be positive (got %d)", who, max_coarse);
+    TB_REQUIRE(max_levels >= 1 && max_levels <= 64, "%s: max_levels must be in 1..64 (got %d)", who, max_levels);
+    return TB_OK;
+}
+
 int build_plans(tb_mg *mg);                                                                  // symbolic phase (tb_mg_setup runs it on its first call): transfers, Galerkin plans, level storage
 void launch_galerkin_plane(tb_mg *mg, int fine_level, const double *Af, double *Ac);        // Ac = Pᵀ Af P on the per-dof plan of fine_level, nothing else (no diagonal fill); enqueues only
 void launch_dense_apply(tb_device *dev, int n, const double *C, const double *r, double *x); // x = C r, dense: one wavefront per row; enqueues only

@@ -1,9 +1,14 @@
 // tb_multigrid.hip — multigrid preconditioner on hexahedral grids (GMGPrecon, PMGPrecon and ChainedMGPrecon of the reference: src/solver/linear/multigrid.jl,
 // ext/ThunderboltFerriteMultigridExt.jl): h-levels of first-order fields on nested grids and, at the top, one p-level from a second-order field to the
 // first-order field on the same cells.  The plans come from tb_mg_planners.cpp (P row-wise, Pᵀ row-wise, the gather plan of PᵀAP, per dof or per
-// 3 × 3 block); this file holds the hierarchy object, the two numeric Galerkin kernels, the transfers, the Chebyshev–Jacobi smoother step, the
-// coarsest inverse and the V-cycle driver.
-// Every sum has one recorded order and no kernel uses an atomic: two setups, and two applications, give the same bits.
+// 3 × 3 block); this file holds the hierarchy object, the two numeric Galerkin kernels, the transfers, the V-cycle driver, and the kernels the whole
+// multigrid family calls through the launchers of tb_mg_internal.hpp (tb_amg.hip, tb_bidomain_mg.hip, the Chebyshev preconditioner of tb_krylov.hip):
+// the Chebyshev–Jacobi smoother step, the dense coarsest inverse and its product, the diagonal fill and the fold of per-workgroup partials.
+// Every sum of this file's kernels has one recorded order and none of them uses an atomic: two applications of one setup give the same bits, and two
+// setups the same level matrices and the same coarsest inverse.  λmax is not this file's: tb_mg_setup takes it from estimate_lambda_max
+// (tb_krylov.hip), whose Lanczos sums leave through block_sum_to — one unsafeAtomicAdd per 1 024-thread workgroup on grid_red workgroups.  Up to two
+// workgroups (levels of at most 2 048 dofs) that is one order; three or more add in arrival order, so on larger levels two setups may differ in the
+// last bits of λmax and, through the smoother's coefficients, of the cycle.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -205,14 +210,30 @@ k_mg_dense_apply(int n, const double *__restrict__ C, const double *__restrict__
     if (lane == 0) x[i] = s;
 }
 
-static inline unsigned blocks_of(int64_t n, int bs) { return (unsigned)std::max<int64_t>(1, (n + bs - 1) / bs); }
+// one workgroup: *out = the sum (MAX: the maximum; the partials folded here are absolute values) of part[0 … nb) in one fixed order — strided lane
+// folds from the lane's own partial, then an LDS tree
+template <bool MAX>
+__global__ void __launch_bounds__(256) k_fold_partials(int nb, const double *__restrict__ part, double *__restrict__ out)
+{
+    __shared__ double sm[256];
+    double v = (int)threadIdx.x < nb ? part[threadIdx.x] : 0.0;
+    for (int k = threadIdx.x + 256; k < nb; k += 256) v = MAX ? fmax(v, part[k]) : v + part[k];
+    sm[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sm[threadIdx.x] = MAX ? fmax(sm[threadIdx.x], sm[threadIdx.x + o]) : sm[threadIdx.x] + sm[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *out = sm[0];
+}
 
 static void free_plans(tb_mg *mg)
 {
     for (MgLevel &L : mg->lv) {
-        void *ptrs[] = {L.d_A, L.d_vec, L.d_presc, L.d_pptr, L.d_rptr, L.d_gptr, L.d_cdiag, L.d_pcol, L.d_rcol, L.d_pexp, L.d_rexp, L.d_gterms, L.d_brow};
+        L.release();
+        void *ptrs[] = {L.d_A, L.d_presc, L.d_pptr, L.d_rptr, L.d_gptr, L.d_cdiag, L.d_pcol, L.d_rcol, L.d_pexp, L.d_rexp, L.d_gterms, L.d_brow};
         for (void *p : ptrs) if (p) (void)hipFree(p);
-        L.d_A = nullptr; L.d_vec = nullptr; L.d_presc = nullptr; L.d_pptr = L.d_rptr = L.d_gptr = L.d_cdiag = nullptr;
+        L.d_A = nullptr; L.d_presc = nullptr; L.d_pptr = L.d_rptr = L.d_gptr = L.d_cdiag = nullptr;
         L.d_pcol = L.d_rcol = nullptr; L.d_pexp = L.d_rexp = nullptr; L.d_gterms = nullptr; L.d_brow = nullptr;
         L.blocked = false; L.n_terms = 0;
         L.A = nullptr;
@@ -301,9 +322,7 @@ int build_plans(tb_mg *mg)
                               g.ptr, &L.d_gptr, g.terms, &L.d_gterms, g.diag_pos, &L.d_cdiag));
         }
         if (!L.h_presc.empty() && l < nl - 1) TB_TRY(upload(dev, L.h_presc, &L.d_presc));
-        // dinv | d | w | x | r; the λmax estimate of setup borrows d, w, x, r and one more vector
-        TB_HIP(hipMalloc((void **)&L.d_vec, sizeof(double) * 6 * (size_t)std::max<int64_t>(L.n, 1)));
-        L.dinv = L.d_vec; L.d = L.dinv + L.n; L.w = L.d + L.n; L.x = L.w + L.n; L.r = L.x + L.n;
+        TB_TRY(L.alloc(L.n));
         if (l < nl - 1) TB_HIP(hipMalloc((void **)&L.d_A, sizeof(double) * (size_t)std::max<int64_t>(L.nnz, 1)));
         TB_TRY(spmv_plans(L.pat));
     }
@@ -329,10 +348,10 @@ static void launch_galerkin(tb_mg *mg, int fine_level)
                                U.pat->d_rowptr, U.A, (const uint8_t *)nullptr, L.d_brow, L.pat->d_bcol, L.pat->d_rowptr, (const uint8_t *)nullptr, L.d_A);
     } else
         hipLaunchKernelGGL(k_mg_galerkin, dim3(blocks_of(L.nnz * 16, 256)), dim3(256), 0, dev->stream, L.nnz, U.d_gptr, U.d_gterms, U.A, L.d_A);
-    if (L.d_presc) hipLaunchKernelGGL(k_mg_fill_diag, dim3(1), dim3(1024), 0, dev->stream, L.n, U.d_cdiag, L.d_presc, L.d_A);
+    if (L.d_presc) launch_fill_diag(dev, L.n, U.d_cdiag, L.d_presc, L.d_A);
 }
 
-// (tb_mg_internal.hpp) one value plane through the per-dof plan of fine_level, and the dense product, for the block cycle of tb_bidomain_mg.hip
+// (tb_mg_internal.hpp) one value plane through the per-dof plan of fine_level for the block cycle of tb_bidomain_mg.hip, and the kernels the family shares
 void launch_galerkin_plane(tb_mg *mg, int fine_level, const double *Af, double *Ac)
 {
     MgLevel &U = mg->lv[fine_level], &L = mg->lv[fine_level - 1];
@@ -343,27 +362,21 @@ void launch_dense_apply(tb_device *dev, int n, const double *C, const double *r,
     hipLaunchKernelGGL(k_mg_dense_apply, dim3(blocks_of((int64_t)n * 64, 256)), dim3(256), 0, dev->stream, n, C, r, x);
 }
 
-static int smooth(tb_mg *mg, int l, const double *r, double *x, bool from_zero)
+void launch_cheb_step(tb_device *dev, int mode, int64_t n, ChebSchedule::Step c, const double *dinv, const double *r, const double *w, double *d, double *x)
 {
-    MgLevel &L = mg->lv[l];
-    tb_device *dev = mg->dev;
-    const unsigned g = grid_for(dev, L.n, 256);
-    const double lmax = L.lmax, lmin = lmax / mg->ratio;
-    const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sigma1 = theta / delta;
-    double rho = 1.0 / sigma1;
-    if (from_zero) hipLaunchKernelGGL(k_mg_cheb<0>, dim3(g), dim3(256), 0, dev->stream, L.n, 0.0, 1.0 / theta, L.dinv, r, (const double *)nullptr, L.d, x);
-    else {
-        TB_TRY(launch_spmv(L.pat, L.A, x, 1.0, 0.0, L.w));
-        hipLaunchKernelGGL(k_mg_cheb<1>, dim3(g), dim3(256), 0, dev->stream, L.n, 0.0, 1.0 / theta, L.dinv, r, L.w, L.d, x);
-    }
-    for (int k = 1; k < mg->degree; ++k) {
-        TB_TRY(launch_spmv(L.pat, L.A, x, 1.0, 0.0, L.w));
-        const double rho_new = 1.0 / (2.0 * sigma1 - rho);
-        hipLaunchKernelGGL(k_mg_cheb<2>, dim3(g), dim3(256), 0, dev->stream, L.n, rho_new * rho, 2.0 * rho_new / delta, L.dinv, r, L.w, L.d, x);
-        rho = rho_new;
-    }
-    return TB_OK;
+    auto *k = mode == 0 ? k_mg_cheb<0> : mode == 1 ? k_mg_cheb<1> : k_mg_cheb<2>;
+    hipLaunchKernelGGL(k, dim3(grid_for(dev, n, 256)), dim3(256), 0, dev->stream, n, c.c1, c.c2, dinv, r, w, d, x);
 }
+void launch_dense_inverse(tb_device *dev, int n, const int64_t *rowptr, const int32_t *colidx, const double *nz, double *C)
+{
+    hipLaunchKernelGGL(k_mg_dense_inverse, dim3(1), dim3(1024), 0, dev->stream, n, rowptr, colidx, nz, C);
+}
+void launch_fill_diag(tb_device *dev, int64_t n, const int64_t *diagpos, const uint8_t *flags, double *A)
+{
+    hipLaunchKernelGGL(k_mg_fill_diag, dim3(1), dim3(1024), 0, dev->stream, n, diagpos, flags, A);
+}
+void launch_fold_sum(tb_device *dev, int nb, const double *part, double *out) { hipLaunchKernelGGL(k_fold_partials<false>, dim3(1), dim3(256), 0, dev->stream, nb, part, out); }
+void launch_fold_max(tb_device *dev, int nb, const double *part, double *out) { hipLaunchKernelGGL(k_fold_partials<true>, dim3(1), dim3(256), 0, dev->stream, nb, part, out); }
 
 // x = M_l⁻¹ r: V(degree, degree) from x = 0; enqueues only
 static int cycle(tb_mg *mg, int l, const double *r, double *x)
@@ -372,17 +385,17 @@ static int cycle(tb_mg *mg, int l, const double *r, double *x)
     MgLevel &L = mg->lv[l];
     if (l == 0) {
         if (mg->amg) return amg_apply_cb(mg->amg, r, x);
-        hipLaunchKernelGGL(k_mg_dense_apply, dim3(blocks_of(L.n * 64, 256)), dim3(256), 0, dev->stream, (int)L.n, mg->d_cinv, r, x);
+        launch_dense_apply(dev, (int)L.n, mg->d_cinv, r, x);
         return TB_OK;
     }
     MgLevel &Cl = mg->lv[l - 1];
-    TB_TRY(smooth(mg, l, r, x, true));
-    TB_TRY(launch_spmv(L.pat, L.A, x, 1.0, 0.0, L.w));
+    auto product = [&](const double *u, double *y) { return launch_spmv(L.pat, L.A, u, 1.0, 0.0, y); };
+    TB_TRY(cheb_smooth(dev, L.n, L, L.lmax, mg->ratio, mg->degree, r, x, true, product));
+    TB_TRY(product(x, L.w));
     hipLaunchKernelGGL(k_mg_restrict, dim3(blocks_of(Cl.n, 256)), dim3(256), 0, dev->stream, Cl.n, L.d_rptr, L.d_rcol, L.d_rexp, r, (const double *)L.w, Cl.r);
     TB_TRY(cycle(mg, l - 1, Cl.r, Cl.x));
     hipLaunchKernelGGL(k_mg_prolong<true>, dim3(blocks_of(L.n, 256)), dim3(256), 0, dev->stream, L.n, L.d_pptr, L.d_pcol, L.d_pexp, (const double *)Cl.x, x);
-    TB_TRY(smooth(mg, l, r, x, false));
-    return TB_OK;
+    return cheb_smooth(dev, L.n, L, L.lmax, mg->ratio, mg->degree, r, x, false, product);
 }
 
 static int mg_apply_cb(void *ctx, const double *r, double *z)
@@ -532,9 +545,7 @@ int tb_mg_set_prescribed(tb_mg *mg, const uint8_t *d_prescribed_fine)
 int tb_mg_set_coarse_amg(tb_mg *mg, double theta, int max_coarse, int max_levels)
 {
     TB_REQUIRE(mg, "tb_mg_set_coarse_amg: NULL argument");
-    TB_REQUIRE(theta >= 0.0 && theta <= 1.0, "tb_mg_set_coarse_amg: theta must be in 0..1 (got %g)", theta);
-    TB_REQUIRE(max_coarse >= 1, "tb_mg_set_coarse_amg: max_coarse must be positive (got %d)", max_coarse);
-    TB_REQUIRE(max_levels >= 1 && max_levels <= 64, "tb_mg_set_coarse_amg: max_levels must be in 1..64 (got %d)", max_levels);
+    TB_TRY(check_amg_args("tb_mg_set_coarse_amg", theta, max_coarse, max_levels));
     TB_NO_CAPTURE(mg->dev);
     TB_HIP(hipSetDevice(mg->dev->id));
     free_plans(mg);
@@ -556,8 +567,7 @@ int tb_mg_coarse_amg(tb_mg *mg, tb_amg **out)
 int tb_mg_setup(tb_mg *mg, const double *d_Anz_fine, int degree, double interval_ratio)
 {
     TB_REQUIRE(mg && d_Anz_fine, "tb_mg_setup: NULL argument");
-    TB_REQUIRE(degree >= 1 && degree <= 64, "tb_mg_setup: smoother degree must be in 1..64 (got %d)", degree);
-    TB_REQUIRE(interval_ratio > 1.0 && std::isfinite(interval_ratio), "tb_mg_setup: interval_ratio must be a finite number above 1 (got %g)", interval_ratio);
+    TB_TRY(check_smoother_args("tb_mg_setup", degree, interval_ratio));
     tb_device *dev = mg->dev;
     TB_NO_CAPTURE(dev); // builds plans, reads λmax back
     TB_HIP(hipSetDevice(dev->id));
@@ -589,7 +599,7 @@ int tb_mg_setup(tb_mg *mg, const double *d_Anz_fine, int degree, double interval
         const int rc = tb_amg_setup(mg->amg, C0.A, degree, interval_ratio);
         if (rc) { free_plans(mg); return rc; }
     } else
-        hipLaunchKernelGGL(k_mg_dense_inverse, dim3(1), dim3(1024), 0, dev->stream, (int)C0.n, C0.pat->d_rowptr, C0.pat->d_colidx, C0.A, mg->d_cinv);
+        launch_dense_inverse(dev, (int)C0.n, C0.pat->d_rowptr, C0.pat->d_colidx, C0.A, mg->d_cinv);
     TB_HIP(hipGetLastError());
     mg->ready = true;
     return TB_OK;

@@ -22,6 +22,8 @@ static inline unsigned grid_for(tb_device *dev, int64_t n, int bs)
     const int64_t cap = (int64_t)dev->n_cu * 8;
     return (unsigned)(nb > cap ? cap : nb);
 }
+// grid of a kernel that gives every work item its own thread: ⌈n / bs⌉ workgroups, at least one
+static inline unsigned blocks_of(int64_t n, int bs) { return (unsigned)std::max<int64_t>(1, (n + bs - 1) / bs); }
 
 // ---- one maximum ----
 // max(a, b) that keeps a NaN of either operand (fmax returns the other one): the `max` of Julia's `maximum`, which the reaction-tangent controller
