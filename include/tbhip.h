@@ -51,6 +51,7 @@ typedef struct tb_locator tb_locator;
 typedef struct tb_ecg tb_ecg;
 typedef struct tb_bidomain tb_bidomain;
 typedef struct tb_bidomain_mg tb_bidomain_mg;
+typedef struct tb_bidomain_amg tb_bidomain_amg;
 typedef struct tb_eikonal tb_eikonal;
 
 enum {
@@ -203,6 +204,7 @@ const char *tb_version(void);
  * Added under 10, purely additive: tb_eikonal_* (create, destroy, solve, residual, last_counts, potential), tb_host_eikonal_local_solve (eikonal activation times: fast iterative method; potential from an action-potential
  * template).
  * Added under 10, purely additive: tb_amg_*, tb_pcg_solve_amg, tb_mg_set_coarse_amg, tb_mg_coarse_amg (smoothed-aggregation algebraic multigrid).
+ * Added under 10, purely additive: tb_bidomain_amg_* (smoothed-aggregation multigrid preconditioner of the bidomain block system: block V-cycle from the matrix alone).
  * A host binding compares tb_abi_revision() with the
  * TB_ABI_REVISION it was written against and refuses to run on a mismatch (julia/ThunderboltHIPBackend.jl does, in __init__) */
 #define TB_ABI_REVISION 10
@@ -1087,6 +1089,61 @@ int tb_bidomain_mg_n_levels(tb_bidomain_mg *h, int *n_levels);
 int tb_bidomain_mg_level_planes(tb_bidomain_mg *h, int level, const double **d_planes, int64_t *nnz);
 int tb_bidomain_mg_level_lambda_max(tb_bidomain_mg *h, int level, double *lmax);
 int tb_bidomain_mg_cycle_below(tb_bidomain_mg *h, int level);
+
+/* ------------------------------------------------------------------ algebraic multigrid preconditioner of the bidomain block system (tb_bidomain_amg.hip)
+ * One smoothed-aggregation V(degree, degree) cycle on the node pairs (φₘ, φₑ) of a tb_bidomain, built from the matrix alone: for tetrahedra, the readers'
+ * meshes and every other mesh without nested grids.  Levels are numbered as tb_amg's: 0 is the finest.
+ *   auxiliary matrix   the a₂₂ = −Δt(Kᵢ + Kₑ) plane with the elimination of the ground baked in (ground_diag on the eliminated diagonals).  The scalar
+ *                      hierarchy of tb_amg_* runs on it unchanged, with one component label: strength of connection, the three host aggregation passes, T,
+ *                      P = T − ω D⁻¹ A T with ω = 4 / (3 λ).  A grounded node has no strong neighbour there: it stays outside every aggregate and its row of
+ *                      P is empty.
+ *   block transfer     𝒫 = P ⊗ I₂: the same scalar P for φₘ and φₑ.  No ground flags below the finest level, no φₑ masks in restriction or prolongation: a
+ *                      grounded node gets no coarse correction in either unknown (the smoother alone treats its φₘ), coarse levels have no ground, and rows
+ *                      and columns of grounded nodes never reach a coarse plane, whatever ground_diag is.
+ *   coarse operators   X_c = Pᵀ X_f P per plane on the scalar hierarchy's planned patterns (A·P, then R·(A·P)); the three distinct planes a₁₁, a₁₂, a₂₂ go
+ *                      through one walk of the index streams, each sum in the order a scalar product of that plane alone has.  The coarse a₂₂ plane is
+ *                      the scalar hierarchy's own next level matrix — computed once, it is the input of strength and λ(D⁻¹A) for the next P and the φₑφₑ
+ *                      plane of the block level.  The coarse a₁₂ plane is symmetric and a₂₁ a copy of it.
+ *   cycle              the smoother, λmax, coarsest level and recursion of tb_bidomain_mg_*: Chebyshev on B⁻¹𝒜 over [λmax/interval_ratio, λmax], B the 2 × 2 node
+ *                      diagonal blocks (masked at grounded nodes on the finest level), one fused pass per step; λmax by 24 ordered Lanczos steps in the B inner
+ *                      product × 1.05; dense inverse of a last level of at most 512 nodes; V(degree, degree) from zero.  z_e = 0 at grounded nodes.
+ * No floating-point atomics in the set-up or in the cycle and one recorded order for every sum: two set-ups give the same planes, P and λmax, two applications
+ * the same bits.  The recursion stops as tb_amg's: max_coarse, max_levels, or aggregation that no longer coarsens.
+ *   tb_bidomain_amg_create   theta, max_coarse, max_levels as tb_amg_create; max_coarse above 512 is TB_ERR_UNSUPPORTED.  bd must outlive the handle.
+ *   tb_bidomain_amg_setup    after tb_bidomain_set_matrices (refused before it, and inside a capture).  The first call plans level by level (strength →
+ *                            download → host planner → upload → numeric); every later call keeps aggregates and patterns and redoes the numeric phase only
+ *                            (D⁻¹ and λ(D⁻¹A) of a₂₂, smoothed P and R, the fused products, sliced planes and block inverses, block λmax, the last level's
+ *                            inverse) — what a new Δt repeats.  A last level above 512 nodes is TB_ERR_UNSUPPORTED with the reason named.  A later
+ *                            tb_bidomain_set_matrices invalidates it: apply, solve and the inspectors refuse until the next set-up.
+ *   tb_bidomain_amg_replan   drops the plan: the next set-up aggregates anew
+ *   tb_bidomain_amg_apply    z = ℳ⁻¹ r, one cycle from z = 0; enqueues only (fits inside tb_graph_begin / tb_graph_end).  r ≠ z, node-interleaved, 16-byte aligned.
+ *   tb_bidomain_amg_solve    the conjugate gradients of tb_bidomain_mg_solve with this cycle: same stopping rule, looks, tb_solver_last_tolerance,
+ *                            not-positive-definite report and non-finite behaviour.  Refused inside a capture.  b ≠ x.
+ *   inspectors (host outputs, any array may be NULL): tb_bidomain_amg_n_levels; _level_size (nodes, non-zeros, aggregates — 0 on the last level); _level_csr
+ *                            (n + 1 row pointers, nnz columns of the level's scalar pattern); _level_planes (a₁₁, a₁₂, a₂₁, a₂₂, nnz values each in that CSR
+ *                            order, elimination baked in on level 0); _level_prolongator (as tb_amg_level_prolongator); _level_aggregates (−1: outside);
+ *                            _level_lambda_max (the block λmax).  The last three are refused on the last level.
+ *   tb_bidomain_amg_counts   successful set-ups of this handle so far, and host aggregation runs so far (one per level planned): a numeric-only set-up adds
+ *                            one to the first and nothing to the second.  Needs no set-up.
+ *   tb_bidomain_amg_products MEASUREMENT HOOK, not part of any solve: the products A·P and R·(A·P) between `level` and the level below once more, on the planes
+ *                            and transfers of the latest set-up — fused != 0: the two three-plane launches of the set-up; fused == 0: three launch pairs of
+ *                            the scalar product kernel on the same plans, one plane each.  Either way every plane comes out with the bits it had
+ *                            (scripts/bench_bidomain_amg.py times one against the other).  Enqueues only. */
+int tb_bidomain_amg_create(tb_bidomain *bd, double theta, int max_coarse, int max_levels, tb_bidomain_amg **out);
+int tb_bidomain_amg_destroy(tb_bidomain_amg *h);
+int tb_bidomain_amg_setup(tb_bidomain_amg *h, int degree, double interval_ratio);
+int tb_bidomain_amg_replan(tb_bidomain_amg *h);
+int tb_bidomain_amg_apply(tb_bidomain_amg *h, const double *d_r, double *d_z);
+int tb_bidomain_amg_solve(tb_bidomain_amg *h, const double *d_b, double *d_x, double rtol, double atol, int maxiter, int *iters, double *resnorm);
+int tb_bidomain_amg_n_levels(tb_bidomain_amg *h, int *n_levels);
+int tb_bidomain_amg_level_size(tb_bidomain_amg *h, int level, int64_t *n, int64_t *nnz, int64_t *n_aggregates);
+int tb_bidomain_amg_level_csr(tb_bidomain_amg *h, int level, int64_t *rowptr, int32_t *colidx);
+int tb_bidomain_amg_level_planes(tb_bidomain_amg *h, int level, double *a11, double *a12, double *a21, double *a22);
+int tb_bidomain_amg_level_prolongator(tb_bidomain_amg *h, int level, int64_t *nnz, int64_t *rowptr, int32_t *colidx, double *values);
+int tb_bidomain_amg_level_aggregates(tb_bidomain_amg *h, int level, int32_t *aggregate);
+int tb_bidomain_amg_level_lambda_max(tb_bidomain_amg *h, int level, double *lmax);
+int tb_bidomain_amg_counts(tb_bidomain_amg *h, int64_t *setups, int64_t *aggregations);
+int tb_bidomain_amg_products(tb_bidomain_amg *h, int level, int fused);
 
 /* ------------------------------------------------------------------ host-side generators (no GPU needed)
  * Ferrite-convention synthetic inputs for benchmarks and tests: generate_grid (src/mesh/generators.jl:942),

@@ -1083,6 +1083,86 @@ end
 # measurement hook: the coarse tail of a cycle on whatever the level's buffers hold; only its duration means something
 mg_cycle_below!(bmg::HIPBidomainMultigrid, level::Integer) = check(ccall((:tb_bidomain_mg_cycle_below, libtbhip), Cint, (Ptr{Cvoid}, Cint), bmg.handle, level))
 
+# Algebraic multigrid preconditioner of the block system (tb_bidomain_amg_*): one smoothed-aggregation V(degree, degree) cycle on the node pairs, built from
+# the matrix alone — for tetrahedra and every other mesh without nested grids.  Levels are numbered as HIPAMGPrecon's: 0 is the finest.  setup! follows every
+# update_system_matrix!: the first one plans, every later one redoes the numeric phase on the same aggregates; replan! drops the plan.
+mutable struct HIPBidomainAlgebraicMultigrid
+    handle::Ptr{Cvoid}
+    sys::HIPBidomainSystem   # outlives the handle
+    degree::Int
+    interval_ratio::Float64
+end
+function HIPBidomainAlgebraicMultigrid(sys::HIPBidomainSystem; theta::Real = 0.25, degree::Integer = 2, interval_ratio::Real = 4.0, max_coarse::Integer = 128,
+                                       max_levels::Integer = 16)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:tb_bidomain_amg_create, libtbhip), Cint, (Ptr{Cvoid}, Cdouble, Cint, Cint, Ref{Ptr{Cvoid}}), sys.handle, theta, max_coarse, max_levels, h))
+    bamg = HIPBidomainAlgebraicMultigrid(h[], sys, degree, interval_ratio)
+    finalizer(m -> (ccall((:tb_bidomain_amg_destroy, libtbhip), Cint, (Ptr{Cvoid},), m.handle); m.handle = C_NULL), bamg)
+    return bamg
+end
+setup!(bamg::HIPBidomainAlgebraicMultigrid) =
+    check(ccall((:tb_bidomain_amg_setup, libtbhip), Cint, (Ptr{Cvoid}, Cint, Cdouble), bamg.handle, bamg.degree, bamg.interval_ratio))
+replan!(bamg::HIPBidomainAlgebraicMultigrid) = check(ccall((:tb_bidomain_amg_replan, libtbhip), Cint, (Ptr{Cvoid},), bamg.handle))
+mg_apply!(z::HIPVector{Float64}, bamg::HIPBidomainAlgebraicMultigrid, r::HIPVector{Float64}) =
+    check(ccall((:tb_bidomain_amg_apply, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), bamg.handle, r.ptr, z.ptr))
+function bidomain_solve!(x::HIPVector{Float64}, bamg::HIPBidomainAlgebraicMultigrid, b::HIPVector{Float64}; rtol::Real = 1e-5, atol::Real = 1e-6, maxiter::Integer = 1000)
+    iters, res = Ref{Cint}(0), Ref{Cdouble}(0.0)
+    check(ccall((:tb_bidomain_amg_solve, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Cint, Ref{Cint}, Ref{Cdouble}),
+        bamg.handle, b.ptr, x.ptr, rtol, atol, maxiter, iters, res))
+    return Int(iters[]), res[]
+end
+function n_levels(bamg::HIPBidomainAlgebraicMultigrid)
+    n = Ref{Cint}(0)
+    check(ccall((:tb_bidomain_amg_n_levels, libtbhip), Cint, (Ptr{Cvoid}, Ref{Cint}), bamg.handle, n))
+    return Int(n[])
+end
+# (nodes, non-zeros of the scalar pattern, aggregates) of a level; the last level has no aggregates
+function amg_level_size(bamg::HIPBidomainAlgebraicMultigrid, level::Integer)
+    n, nnz, na = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:tb_bidomain_amg_level_size, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ref{Int64}, Ref{Int64}, Ref{Int64}), bamg.handle, level, n, nnz, na))
+    return n[], nnz[], na[]
+end
+# the level's scalar pattern (0-based row pointers and columns) and its four planes (a₁₁, a₁₂, a₂₁, a₂₂) in that CSR order, on the host
+function amg_level_blocks(bamg::HIPBidomainAlgebraicMultigrid, level::Integer)
+    n, nnz, _ = amg_level_size(bamg, level)
+    rowptr, colidx = Vector{Int64}(undef, n + 1), Vector{Int32}(undef, nnz)
+    check(ccall((:tb_bidomain_amg_level_csr, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ptr{Int64}, Ptr{Int32}), bamg.handle, level, rowptr, colidx))
+    planes = [Vector{Float64}(undef, nnz) for _ in 1:4]
+    check(ccall((:tb_bidomain_amg_level_planes, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), bamg.handle, level,
+        planes[1], planes[2], planes[3], planes[4]))
+    return rowptr, colidx, planes
+end
+# the scalar P from level + 1 to level (0-based CSR); the block transfer is P ⊗ I₂
+function amg_level_prolongator(bamg::HIPBidomainAlgebraicMultigrid, level::Integer)
+    n, _, _ = amg_level_size(bamg, level)
+    nnz = Ref{Int64}(0)
+    check(ccall((:tb_bidomain_amg_level_prolongator, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ref{Int64}, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}), bamg.handle, level, nnz,
+        Ptr{Int64}(C_NULL), Ptr{Int32}(C_NULL), Ptr{Float64}(C_NULL)))
+    rowptr, colidx, values = Vector{Int64}(undef, n + 1), Vector{Int32}(undef, nnz[]), Vector{Float64}(undef, nnz[])
+    check(ccall((:tb_bidomain_amg_level_prolongator, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ref{Int64}, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}), bamg.handle, level, nnz,
+        rowptr, colidx, values))
+    return rowptr, colidx, values
+end
+function amg_level_aggregates(bamg::HIPBidomainAlgebraicMultigrid, level::Integer)
+    agg = Vector{Int32}(undef, amg_level_size(bamg, level)[1])
+    check(ccall((:tb_bidomain_amg_level_aggregates, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ptr{Int32}), bamg.handle, level, agg))
+    return agg
+end
+# (successful set-ups so far, host aggregation runs so far): a numeric-only set-up adds one to the first and nothing to the second
+function amg_counts(bamg::HIPBidomainAlgebraicMultigrid)
+    s, a = Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:tb_bidomain_amg_counts, libtbhip), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), bamg.handle, s, a))
+    return s[], a[]
+end
+# measurement hook: the Galerkin products between `level` and the level below once more, fused or as three launch pairs of the scalar kernel; same bits
+amg_products!(bamg::HIPBidomainAlgebraicMultigrid, level::Integer, fused::Bool = true) =
+    check(ccall((:tb_bidomain_amg_products, libtbhip), Cint, (Ptr{Cvoid}, Cint, Cint), bamg.handle, level, fused ? 1 : 0))
+function amg_level_lambda_max(bamg::HIPBidomainAlgebraicMultigrid, level::Integer)
+    λ = Ref{Cdouble}(0.0)
+    check(ccall((:tb_bidomain_amg_level_lambda_max, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ref{Cdouble}), bamg.handle, level, λ))
+    return λ[]
+end
+
 # ---------------------------------------------------------------- Newmark-β elastodynamics (src/solver/time/newmark.jl)
 # The mass operator of the displacement field is an ordinary HIPBilinearOperator: tb_assemble_matrix accepts BilinearMassIntegrator on ncomp = 3.
 # ũ = uₙ + Δt vₙ + (½−β)Δt² aₙ, ṽ = vₙ + (1−γ)Δt aₙ (newmark.jl:580-581)

@@ -34,6 +34,7 @@ from .multidomain import (insert_interfaces, InterfaceRecords, interface_dofs, e
                           InterfaceDiffusionModel, ReactionDiffusionSplit, InterfaceDiffusionForm, PointwiseMultiODEFunction, MultiSolverCache,
                           MultiDomainFunction, plan_ep, semidiscretize_ep, MultiDomainHeatStage, MultiDomainLieTrotterGodunov, heat_dofrange_of, QUAD_FACETS)
 from . import bidomain  # noqa: F401
-from .bidomain import ParabolicEllipticBidomainModel, BidomainBackwardEulerStage, BidomainSystem, BidomainMultigrid  # noqa: F401
+from .bidomain import (ParabolicEllipticBidomainModel, BidomainBackwardEulerStage, BidomainSystem, BidomainMultigrid, BidomainAMGPrecon,  # noqa: F401
+                       BidomainAlgebraicMultigrid)
 from . import eikonal  # noqa: F401
 from .eikonal import EikonalModel, EikonalActivationCache, solve_activation, ActionPotentialTemplate, activation_potential  # noqa: F401

@@ -257,6 +257,21 @@ SIGNATURES = {
     "tb_bidomain_mg_level_planes": (C.c_int, [vp, C.c_int, C.POINTER(vp), c_i64p]),
     "tb_bidomain_mg_level_lambda_max": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double)]),
     "tb_bidomain_mg_cycle_below": (C.c_int, [vp, C.c_int]),
+    "tb_bidomain_amg_create": (C.c_int, [vp, C.c_double, C.c_int, C.c_int, C.POINTER(vp)]),
+    "tb_bidomain_amg_destroy": (C.c_int, [vp]),
+    "tb_bidomain_amg_setup": (C.c_int, [vp, C.c_int, C.c_double]),
+    "tb_bidomain_amg_replan": (C.c_int, [vp]),
+    "tb_bidomain_amg_apply": (C.c_int, [vp, vp, vp]),
+    "tb_bidomain_amg_solve": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "tb_bidomain_amg_n_levels": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "tb_bidomain_amg_level_size": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tb_bidomain_amg_level_csr": (C.c_int, [vp, C.c_int, c_i64p, c_i32p]),
+    "tb_bidomain_amg_level_planes": (C.c_int, [vp, C.c_int, c_dp, c_dp, c_dp, c_dp]),
+    "tb_bidomain_amg_level_prolongator": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int64), c_i64p, c_i32p, c_dp]),
+    "tb_bidomain_amg_level_aggregates": (C.c_int, [vp, C.c_int, c_i32p]),
+    "tb_bidomain_amg_level_lambda_max": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double)]),
+    "tb_bidomain_amg_products": (C.c_int, [vp, C.c_int, C.c_int]),
+    "tb_bidomain_amg_counts": (C.c_int, [vp, c_i64p, c_i64p]),
     "tb_eikonal_create": (C.c_int, [vp, C.POINTER(vp)]),
     "tb_eikonal_destroy": (C.c_int, [vp]),
     "tb_eikonal_solve": (C.c_int, [vp, C.c_int64, c_i32p, c_dp, C.c_double, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -7,7 +7,7 @@ and the ECG caches drive through the protocol of the geometric multigrid (materi
 and GMGPrecon(gh, coarse=AMGPrecon()) it replaces the dense inverse of the coarsest level (multigrid.py → tb_mg_set_coarse_amg).
 
 Covered: one field of 1 or 3 components on the whole grid, CG, V-cycles with the Chebyshev–Jacobi smoother.  Refused with a message: the bidomain block
-system, GMRES, W- and F-cycles, other smoothers, subdomain dof handlers.  Out of scope: rigid-body rotations in the near-null space (elasticity gets the
+system (BidomainAMGPrecon in bidomain.py is its recipe), GMRES, W- and F-cycles, other smoothers, subdomain dof handlers.  Out of scope: rigid-body rotations in the near-null space (elasticity gets the
 translations only), block aggregation, aggregation on the device, classical Ruge–Stüben coarsening, Float32, several ranks."""
 import ctypes as C
 

@@ -12,7 +12,9 @@ those dofs are eliminated, the mean diagonal of the φₑφₑ block goes on the
 
 The coupled solve runs in csrc/tb_bidomain.hip (tb_bidomain_*): one fused product for all four blocks over a node-interleaved unknown, and conjugate
 gradients preconditioned with the inverse 2 × 2 diagonal blocks — or, with `precond=GMGPrecon(gh)`, with one geometric multigrid V-cycle on the node
-pairs (csrc/tb_bidomain_mg.hip, tb_bidomain_mg_*: BidomainMultigrid), whose iteration count does not grow with the mesh.  BidomainBackwardEulerStage has
+pairs (csrc/tb_bidomain_mg.hip, tb_bidomain_mg_*: BidomainMultigrid), whose iteration count does not grow with the mesh; on meshes without a
+GridHierarchy (tetrahedra, the readers' meshes, the generated ventricle) `precond=BidomainAMGPrecon()` gives the same from the matrix alone: one
+smoothed-aggregation V-cycle on the node pairs (csrc/tb_bidomain_amg.hip, tb_bidomain_amg_*: BidomainAlgebraicMultigrid).  BidomainBackwardEulerStage has
 the interface of BackwardEulerStage, so it goes into LieTrotterGodunov and ReactionTangentController unchanged."""
 import ctypes as C
 
@@ -23,6 +25,8 @@ from ._lib import check, lib
 from .api import (BilinearDiffusionIntegrator, BilinearMassIntegrator, ConductivityToDiffusivityCoefficient, ConstantCoefficient, DeviceVector, DofHandler,
                   LagrangeCollection, LinearIntegrator, _ptr, allocate_matrix, needs_update, setup_operator, solve_converged, update_operator)
 from .ecg import _vertex_ids, vertex_dofs
+from .amg import AMGPrecon
+from .amg import check_supported as amg_check_supported
 from .multigrid import ChainedMGPrecon, GMGPrecon, PMGPrecon, check_supported
 from .solid import meandiag
 
@@ -69,16 +73,17 @@ class BidomainSystem:
 
     def solve(self, b, x, rtol=1e-5, atol=1e-6, maxiter=1000, precond=None):
         """(iterations, residual norm).  precond None: block-Jacobi PCG (tb_bidomain_solve); a BidomainMultigrid of this system, set up for the current
-        matrices: CG preconditioned by one V-cycle (tb_bidomain_mg_solve)"""
+        matrices: CG preconditioned by one V-cycle (tb_bidomain_mg_solve); a BidomainAlgebraicMultigrid likewise (tb_bidomain_amg_solve)"""
         it, res = C.c_int(), C.c_double()
         if precond is None:
             check(lib().tb_bidomain_solve(self.h, _ptr(b), _ptr(x), float(rtol), float(atol), int(maxiter), C.byref(it), C.byref(res)))
-        elif isinstance(precond, BidomainMultigrid):
+        elif isinstance(precond, (BidomainMultigrid, BidomainAlgebraicMultigrid)):
             if precond.system is not self:
                 raise ValueError("BidomainSystem.solve: the multigrid hierarchy was materialised for another block system")
-            check(lib().tb_bidomain_mg_solve(precond.h, _ptr(b), _ptr(x), float(rtol), float(atol), int(maxiter), C.byref(it), C.byref(res)))
+            solve = lib().tb_bidomain_mg_solve if isinstance(precond, BidomainMultigrid) else lib().tb_bidomain_amg_solve
+            check(solve(precond.h, _ptr(b), _ptr(x), float(rtol), float(atol), int(maxiter), C.byref(it), C.byref(res)))
         else:
-            raise TypeError("BidomainSystem.solve: precond is None (block-Jacobi) or a BidomainMultigrid")
+            raise TypeError("BidomainSystem.solve: precond is None (block-Jacobi), a BidomainMultigrid or a BidomainAlgebraicMultigrid")
         return it.value, res.value
 
     def pack(self, m, e, out, zero_ground=False):
@@ -169,14 +174,141 @@ class BidomainMultigrid:
             pass
 
 
+class BidomainAMGPrecon:
+    """BidomainAMGPrecon(theta=0.25, degree=2, interval_ratio=4.0, max_coarse=128, max_levels=16): the recipe of the algebraic block cycle — AMGPrecon's
+    arguments with nodes in the place of dofs.  The last level is inverted densely: at most 512 nodes (1 024 unknowns); the default of 128 keeps the
+    one-workgroup dense inverse from dominating the numeric set-up."""
+
+    def __init__(self, theta=0.25, degree=2, interval_ratio=4.0, max_coarse=128, max_levels=16, cycle="V", smoother="chebyshev"):
+        if cycle != "V":
+            raise NotImplementedError("BidomainAMGPrecon: V-cycles only (W- and F-cycles are out of scope)")
+        if smoother != "chebyshev":
+            raise NotImplementedError("BidomainAMGPrecon: the Chebyshev smoother on the 2 x 2 node blocks only")
+        self.theta, self.degree, self.interval_ratio = float(theta), int(degree), float(interval_ratio)
+        self.max_coarse, self.max_levels = int(max_coarse), int(max_levels)
+
+    def check(self, dh):
+        amg_check_supported(dh)
+        if dh.ip.order != 1 or dh.ip.ncomp != 1:
+            raise NotImplementedError("BidomainAMGPrecon: first-order scalar fields only (order %d, %d component(s))" % (dh.ip.order, dh.ip.ncomp))
+
+    def materialize(self, system):
+        return BidomainAlgebraicMultigrid(system, self.theta, self.degree, self.interval_ratio, self.max_coarse, self.max_levels)
+
+
+class BidomainAlgebraicMultigrid:
+    """BidomainAlgebraicMultigrid(system, theta=0.25, degree=2, interval_ratio=4.0, max_coarse=128, max_levels=16): the materialised smoothed-aggregation
+    hierarchy of one BidomainSystem (tb_bidomain_amg_*).  Level 0 is the block system, level l + 1 the Galerkin operator of level l's aggregates (found on
+    the φₑφₑ plane, one scalar prolongator for both unknowns).  `setup()` follows every `system.set_matrices`: the first one plans, every later one
+    redoes the numeric phase on the same aggregates; `replan()` drops the plan.  `setups` and `aggregations` are the library's own counts
+    (tb_bidomain_amg_counts): successful set-ups, and host aggregation runs — one per level planned, none in a numeric-only set-up.  `apply(r, z)` is one
+    V(degree, degree) cycle on node-interleaved vectors."""
+
+    def __init__(self, system, theta=0.25, degree=2, interval_ratio=4.0, max_coarse=128, max_levels=16):
+        if not isinstance(system, BidomainSystem):
+            raise TypeError("BidomainAlgebraicMultigrid: pass the BidomainSystem the hierarchy preconditions")
+        self.system, self.device, self.degree, self.interval_ratio = system, system.pattern.dmesh.device, int(degree), float(interval_ratio)
+        self.h = C.c_void_p()
+        check(lib().tb_bidomain_amg_create(system.h, float(theta), int(max_coarse), int(max_levels), C.byref(self.h)))
+
+    def setup(self):
+        """plan (first call) and numeric phase for the matrices of the latest system.set_matrices"""
+        check(lib().tb_bidomain_amg_setup(self.h, self.degree, self.interval_ratio))
+        return self
+
+    def replan(self):
+        check(lib().tb_bidomain_amg_replan(self.h))
+        return self
+
+    def _counts(self):
+        s, a = C.c_int64(), C.c_int64()
+        check(lib().tb_bidomain_amg_counts(self.h, C.byref(s), C.byref(a)))
+        return s.value, a.value
+
+    @property
+    def setups(self):
+        return self._counts()[0]
+
+    @property
+    def aggregations(self):
+        return self._counts()[1]
+
+    def apply(self, r, z):
+        check(lib().tb_bidomain_amg_apply(self.h, _ptr(r), _ptr(z)))
+        return z
+
+    @property
+    def n_levels(self):
+        n = C.c_int()
+        check(lib().tb_bidomain_amg_n_levels(self.h, C.byref(n)))
+        return n.value
+
+    def level_size(self, level):
+        """(nodes, non-zeros of the scalar pattern, aggregates) of a level; the last level has no aggregates"""
+        n, nnz, na = C.c_int64(), C.c_int64(), C.c_int64()
+        check(lib().tb_bidomain_amg_level_size(self.h, level, C.byref(n), C.byref(nnz), C.byref(na)))
+        return n.value, nnz.value, na.value
+
+    def level_pattern(self, level):
+        """(rowptr, colidx) of the level's scalar pattern"""
+        n, nnz, _ = self.level_size(level)
+        ptr, col = np.empty(n + 1, dtype=np.int64), np.empty(nnz, dtype=np.int32)
+        check(lib().tb_bidomain_amg_level_csr(self.h, level, ptr.ctypes.data_as(L.c_i64p), col.ctypes.data_as(L.c_i32p)))
+        return ptr, col
+
+    def level_blocks(self, level):
+        """(a₁₁, a₁₂, a₂₁, a₂₂) of the level's operator: CSR values on level_pattern(level), host arrays"""
+        out = np.empty((4, self.level_size(level)[1]))
+        check(lib().tb_bidomain_amg_level_planes(self.h, level, *(out[q].ctypes.data_as(L.c_dp) for q in range(4))))
+        return tuple(out)
+
+    def prolongator(self, level):
+        """the scalar P from level + 1 to level as a scipy.sparse.csr_matrix (the block transfer is P ⊗ I₂)"""
+        import scipy.sparse as sparse
+        n, _, na = self.level_size(level)
+        nnz = C.c_int64()
+        check(lib().tb_bidomain_amg_level_prolongator(self.h, level, C.byref(nnz), None, None, None))
+        ptr, col, val = np.empty(n + 1, dtype=np.int64), np.empty(nnz.value, dtype=np.int32), np.empty(nnz.value)
+        check(lib().tb_bidomain_amg_level_prolongator(self.h, level, None, ptr.ctypes.data_as(L.c_i64p), col.ctypes.data_as(L.c_i32p), val.ctypes.data_as(L.c_dp)))
+        return sparse.csr_matrix((val, col, ptr), shape=(n, na))
+
+    def aggregates(self, level):
+        """the aggregate of every node of the level (−1: outside every aggregate, as every grounded node is)"""
+        out = np.empty(self.level_size(level)[0], dtype=np.int32)
+        check(lib().tb_bidomain_amg_level_aggregates(self.h, level, out.ctypes.data_as(L.c_i32p)))
+        return out
+
+    def lambda_max(self, level):
+        """the estimate of λmax(B⁻¹𝒜) the level's smoother runs on"""
+        out = C.c_double()
+        check(lib().tb_bidomain_amg_level_lambda_max(self.h, level, C.byref(out)))
+        return out.value
+
+    def products(self, level, fused=True):
+        """measurement hook: the Galerkin products between `level` and the level below once more (enqueues only) — fused: the two three-plane launches
+        of the set-up; otherwise three launch pairs of the scalar product kernel, one plane each.  The planes keep their bits either way."""
+        check(lib().tb_bidomain_amg_products(self.h, int(level), int(bool(fused))))
+
+    def close(self):
+        if self.h:
+            lib().tb_bidomain_amg_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class BidomainBackwardEulerStage:
     """BackwardEulerStage for the bidomain block system: perform_step(φₘ, t, Δt) advances φₘ in place and the stage's own `phi_e` (n values, zero at
     the start, the initial guess of the next step).  `ground`: vertex ids (or positions), mandatory.  `source`: the transmembrane stimulus, a
     LinearIntegrator scaled as BackwardEulerStage scales its source.  `source_e`: the extracellular current Iₛₜᵢₘ,ₑ − Iₛₜᵢₘ,ᵢ, a LinearIntegrator or
     nodal currents by dof (array of n values); it has to sum to zero (checked whenever it is (re)assembled).  The combined operator is rebuilt only
     when Δt changes (`generation` counts the rebuilds).  `solver.mirror` has no meaning here.  `precond` (keyword only): None — block-Jacobi PCG — or
-    GMGPrecon(gh) with gh's finest grid the stage's: the hierarchy is materialised here (`multigrid`, a BidomainMultigrid) and set up again with every
-    rebuild of the operator."""
+    GMGPrecon(gh) with gh's finest grid the stage's, or BidomainAMGPrecon(...) on any mesh: the hierarchy is materialised here (`multigrid`, a
+    BidomainMultigrid or a BidomainAlgebraicMultigrid) and set up again with every rebuild of the operator (the algebraic one keeps its aggregates)."""
 
     def __init__(self, solver, strategy, dh, diffusion_i, diffusion_e, ground, source=None, source_e=None, pattern=None, t0=0.0, *, precond=None):
         if dh.ip.order != 1 or dh.ip.ncomp != 1:
@@ -184,7 +316,9 @@ class BidomainBackwardEulerStage:
         if precond is not None:
             if isinstance(precond, (PMGPrecon, ChainedMGPrecon)):
                 raise NotImplementedError("BidomainBackwardEulerStage: %s is out of scope - the block system is first order, pass GMGPrecon(gh)" % type(precond).__name__)
-            if not isinstance(precond, GMGPrecon):
+            if isinstance(precond, AMGPrecon):
+                raise NotImplementedError("BidomainBackwardEulerStage: the scalar AMGPrecon is out of scope for the block system - pass BidomainAMGPrecon(...)")
+            if not isinstance(precond, (GMGPrecon, BidomainAMGPrecon)):
                 raise NotImplementedError("BidomainBackwardEulerStage: precond is None (block-Jacobi) or GMGPrecon(gh); %r is out of scope" % (precond,))
             precond.check(dh)
         if ground is None or len(ground) == 0:
@@ -216,7 +350,10 @@ class BidomainBackwardEulerStage:
         else:
             self.source_e_b = None
         self.system = BidomainSystem(self.M.pattern)
-        self.multigrid = None if precond is None else BidomainMultigrid(self.system, precond.gh, precond.degree, precond.interval_ratio)
+        if isinstance(precond, BidomainAMGPrecon):
+            self.multigrid = precond.materialize(self.system)
+        else:
+            self.multigrid = None if precond is None else BidomainMultigrid(self.system, precond.gh, precond.degree, precond.interval_ratio)
         # the mean diagonal of Kᵢ + Kₑ does not depend on Δt: read once (tb_meandiag is Ferrite's: the mean of |dᵢᵢ|, and K's diagonal is negative)
         self._kdiag = meandiag(self.Ki.pattern, self.Ki.A) + meandiag(self.Ke.pattern, self.Ke.A)
         self.phi_e = self.device.zeros(n)

@@ -336,6 +336,7 @@ static int plan_level_below(tb_amg *amg, int l, bool *coarsened)
         const int64_t *hp = l == 0 ? amg->pat->h_rowptr.data() : L.h_rowptr.data();
         const int32_t *hc = l == 0 ? amg->pat->h_colidx.data() : L.h_colidx.data();
         amgplan::plan_level(n, hp, hc, L.h_comp.empty() ? nullptr : L.h_comp.data(), L.h_strength.data(), L.plan);
+        ++amg->aggregations;
         if (L.plan.nc <= 0 || L.plan.nc >= n) { L.plan = amgplan::LevelPlan(); L.plan.n = n; return TB_OK; }
         amgplan::LevelPlan &p = L.plan;
         std::vector<double> tval((size_t)p.nc);
@@ -369,8 +370,14 @@ static int plan_level_below(tb_amg *amg, int l, bool *coarsened)
     return TB_OK;
 }
 
-// numeric phase between level l and l + 1: smoothed P, R, A·P, A_{l+1} = R (A·P); enqueues only
-static void launch_level_numeric(tb_amg *amg, int l)
+void launch_amg_spgemm(tb_device *dev, int64_t cnnz, const int32_t *crow, const int32_t *ccol, const int64_t *aptr, const int32_t *acol, const double *aval, const int64_t *bptr,
+                       const int32_t *bcol, const double *bval, double *cval)
+{
+    hipLaunchKernelGGL(k_amg_spgemm, dim3(blocks_of(cnnz, 256)), dim3(256), 0, dev->stream, cnnz, crow, ccol, aptr, acol, aval, bptr, bcol, bval, cval);
+}
+
+// numeric phase between level l and l + 1: smoothed P, R, A·P, A_{l+1} = R (A·P); enqueues only (the products of a block hierarchy may allocate on their first call)
+static int launch_level_numeric(tb_amg *amg, int l)
 {
     tb_device *dev = amg->dev;
     AmgLevel &L = amg->lv[(size_t)l], &N = amg->lv[(size_t)l + 1];
@@ -378,10 +385,10 @@ static void launch_level_numeric(tb_amg *amg, int l)
     hipLaunchKernelGGL(k_amg_smooth_p, dim3(blocks_of(L.pnnz, 256)), dim3(256), 0, dev->stream, L.pnnz, (const int32_t *)L.d_prow, (const int32_t *)L.d_pcol, L.rowptr,
                        L.colidx, L.A, (const int32_t *)L.d_agg, (const double *)L.d_tval, (const double *)L.dinv, omega, L.d_P);
     hipLaunchKernelGGL(k_amg_gather, dim3(blocks_of(L.pnnz, 256)), dim3(256), 0, dev->stream, L.pnnz, (const int64_t *)L.d_rperm, (const double *)L.d_P, L.d_R);
-    hipLaunchKernelGGL(k_amg_spgemm, dim3(blocks_of(L.apnnz, 256)), dim3(256), 0, dev->stream, L.apnnz, (const int32_t *)L.d_aprow, (const int32_t *)L.d_apcol, L.rowptr,
-                       L.colidx, L.A, (const int64_t *)L.d_pptr, (const int32_t *)L.d_pcol, (const double *)L.d_P, L.d_AP);
-    hipLaunchKernelGGL(k_amg_spgemm, dim3(blocks_of(N.nnz, 256)), dim3(256), 0, dev->stream, N.nnz, (const int32_t *)L.d_crow, N.colidx, (const int64_t *)L.d_rptr,
-                       (const int32_t *)L.d_rcol, (const double *)L.d_R, (const int64_t *)L.d_apptr, (const int32_t *)L.d_apcol, (const double *)L.d_AP, N.d_A);
+    if (amg->products) return amg->products(amg->products_ctx, l);
+    launch_amg_spgemm(dev, L.apnnz, L.d_aprow, L.d_apcol, L.rowptr, L.colidx, L.A, L.d_pptr, L.d_pcol, L.d_P, L.d_AP);
+    launch_amg_spgemm(dev, N.nnz, L.d_crow, N.colidx, L.d_rptr, L.d_rcol, L.d_R, L.d_apptr, L.d_apcol, L.d_AP, N.d_A);
+    return TB_OK;
 }
 
 // x = M_l⁻¹ r: V(degree, degree) from x = 0; enqueues only
@@ -430,12 +437,13 @@ static int setup_levels(tb_amg *amg)
         }
         AmgLevel &L = amg->lv[(size_t)l];
         if (last) {
-            if (L.n > MG_COARSEST_MAX) {
-                set_error("tb_amg_setup: the last level (%d) has %lld dofs; its dense inverse takes at most %d - the hierarchy stopped because %s", l, (long long)L.n,
-                          MG_COARSEST_MAX, l + 1 >= amg->max_levels ? "max_levels was reached (raise it)" : L.n <= amg->max_coarse ? "max_coarse allows it (lower it)"
+            if (L.n > amg->last_max) {
+                set_error("%s: the last level (%d) has %lld %s; its dense inverse takes at most %d - the hierarchy stopped because %s", amg->who, l, (long long)L.n,
+                          amg->unit, amg->last_max, l + 1 >= amg->max_levels ? "max_levels was reached (raise it)" : L.n <= amg->max_coarse ? "max_coarse allows it (lower it)"
                           : "aggregation no longer reduces the number of dofs (no strong couplings: lower theta)");
                 return TB_ERR_UNSUPPORTED;
             }
+            if (amg->products) break; // the block hierarchy inverts its own last level
             if (!amg->d_cinv) TB_HIP(hipMalloc((void **)&amg->d_cinv, sizeof(double) * (size_t)L.n * (size_t)L.n));
             launch_dense_inverse(dev, (int)L.n, L.rowptr, L.colidx, L.A, amg->d_cinv);
             break;
@@ -443,10 +451,10 @@ static int setup_levels(tb_amg *amg)
         hipLaunchKernelGGL(k_amg_dinv, dim3(blocks_of(L.n, 256)), dim3(256), 0, dev->stream, L.n, (const int64_t *)L.d_diag, L.A, L.dinv);
         TB_TRY(level_lambda_max(amg, l, &L.lmax));
         if (!(L.lmax > 0.0) || !std::isfinite(L.lmax)) {
-            set_error("tb_amg_setup: the estimate of lambda_max(D^-1 A) on level %d is %g (a matrix without positive diagonal, or non-finite entries)", l, L.lmax);
+            set_error("%s: the estimate of lambda_max(D^-1 A) on level %d is %g (a matrix without positive diagonal, or non-finite entries)", amg->who, l, L.lmax);
             return TB_ERR_BAD_ARG;
         }
-        launch_level_numeric(amg, l);
+        TB_TRY(launch_level_numeric(amg, l));
     }
     TB_HIP(hipGetLastError());
     amg->planned = true;

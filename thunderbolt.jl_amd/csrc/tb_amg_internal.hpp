@@ -36,6 +36,9 @@ struct AmgLevel : MgVectors {
 };
 
 int amg_apply_cb(void *ctx, const double *r, double *z); // z = one V-cycle on r (ctx: the tb_amg); enqueues only
+// k_amg_spgemm, C = A·B on the planned pattern of C (crow, ccol: row and column of every non-zero of C); enqueues only
+void launch_amg_spgemm(tb_device *dev, int64_t cnnz, const int32_t *crow, const int32_t *ccol, const int64_t *aptr, const int32_t *acol, const double *aval, const int64_t *bptr,
+                       const int32_t *bcol, const double *bval, double *cval);
 
 } // namespace tb
 
@@ -51,4 +54,12 @@ struct tb_amg {
     double ratio = 4.0;
     double *d_cinv = nullptr;            // dense inverse of the last level's operator
     double *d_red = nullptr;             // partials and result of the ordered reductions
+    // a block hierarchy on top of this one (tb_bidomain_amg.hip): `products(ctx, l)` replaces the two products of launch_level_numeric between level l and
+    // l + 1 — it carries further planes through the same walk and leaves this hierarchy's own A·P and A_{l+1} where the scalar products would; the last
+    // level is inverted there (at most last_max of its units here), and the set-up's messages carry its entry's name and unit
+    int (*products)(void *ctx, int l) = nullptr;
+    void *products_ctx = nullptr;
+    int last_max = tb::MG_COARSEST_MAX;
+    const char *who = "tb_amg_setup", *unit = "dofs";
+    int64_t aggregations = 0;            // host aggregation runs so far (one per level planned): what a numeric-only set-up leaves as it is
 };

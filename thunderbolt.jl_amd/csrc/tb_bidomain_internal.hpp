@@ -1,11 +1,15 @@
-// tb_bidomain_internal.hpp — what tb_bidomain.hip shares with tb_bidomain_mg.hip (the multigrid preconditioner of the block system): the block system's
-// record, the sliced block product with its two storage variants and its smoother epilogue, and the 2 × 2 block preconditioner of one node.
+// tb_bidomain_internal.hpp — what tb_bidomain.hip shares with tb_bidomain_mg.hip and tb_bidomain_amg.hip (the multigrid preconditioners of the block system):
+// the block system's record, the sliced block product with its two storage variants and its smoother epilogue, the 2 × 2 block preconditioner of one
+// node, and the level record, smoother, λmax estimate and conjugate gradients of a block cycle.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
+#include <vector>
 
 #include "tb_internal.h"
+#include "tb_mg_internal.hpp"
 #include "tb_reduce.hpp"
 
 struct tb_bidomain {
@@ -116,5 +120,61 @@ static void enqueue_apply(tb_bidomain *h, const double *x, double *y, double *xy
     hipLaunchKernelGGL((k_bd_apply<DOT>), dim3((unsigned)((h->n_slices + 3) / 4)), dim3(256), 0, h->pat->mesh->dev->stream, h->n, h->n_slices, h->d_base, h->entries, h->d_col,
                        h->d_val, h->d_ground, h->ground_diag, (const double2 *)x, (double2 *)y, xy, BdStep());
 }
+
+// ---- what the two multigrid preconditioners of the block system share (tb_bidomain_mg.hip: nested hexahedral grids; tb_bidomain_amg.hip: smoothed
+// aggregation).  The kernels live in tb_bidomain_mg.hip behind the functions below.
+constexpr int BD_COARSEST_NODES = MG_COARSEST_MAX / 2; // 512 nodes, 1 024 unknowns: the dense inverse of tb_multigrid.hip
+
+// a level of a block cycle
+struct BdMgLevel {
+    tb_pattern *pat = nullptr;       // the level's scalar pattern (geometric levels and the finest level)
+    int64_t n = 0, nnz = 0, n_slices = 0, entries = 0;
+    bool fine = false;               // the finest level: products run on the block system's own three planes and flags
+    const uint8_t *ground = nullptr; // what the kernels read (finest: the block system's flags)
+    uint8_t *d_ground = nullptr;     // owned, below the finest level
+    double *d_csr = nullptr;         // 4 · nnz: planes a₁₁, a₁₂, a₂₁, a₂₂ in the pattern's CSR order, elimination baked in
+    int64_t *d_base = nullptr;       // sliced storage of the smoothed levels below the finest (the finest level's is the block system's)
+    uint32_t *d_col = nullptr;
+    double *d_val = nullptr;         // 4 · entries
+    double *d_binv = nullptr;        // 3 n: inverse diagonal blocks, zero in the φₑ row and column of a grounded node
+    double *d_vec = nullptr;         // d | w | xt | x | r, 2n each (the Lanczos estimate of set-up borrows all five)
+    double *d = nullptr, *w = nullptr, *xt = nullptr, *x = nullptr, *r = nullptr;
+    double lmax = 0.0;
+};
+
+// what the smoother, the λmax estimate and the solve need of the hierarchy they run in
+struct BdCycle {
+    tb_bidomain *bd;
+    tb_device *dev;
+    int degree;
+    double ratio;
+    bool split;     // product + vector kernel per smoothing step (profiling build of the geometric cycle)
+    double *d_scal; // 8 scalars
+    double *d_part; // one partial per workgroup of the ordered reductions (8 · CUs)
+    double *d_ws;   // z, p, Ap, r of the solve (2n each)
+};
+
+// base[s] = first value slot of slice s (64 rows, 64 · the widest row of the slice): n_slices + 1 entries
+inline void bd_slice_table(int64_t n, const int64_t *rowptr, std::vector<int64_t> &base)
+{
+    const int64_t n_slices = (n + 63) / 64;
+    base.assign((size_t)n_slices + 1, 0);
+    for (int64_t s = 0; s < n_slices; ++s) {
+        int64_t w = 0;
+        for (int64_t r = 64 * s; r < std::min<int64_t>(n, 64 * s + 64); ++r) w = std::max(w, rowptr[r + 1] - rowptr[r]);
+        base[(size_t)s + 1] = base[(size_t)s] + 64 * w;
+    }
+}
+
+void bd_level_product(const BdCycle &cy, const BdMgLevel &L, int step, const double *x, double *y, const BdStep &st); // y = 𝒜_l x (step 0) or a fused smoother step (1, 2)
+void bd_smooth(const BdCycle &cy, BdMgLevel &L, const double *r, double *&cur, double *&other, bool from_zero);      // `degree` Chebyshev steps on B⁻¹𝒜_l
+int bd_lambda_max(const BdCycle &cy, BdMgLevel &L, const char *who, int l, double *out);                              // 1.05 × the Lanczos estimate of λmax(B⁻¹𝒜_l); reads back
+// CG on 𝒜x = b with z = ℳ⁻¹r from `cycle` (enqueue-only); `who` names the entry in the not-positive-definite report
+int bd_pcg(const BdCycle &cy, const char *who, void (*cycle)(void *ctx, const double *r, double *z), void *ctx, const double *b, double *x, double rtol, double atol, int maxiter,
+           int *iters, double *resnorm);
+void launch_bd_csr_fine(tb_bidomain *bd, double *csr);    // the block system's planes → 4 CSR planes with the elimination baked in, ground_diag on the eliminated φₑφₑ diagonals
+void launch_bd_binv_fine(tb_bidomain *bd, double *binv);  // the block system's block inverses with the ground masked
+void launch_bd_fill_sliced(tb_device *dev, const BdMgLevel &L, const int64_t *rowptr, const int32_t *colidx); // CSR planes → sliced planes, columns, block inverses
+void launch_bd_dense_inverse(tb_device *dev, int n, const int64_t *rowptr, const int32_t *colidx, int64_t nnz, const double *csr, double *C); // C = 𝒜⁻¹, n ≤ BD_COARSEST_NODES
 
 } // namespace tb

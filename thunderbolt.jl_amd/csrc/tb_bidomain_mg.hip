@@ -25,27 +25,6 @@
 #include "tb_mg_internal.hpp"
 #include "tb_reduce.hpp"
 
-namespace tb {
-
-constexpr int BDMG_COARSEST_NODES = MG_COARSEST_MAX / 2; // 512 nodes, 1 024 unknowns: the dense inverse of tb_multigrid.hip
-
-struct BdMgLevel {
-    tb_pattern *pat = nullptr;
-    int64_t n = 0, nnz = 0, n_slices = 0, entries = 0;
-    const uint8_t *ground = nullptr; // what the kernels read (finest: the block system's flags)
-    uint8_t *d_ground = nullptr;     // owned, below the finest level
-    double *d_csr = nullptr;         // 4 · nnz: planes a₁₁, a₁₂, a₂₁, a₂₂ in the pattern's CSR order, elimination baked in
-    int64_t *d_base = nullptr;       // sliced storage of the levels 1 … L−2 (the finest level's is the block system's, level 0 is inverted)
-    uint32_t *d_col = nullptr;
-    double *d_val = nullptr;         // 4 · entries
-    double *d_binv = nullptr;        // 3 n: inverse diagonal blocks, zero in the φₑ row and column of a grounded node
-    double *d_vec = nullptr;         // d | w | xt | x | r, 2n each (the Lanczos estimate of set-up borrows all five)
-    double *d = nullptr, *w = nullptr, *xt = nullptr, *x = nullptr, *r = nullptr;
-    double lmax = 0.0;
-};
-
-} // namespace tb
-
 struct tb_bidomain_mg {
     tb_bidomain *bd = nullptr;
     tb_mg *mg = nullptr;
@@ -59,6 +38,7 @@ struct tb_bidomain_mg {
     double *d_scal = nullptr;          // 8 scalars: λmax estimate, solve
     double *d_part = nullptr;          // one partial sum per workgroup of the λmax estimate's ordered reductions (8 · CUs)
     double *d_ws = nullptr;            // z, p, Ap, r of the solve (2n each)
+    tb::BdCycle cycle_record() const { return tb::BdCycle{bd, dev, degree, ratio, split, d_scal, d_part, d_ws}; }
 };
 
 namespace tb {
@@ -383,39 +363,42 @@ static void free_bdmg(tb_bidomain_mg *h)
     delete h;
 }
 
-// y = 𝒜_l x (STEP 0; DOT: xᵀy into the slot group xy) or one fused smoother step x → y (STEP 1, 2): the fine level on the block system's three planes
-// and flags, a coarse level on its four planes
-template <bool DOT, int STEP>
-static void level_product(tb_bidomain_mg *h, int l, const double *x, double *y, double *xy, const BdStep &st)
+// y = 𝒜_l x (step 0) or one fused smoother step x → y (step 1, 2): the fine level on the block system's three planes and flags, every other level on its
+// four planes
+template <int STEP>
+static void level_product_step(const BdCycle &cy, const BdMgLevel &L, const double *x, double *y, const BdStep &st)
 {
-    const BdMgLevel &L = h->lv[l];
-    if (l == (int)h->lv.size() - 1) {
-        tb_bidomain *bd = h->bd;
-        hipLaunchKernelGGL((k_bd_apply<DOT, false, STEP>), dim3((unsigned)((bd->n_slices + 3) / 4)), dim3(256), 0, h->dev->stream, bd->n, bd->n_slices, bd->d_base, bd->entries,
-                           bd->d_col, bd->d_val, bd->d_ground, bd->ground_diag, (const double2 *)x, (double2 *)y, xy, st);
+    if (L.fine) {
+        tb_bidomain *bd = cy.bd;
+        hipLaunchKernelGGL((k_bd_apply<false, false, STEP>), dim3((unsigned)((bd->n_slices + 3) / 4)), dim3(256), 0, cy.dev->stream, bd->n, bd->n_slices, bd->d_base, bd->entries,
+                           bd->d_col, bd->d_val, bd->d_ground, bd->ground_diag, (const double2 *)x, (double2 *)y, (double *)nullptr, st);
     } else
-        hipLaunchKernelGGL((k_bd_apply<DOT, true, STEP>), dim3((unsigned)((L.n_slices + 3) / 4)), dim3(256), 0, h->dev->stream, L.n, L.n_slices, L.d_base, L.entries, L.d_col,
-                           L.d_val, (const uint8_t *)nullptr, 0.0, (const double2 *)x, (double2 *)y, xy, st);
+        hipLaunchKernelGGL((k_bd_apply<false, true, STEP>), dim3((unsigned)((L.n_slices + 3) / 4)), dim3(256), 0, cy.dev->stream, L.n, L.n_slices, L.d_base, L.entries, L.d_col,
+                           L.d_val, (const uint8_t *)nullptr, 0.0, (const double2 *)x, (double2 *)y, (double *)nullptr, st);
+}
+void bd_level_product(const BdCycle &cy, const BdMgLevel &L, int step, const double *x, double *y, const BdStep &st)
+{
+    if (step == 0) level_product_step<0>(cy, L, x, y, st);
+    else if (step == 1) level_product_step<1>(cy, L, x, y, st);
+    else level_product_step<2>(cy, L, x, y, st);
 }
 
 // `degree` Chebyshev steps on B⁻¹𝒜_l for 𝒜_l x = r (the ChebSchedule of the scalar cycle's cheb_smooth), from zero or from *cur.  Fused: a step reads *cur and writes *other, then the two swap; split: product into w, vector kernel in place.
-static void smooth(tb_bidomain_mg *h, int l, const double *r, double *&cur, double *&other, bool from_zero)
+void bd_smooth(const BdCycle &cy, BdMgLevel &L, const double *r, double *&cur, double *&other, bool from_zero)
 {
-    BdMgLevel &L = h->lv[l];
-    tb_device *dev = h->dev;
+    tb_device *dev = cy.dev;
     const unsigned g = grid_for(dev, L.n, 256);
-    ChebSchedule sched(L.lmax, h->ratio);
+    ChebSchedule sched(L.lmax, cy.ratio);
     auto step = [&](bool first, ChebSchedule::Step c) {
-        if (h->split) {
-            level_product<false, 0>(h, l, cur, L.w, nullptr, BdStep());
+        if (cy.split) {
+            bd_level_product(cy, L, 0, cur, L.w, BdStep());
             if (first) hipLaunchKernelGGL(k_bdmg_cheb<1>, dim3(g), dim3(256), 0, dev->stream, L.n, c.c1, c.c2, L.d_binv, (const double2 *)r, (const double2 *)L.w, (double2 *)L.d, (double2 *)cur);
             else hipLaunchKernelGGL(k_bdmg_cheb<2>, dim3(g), dim3(256), 0, dev->stream, L.n, c.c1, c.c2, L.d_binv, (const double2 *)r, (const double2 *)L.w, (double2 *)L.d, (double2 *)cur);
             return;
         }
         BdStep st;
         st.c1 = c.c1; st.c2 = c.c2; st.binv = L.d_binv; st.r = (const double2 *)r; st.d = (double2 *)L.d;
-        if (first) level_product<false, 1>(h, l, cur, other, nullptr, st);
-        else level_product<false, 2>(h, l, cur, other, nullptr, st);
+        bd_level_product(cy, L, first ? 1 : 2, cur, other, st);
         std::swap(cur, other);
     };
     if (from_zero)
@@ -423,7 +406,7 @@ static void smooth(tb_bidomain_mg *h, int l, const double *r, double *&cur, doub
                            (double2 *)cur);
     else
         step(true, sched.first());
-    for (int k = 1; k < h->degree; ++k) step(false, sched.next());
+    for (int k = 1; k < cy.degree; ++k) step(false, sched.next());
 }
 
 // x = ℳ_l⁻¹ r: V(degree, degree) from x = 0; enqueues only.  The fused smoother swaps its two buffers 2·degree − 1 times on a level, so it starts in the
@@ -432,6 +415,7 @@ static void cycle(tb_bidomain_mg *h, int l, const double *r, double *x)
 {
     tb_device *dev = h->dev;
     BdMgLevel &L = h->lv[l];
+    const BdCycle cy = h->cycle_record();
     if (l == 0) {
         launch_dense_apply(dev, (int)(2 * L.n), h->d_cinv, r, x);
         return;
@@ -439,26 +423,25 @@ static void cycle(tb_bidomain_mg *h, int l, const double *r, double *x)
     BdMgLevel &Cl = h->lv[l - 1];
     const MgLevel &T = h->mg->lv[l]; // the transfer plans between l and l − 1
     double *cur = h->split ? x : L.xt, *other = h->split ? L.xt : x;
-    smooth(h, l, r, cur, other, true);
-    level_product<false, 0>(h, l, cur, L.w, nullptr, BdStep());
+    bd_smooth(cy, L, r, cur, other, true);
+    bd_level_product(cy, L, 0, cur, L.w, BdStep());
     hipLaunchKernelGGL(k_bdmg_restrict, dim3(blocks_of(Cl.n, 256)), dim3(256), 0, dev->stream, Cl.n, T.d_rptr, T.d_rcol, T.d_rexp, (const double2 *)r, (const double2 *)L.w, L.ground,
                        Cl.ground, (double2 *)Cl.r);
     cycle(h, l - 1, Cl.r, Cl.x);
     hipLaunchKernelGGL(k_bdmg_prolong_add, dim3(blocks_of(L.n, 256)), dim3(256), 0, dev->stream, L.n, T.d_pptr, T.d_pcol, T.d_pexp, (const double2 *)Cl.x, L.ground, Cl.ground,
                        (double2 *)cur);
-    smooth(h, l, r, cur, other, false);
+    bd_smooth(cy, L, r, cur, other, false);
 }
 
 // λmax(B⁻¹𝒜_l): the largest Ritz value of 24 Lanczos steps in the B inner product (it converges from below), inflated by 5 % — the recipe of
 // estimate_lambda_max; its Gershgorin cap has no cheap counterpart for 2 × 2 blocks (a bound needs the norms of B_i^-½ 𝒜_ij B_j^-½) and is left out.
 // With t = B⁻¹s: β² = tᵀs, v = t/β, u = s/β = B v;  s ← 𝒜v − αu − βu₋₁, α = vᵀ𝒜v.  Reads scalars back.
-static int lambda_max(tb_bidomain_mg *h, int l, double *out)
+int bd_lambda_max(const BdCycle &cy, BdMgLevel &L, const char *who, int l, double *out)
 {
-    tb_device *dev = h->dev;
-    BdMgLevel &L = h->lv[l];
+    tb_device *dev = cy.dev;
     constexpr int KL = 24;
     const unsigned g = grid_for(dev, L.n, 256);
-    double *v = L.d, *s = L.w, *t = L.xt, *u = L.x, *up = L.r, *S = h->d_scal, *part = h->d_part;
+    double *v = L.d, *s = L.w, *t = L.xt, *u = L.x, *up = L.r, *S = cy.d_scal, *part = cy.d_part;
     double al[KL], be[KL + 1], hh[1];
     auto fold = [&](double *out) { launch_fold_sum(dev, (int)g, part, out); };
     hipLaunchKernelGGL(k_bdmg_lanczos_start, dim3(g), dim3(256), 0, dev->stream, L.n, L.d_binv, L.ground, (double2 *)s, (double2 *)t, part);
@@ -471,7 +454,7 @@ static int lambda_max(tb_bidomain_mg *h, int l, double *out)
         for (int k = 0; k < KL; ++k) {
             hipLaunchKernelGGL(k_bdmg_lanczos_scale, dim3(g), dim3(256), 0, dev->stream, L.n, 1.0 / beta, (const double2 *)t, (const double2 *)s, (double2 *)v, (double2 *)up);
             std::swap(u, up); // u = B v; up: the previous one
-            level_product<false, 0>(h, l, v, s, nullptr, BdStep()); // s = 𝒜 v
+            bd_level_product(cy, L, 0, v, s, BdStep()); // s = 𝒜 v
             hipLaunchKernelGGL(k_bdmg_dot_partial, dim3(g), dim3(256), 0, dev->stream, L.n, (const double2 *)v, (const double2 *)s, part); // α = vᵀ𝒜v, ordered (the fused sum of
             fold(S);                                                                                                                    // k_bd_apply<true> is not, above 64 workgroups)
             TB_TRY(read_back(dev, hh, S, 1));
@@ -486,21 +469,21 @@ static int lambda_max(tb_bidomain_mg *h, int l, double *out)
         }
     }
     TB_HIP(hipGetLastError());
-    if (kdone == 0) { set_error("tb_bidomain_mg_setup: the λmax estimate of level %d found no start vector (non-finite operator?)", l); return TB_ERR_BAD_ARG; }
+    if (kdone == 0) { set_error("%s: the λmax estimate of level %d found no start vector (non-finite operator?)", who, l); return TB_ERR_BAD_ARG; }
     *out = 1.05 * largest_tridiagonal_eigenvalue(al, be, kdone);
     return TB_OK;
 }
 
 // CG on 𝒜x = b with z = ℳ⁻¹r from one cycle: the loop of pcg_loop (tb_krylov.hip) with the slot groups of tb_bidomain_solve — r·z in the ring 4, 5, 6,
 // pᵀ𝒜p in 3, r·r in 7, folded into S[3] for the look (S[4]: the sticky flag); a look at every iteration up to the 64th and at every fourth from there
-static int bdmg_pcg(tb_bidomain_mg *h, const double *b, double *x, double rtol, double atol, int maxiter, int *iters, double *resnorm)
+int bd_pcg(const BdCycle &cy, const char *who, void (*cycle)(void *ctx, const double *r, double *z), void *ctx, const double *b, double *x, double rtol, double atol, int maxiter,
+           int *iters, double *resnorm)
 {
-    tb_bidomain *bd = h->bd;
-    tb_device *dev = h->dev;
+    tb_bidomain *bd = cy.bd;
+    tb_device *dev = cy.dev;
     TB_NO_CAPTURE(dev); // reads scalars back (convergence looks)
     const int64_t n2 = 2 * bd->n;
-    const int top = (int)h->lv.size() - 1;
-    double *z = h->d_ws, *p = z + n2, *Ap = p + n2, *r = Ap + n2, *S = h->d_scal, *const g_pap = red_group(dev, 3), *const g_rr = red_group(dev, 7);
+    double *z = cy.d_ws, *p = z + n2, *Ap = p + n2, *r = Ap + n2, *S = cy.d_scal, *const g_pap = red_group(dev, 3), *const g_rr = red_group(dev, 7);
     auto g_rz = [&](int k) { return red_group(dev, 4 + k); };
     const unsigned g = grid_for(dev, n2, 256);
     TB_HIP(hipMemsetAsync(p, 0, sizeof(double) * n2, dev->stream)); // the first direction is p = z + 0·p
@@ -519,7 +502,7 @@ static int bdmg_pcg(tb_bidomain_mg *h, const double *b, double *x, double rtol, 
         const int look_every = it >= 64 ? 4 : 1;
         for (int s2 = 0; s2 < look_every && it < maxiter; ++s2, ++it) {
             const int nxt = (cur + 1) % 3, ret = (cur + 2) % 3;
-            cycle(h, top, r, z);
+            cycle(ctx, r, z);
             hipLaunchKernelGGL(k_bdmg_dot, dim3(g), dim3(256), 0, dev->stream, n2, (const double *)r, (const double *)z, g_rz(nxt));
             hipLaunchKernelGGL(k_bdmg_direction, dim3(g), dim3(256), 0, dev->stream, n2, (const double *)g_rz(cur), (const double *)g_rz(nxt), g_rz(ret), g_pap, (const double *)z, p);
             enqueue_apply<true>(bd, p, Ap, g_pap);
@@ -531,7 +514,7 @@ static int bdmg_pcg(tb_bidomain_mg *h, const double *b, double *x, double rtol, 
         }
         TB_TRY(read_back(dev, hh, S + 3, 2));
         if (hh[1] != 0.0) {
-            set_error("tb_bidomain_mg_solve: matrix or multigrid preconditioner is not positive definite (pᵀAp = %g)", hh[1] == -1e-300 ? 0.0 : hh[1]);
+            set_error("%s: matrix or multigrid preconditioner is not positive definite (pᵀAp = %g)", who, hh[1] == -1e-300 ? 0.0 : hh[1]);
             rc = TB_ERR_BAD_ARG;
             break;
         }
@@ -543,6 +526,35 @@ static int bdmg_pcg(tb_bidomain_mg *h, const double *b, double *x, double rtol, 
     if (iters) *iters = it;
     if (resnorm) *resnorm = rnorm;
     return TB_OK;
+}
+
+static void geometric_cycle(void *ctx, const double *r, double *z)
+{
+    tb_bidomain_mg *h = (tb_bidomain_mg *)ctx;
+    cycle(h, (int)h->lv.size() - 1, r, z);
+}
+
+// ---- enqueue-only launchers of the kernels the algebraic block cycle (tb_bidomain_amg.hip) shares
+void launch_bd_csr_fine(tb_bidomain *bd, double *csr)
+{
+    tb_pattern *pat = bd->pat;
+    hipStream_t st = pat->mesh->dev->stream;
+    const unsigned gn = blocks_of(bd->n, 256);
+    hipLaunchKernelGGL(k_bdmg_csr_fine, dim3(gn), dim3(256), 0, st, bd->n, bd->d_base, bd->entries, bd->d_col, bd->d_val, bd->d_ground, pat->d_rowptr, pat->nnz, csr);
+    hipLaunchKernelGGL(k_bdmg_set_ground_diag, dim3(gn), dim3(256), 0, st, bd->n, pat->d_rowptr, pat->d_colidx, bd->d_ground, bd->ground_diag, csr + 3 * pat->nnz);
+}
+void launch_bd_binv_fine(tb_bidomain *bd, double *binv)
+{
+    hipLaunchKernelGGL(k_bdmg_binv_fine, dim3(blocks_of(bd->n, 256)), dim3(256), 0, bd->pat->mesh->dev->stream, bd->n, bd->d_binv, bd->d_ground, binv);
+}
+void launch_bd_fill_sliced(tb_device *dev, const BdMgLevel &L, const int64_t *rowptr, const int32_t *colidx)
+{
+    hipLaunchKernelGGL(k_bdmg_fill_sliced, dim3(blocks_of(L.n_slices * 64, 256)), dim3(256), 0, dev->stream, L.n, L.n_slices, L.d_base, L.entries, rowptr, colidx, L.nnz, L.d_csr,
+                       L.ground, L.d_col, L.d_val, L.d_binv);
+}
+void launch_bd_dense_inverse(tb_device *dev, int n, const int64_t *rowptr, const int32_t *colidx, int64_t nnz, const double *csr, double *C)
+{
+    hipLaunchKernelGGL(k_bdmg_dense_inverse, dim3(1), dim3(1024), 0, dev->stream, n, rowptr, colidx, nnz, csr, C);
 }
 
 } // namespace tb
@@ -579,9 +591,9 @@ int tb_bidomain_mg_create(tb_bidomain *bd, tb_mg *mg, tb_bidomain_mg **out)
     }
     TB_REQUIRE(mg->lv.back().h_presc.empty(), "tb_bidomain_mg_create: the hierarchy has prescribed dofs (tb_mg_set_prescribed): the block cycle runs on its unflagged plans, the ground "
                                               "comes from tb_bidomain_set_matrices");
-    if (mg->lv[0].pat->n_rows > BDMG_COARSEST_NODES) {
+    if (mg->lv[0].pat->n_rows > BD_COARSEST_NODES) {
         set_error("tb_bidomain_mg_create: the coarsest level has %lld nodes (%lld unknowns); its dense inverse takes at most %d nodes - add a level",
-                  (long long)mg->lv[0].pat->n_rows, 2 * (long long)mg->lv[0].pat->n_rows, BDMG_COARSEST_NODES);
+                  (long long)mg->lv[0].pat->n_rows, 2 * (long long)mg->lv[0].pat->n_rows, BD_COARSEST_NODES);
         return TB_ERR_UNSUPPORTED;
     }
     TB_HIP(hipSetDevice(dev->id));
@@ -598,6 +610,7 @@ int tb_bidomain_mg_create(tb_bidomain *bd, tb_mg *mg, tb_bidomain_mg **out)
         TB_HIP(hipMalloc((void **)&L.d_csr, sizeof(double) * 4 * (size_t)std::max<int64_t>(L.nnz, 1)));
         TB_HIP(hipMalloc((void **)&L.d_vec, sizeof(double) * 10 * (size_t)L.n));
         L.d = L.d_vec; L.w = L.d + 2 * L.n; L.xt = L.w + 2 * L.n; L.x = L.xt + 2 * L.n; L.r = L.x + 2 * L.n;
+        L.fine = l == nl - 1;
         if (l == nl - 1) L.ground = bd->d_ground;
         else {
             TB_HIP(hipMalloc((void **)&L.d_ground, (size_t)L.n));
@@ -607,12 +620,8 @@ int tb_bidomain_mg_create(tb_bidomain *bd, tb_mg *mg, tb_bidomain_mg **out)
         TB_HIP(hipMalloc((void **)&L.d_binv, sizeof(double) * 3 * (size_t)L.n));
         if (l == nl - 1) continue; // the block system's own sliced planes
         L.n_slices = (L.n + 63) / 64;
-        std::vector<int64_t> base((size_t)L.n_slices + 1, 0);
-        for (int64_t s = 0; s < L.n_slices; ++s) {
-            int64_t w = 0;
-            for (int64_t r = 64 * s; r < std::min<int64_t>(L.n, 64 * s + 64); ++r) w = std::max(w, pat->h_rowptr[r + 1] - pat->h_rowptr[r]);
-            base[s + 1] = base[s] + 64 * w;
-        }
+        std::vector<int64_t> base;
+        bd_slice_table(L.n, pat->h_rowptr.data(), base);
         L.entries = base.back();
         TB_TRY(upload(dev, base, &L.d_base));
         TB_HIP(hipMalloc((void **)&L.d_col, std::max<size_t>(1, (size_t)L.entries) * sizeof(uint32_t)));
@@ -671,7 +680,7 @@ int tb_bidomain_mg_setup(tb_bidomain_mg *h, int degree, double interval_ratio)
             hipLaunchKernelGGL(k_bdmg_fill_sliced, dim3(blocks_of(L.n_slices * 64, 256)), dim3(256), 0, dev->stream, L.n, L.n_slices, L.d_base, L.entries, L.pat->d_rowptr,
                                L.pat->d_colidx, L.nnz, L.d_csr, L.ground, L.d_col, L.d_val, L.d_binv);
         TB_HIP(hipGetLastError());
-        TB_TRY(lambda_max(h, l, &L.lmax));
+        TB_TRY(bd_lambda_max(h->cycle_record(), L, "tb_bidomain_mg_setup", l, &L.lmax));
     }
     BdMgLevel &C0 = h->lv[0];
     hipLaunchKernelGGL(k_bdmg_dense_inverse, dim3(1), dim3(1024), 0, dev->stream, (int)C0.n, C0.pat->d_rowptr, C0.pat->d_colidx, C0.nnz, C0.d_csr, h->d_cinv);
@@ -738,7 +747,7 @@ int tb_bidomain_mg_solve(tb_bidomain_mg *h, const double *d_b, double *d_x, doub
     TB_REQUIRE(d_b != d_x, "tb_bidomain_mg_solve: b and x alias");
     BD_ALIGNED(d_b, "tb_bidomain_mg_solve"); BD_ALIGNED(d_x, "tb_bidomain_mg_solve");
     TB_HIP(hipSetDevice(h->dev->id));
-    return bdmg_pcg(h, d_b, d_x, rtol, atol, maxiter, iters, resnorm);
+    return bd_pcg(h->cycle_record(), "tb_bidomain_mg_solve", geometric_cycle, h, d_b, d_x, rtol, atol, maxiter, iters, resnorm);
 }
 
 } // extern "C"
