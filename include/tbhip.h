@@ -205,6 +205,8 @@ const char *tb_version(void);
  * template).
  * Added under 10, purely additive: tb_amg_*, tb_pcg_solve_amg, tb_mg_set_coarse_amg, tb_mg_coarse_amg (smoothed-aggregation algebraic multigrid).
  * Added under 10, purely additive: tb_bidomain_amg_* (smoothed-aggregation multigrid preconditioner of the bidomain block system: block V-cycle from the matrix alone).
+ * Added under 10, purely additive: tb_amg_set_near_nullspace, tb_amg_level_nodes, tb_amg_level_near_nullspace, tb_amg_level_tentative, tb_amg_level_dead,
+ * tb_mg_set_coarse_amg_near_nullspace (node-wise aggregation with rigid-body modes for elasticity); without them tb_amg_* behaves bit for bit as before.
  * A host binding compares tb_abi_revision() with the
  * TB_ABI_REVISION it was written against and refuses to run on a mismatch (julia/ThunderboltHIPBackend.jl does, in __init__) */
 #define TB_ABI_REVISION 10
@@ -995,7 +997,39 @@ int tb_pcg_solve_mg(tb_pattern *pat, const double *d_Anz, const double *d_b, dou
  *                       the components of the level-0 field, degree and interval_ratio those of tb_mg_setup, which sets the AMG up after the Galerkin
  *                       chain.  Call it before tb_mg_setup; without it tb_mg_* behaves bit for bit as before.
  *   tb_mg_coarse_amg    that hierarchy, for the inspectors (after one tb_mg_setup; NULL without tb_mg_set_coarse_amg).  The tb_mg owns it: it is not to be
- *                       set up, re-planned or destroyed by the caller, and a new plan of the tb_mg replaces it. */
+ *                       set up, re-planned or destroyed by the caller, and a new plan of the tb_mg replaces it.
+ * With a near-null-space (tb_amg_set_near_nullspace; tb_amg_block.hip): node-wise smoothed aggregation with k ≤ 6 candidate vectors, after Vaněk–Mandel–
+ * Brezina — for elasticity the six rigid-body modes, of which the method above carries the three translations only.  Per level l; level 0 has 3 dofs per
+ * node in any numbering, described by a dof → node map; every level below has k dofs per node, node = aggregate of the level above, numbered
+ * k·a … k·a + k − 1:
+ *   1 candidates   B_l is n_l × k.  A dof whose row has no non-zero off-diagonal entry is an eliminated Dirichlet dof: its row of B_l is set to zero.  Decided
+ *                  per dof: symmetry and roller conditions eliminate one component of a node and leave the node in its aggregate.
+ *   2 strength     s_IJ = Frobenius norm of the block of entries of A_l between nodes I and J, the squares summed in stored row-major order (rows of I in
+ *                  ascending dof order).  Criterion and symmetrisation as above on the node graph: strong from I iff m_I = max over J ≠ I of s_IJ > 0 and
+ *                  s_IJ ≥ θ·m_I; the flag is strong from I or from J.  No component labels.
+ *   3 aggregation  the three host passes above, unchanged, on the node graph; a node without a strong neighbour stays outside every aggregate.
+ *   4 tentative    device.  Per aggregate a the rows of B_l of its dofs in ascending dof order (B_a, m_a × k) are orthonormalised by modified Gram–Schmidt,
+ *                  columns in order, R_jj > 0: B_a = Q_a R_a.  A column is dead when its norm after orthogonalisation is ≤ 1e-8 × its norm before (a pair
+ *                  of nodes has one: its rotation about the joining axis vanishes; a single node has three): a zero column of Q_a with R_jj = 0; the
+ *                  projections R_ij (i < j) already taken are kept, so T_l B_{l+1} = B_l holds for dead columns too.  T_l has Q_a in rows(a) × columns
+ *                  (k·a …); B_{l+1} has R_a in rows k·a ….  Every dot product is a sum of 64 lane sums in stride order folded by a fixed butterfly.
+ *   5 prolongator  P = T − ω D⁻¹ A T, ω = 4 / (3 λ), on rows of aggregated nodes only and on the planned pattern of A·T (k columns per aggregate met in
+ *                  the row); R = Pᵀ; A_c = R (A P) by the products above on planned patterns.
+ *   6 dead dofs    the diagonal of A_c at a dead coarse dof is set to 1; its row and column are zero otherwise: neither the smoother nor the dense inverse
+ *                  of the last level sees a singular row.
+ *   7 the rest     λ per level, the V(degree, degree) cycle, the dense last level, the enqueue-only tb_amg_apply, no floating-point atomics, the same bits
+ *                  from two set-ups and two applications: as above.  Coarsening also stops when k × aggregates ≥ n_l.
+ * Steps 1 – 4 belong to the planning set-up (the first tb_amg_setup and any after tb_amg_replan): B and the aggregates depend on geometry and the first
+ * matrix only; every later tb_amg_setup redoes steps 5 – 7 on the same T.
+ *   tb_amg_set_near_nullspace  host arrays: the node of every dof (n_nodes nodes of 3 dofs each) and B, row-major n × k.  Before the first set-up or after
+ *                       tb_amg_replan.  TB_ERR_BAD_ARG with a message: k outside 1..6, a node with other than 3 dofs, node ids out of range, a non-finite
+ *                       B, a planned hierarchy.  The component labels of tb_amg_create are dropped.
+ *   inspectors (host outputs, after one setup, on a hierarchy with a near-null-space): tb_amg_level_nodes (node count and the node of every dof);
+ *                       tb_amg_level_near_nullspace (k, and B_l with its zeroed rows, n_l × k); tb_amg_level_tentative (T_l, dense n_l × k; not on the
+ *                       last level); tb_amg_level_dead (one byte per dof of level l + 1; not on the last level).  On such a hierarchy
+ *                       tb_amg_level_aggregates returns the aggregate of each dof's node and tb_amg_level_strength, per non-zero of A_l, the flag of its
+ *                       node pair (0 inside a node).
+ *   tb_mg_set_coarse_amg_near_nullspace  stores the arrays for the AMG that tb_mg_setup creates on level 0 (after tb_mg_set_coarse_amg, before tb_mg_setup). */
 typedef struct tb_amg tb_amg;
 int tb_amg_create(tb_pattern *pat, const int8_t *comp_host, double theta, int max_coarse, int max_levels, tb_amg **out);
 int tb_amg_setup(tb_amg *amg, const double *d_Anz, int degree, double interval_ratio);
@@ -1013,6 +1047,12 @@ int tb_amg_level_strength(tb_amg *amg, int level, uint8_t *flags);
 int tb_amg_level_lambda_max(tb_amg *amg, int level, double *lmax);
 int tb_mg_set_coarse_amg(tb_mg *mg, double theta, int max_coarse, int max_levels);
 int tb_mg_coarse_amg(tb_mg *mg, tb_amg **out);
+int tb_amg_set_near_nullspace(tb_amg *amg, int64_t n_nodes, const int32_t *node_of_dof, int k, const double *B);
+int tb_amg_level_nodes(tb_amg *amg, int level, int64_t *n_nodes, int32_t *node_of_dof);
+int tb_amg_level_near_nullspace(tb_amg *amg, int level, int *k, double *B);
+int tb_amg_level_tentative(tb_amg *amg, int level, double *T);
+int tb_amg_level_dead(tb_amg *amg, int level, uint8_t *dead);
+int tb_mg_set_coarse_amg_near_nullspace(tb_mg *mg, int64_t n_nodes, const int32_t *node_of_dof, int k, const double *B);
 
 /* ------------------------------------------------------------------ parabolic-elliptic bidomain block system (tb_bidomain.hip)
  * ParabolicEllipticBidomainModel (src/modeling/electrophysiology.jl:305-326, declared "Not implemented yet" there).  Backward Euler on the transformed

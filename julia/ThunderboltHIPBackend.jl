@@ -822,6 +822,37 @@ function amg_lambda_max(amg::HIPAMGPrecon, level::Integer)
     check(ccall((:tb_amg_level_lambda_max, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ref{Cdouble}), amg.handle, level, r))
     return r[]
 end
+# Near-null-space of k ≤ 6 candidates on node blocks (rigid-body modes for elasticity): `node_of_dof` 0-based, 3 dofs per node; `B` is ndofs × k and is
+# handed over row-major.  Before the first setup! or after replan!.
+function set_near_nullspace!(amg::HIPAMGPrecon, n_nodes::Integer, node_of_dof::Vector{Int32}, B::Matrix{Float64})
+    Bt = permutedims(B)
+    check(ccall((:tb_amg_set_near_nullspace, libtbhip), Cint, (Ptr{Cvoid}, Int64, Ptr{Int32}, Cint, Ptr{Float64}), amg.handle, n_nodes, node_of_dof, size(B, 2), Bt))
+end
+function amg_level_nodes(amg::HIPAMGPrecon, level::Integer)
+    nn = Ref{Int64}(0)
+    node = Vector{Int32}(undef, amg_level_size(amg, level)[1])
+    check(ccall((:tb_amg_level_nodes, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ref{Int64}, Ptr{Int32}), amg.handle, level, nn, node))
+    return nn[], node
+end
+# B_l (k × n_l: the columns are the dofs' rows of the row-major n_l × k array), rows of eliminated dofs zeroed
+function amg_level_near_nullspace(amg::HIPAMGPrecon, level::Integer)
+    k = Ref{Cint}(0)
+    check(ccall((:tb_amg_level_near_nullspace, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ref{Cint}, Ptr{Float64}), amg.handle, level, k, Ptr{Float64}(C_NULL)))
+    B = Matrix{Float64}(undef, Int(k[]), amg_level_size(amg, level)[1])
+    check(ccall((:tb_amg_level_near_nullspace, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ref{Cint}, Ptr{Float64}), amg.handle, level, k, B))
+    return B
+end
+# the tentative prolongator T_l, dense, as k × n_l (row i of the row-major array lies in the column block of its node's aggregate)
+function amg_level_tentative(amg::HIPAMGPrecon, level::Integer, k::Integer)
+    T = Matrix{Float64}(undef, k, amg_level_size(amg, level)[1])
+    check(ccall((:tb_amg_level_tentative, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), amg.handle, level, T))
+    return T
+end
+function amg_level_dead(amg::HIPAMGPrecon, level::Integer)
+    dead = Vector{UInt8}(undef, amg_level_size(amg, level + 1)[1])
+    check(ccall((:tb_amg_level_dead, libtbhip), Cint, (Ptr{Cvoid}, Cint, Ptr{UInt8}), amg.handle, level, dead))
+    return dead
+end
 # KrylovMGSolver(CG, amg): rebuild the numeric phase from the matrix, then CG with one cycle per iteration
 function pcg_amg!(x::HIPVector{Float64}, A::HIPSparseMatrixCSR{Float64}, b::HIPVector{Float64}, amg::HIPAMGPrecon; rtol = 1e-5, atol = 1e-6, maxiter = 1000, setup = true)
     setup && setup!(amg, A)
@@ -834,6 +865,10 @@ end
 # coarse_amg returns that hierarchy's handle for the amg_* inspectors (owned by the HIPGMGPrecon)
 set_coarse_amg!(mg::HIPGMGPrecon; theta = 0.25, max_coarse = 1024, max_levels = 16) =
     check(ccall((:tb_mg_set_coarse_amg, libtbhip), Cint, (Ptr{Cvoid}, Cdouble, Cint, Cint), mg.handle, theta, max_coarse, max_levels))
+function set_coarse_amg_near_nullspace!(mg::HIPGMGPrecon, n_nodes::Integer, node_of_dof::Vector{Int32}, B::Matrix{Float64})
+    Bt = permutedims(B)
+    check(ccall((:tb_mg_set_coarse_amg_near_nullspace, libtbhip), Cint, (Ptr{Cvoid}, Int64, Ptr{Int32}, Cint, Ptr{Float64}), mg.handle, n_nodes, node_of_dof, size(B, 2), Bt))
+end
 function coarse_amg(mg::HIPGMGPrecon)
     h = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:tb_mg_coarse_amg, libtbhip), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), mg.handle, h))

@@ -179,7 +179,9 @@ class BidomainAMGPrecon:
     arguments with nodes in the place of dofs.  The last level is inverted densely: at most 512 nodes (1 024 unknowns); the default of 128 keeps the
     one-workgroup dense inverse from dominating the numeric set-up."""
 
-    def __init__(self, theta=0.25, degree=2, interval_ratio=4.0, max_coarse=128, max_levels=16, cycle="V", smoother="chebyshev"):
+    def __init__(self, theta=0.25, degree=2, interval_ratio=4.0, max_coarse=128, max_levels=16, cycle="V", smoother="chebyshev", near_nullspace=None):
+        if near_nullspace is not None:
+            raise NotImplementedError("BidomainAMGPrecon: a near_nullspace is out of scope for the block system (its fields are scalar: the constant is their near-null space)")
         if cycle != "V":
             raise NotImplementedError("BidomainAMGPrecon: V-cycles only (W- and F-cycles are out of scope)")
         if smoother != "chebyshev":
@@ -318,6 +320,8 @@ class BidomainBackwardEulerStage:
                 raise NotImplementedError("BidomainBackwardEulerStage: %s is out of scope - the block system is first order, pass GMGPrecon(gh)" % type(precond).__name__)
             if isinstance(precond, AMGPrecon):
                 raise NotImplementedError("BidomainBackwardEulerStage: the scalar AMGPrecon is out of scope for the block system - pass BidomainAMGPrecon(...)")
+            if getattr(getattr(precond, "coarse", None), "near_nullspace", None) is not None:
+                raise NotImplementedError("BidomainBackwardEulerStage: a near_nullspace is out of scope for the block system (its fields are scalar)")
             if not isinstance(precond, (GMGPrecon, BidomainAMGPrecon)):
                 raise NotImplementedError("BidomainBackwardEulerStage: precond is None (block-Jacobi) or GMGPrecon(gh); %r is out of scope" % (precond,))
             precond.check(dh)

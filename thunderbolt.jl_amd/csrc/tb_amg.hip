@@ -240,6 +240,7 @@ static void free_dev(T *&p)
 static void free_level(AmgLevel &L)
 {
     L.release();
+    amg_block_free_level(L);
     free_dev(L.d_rowptr); free_dev(L.d_colidx); free_dev(L.d_A); free_dev(L.d_comp); free_dev(L.d_diag); free_dev(L.d_strength);
     free_dev(L.d_agg); free_dev(L.d_tval); free_dev(L.d_pptr); free_dev(L.d_pcol); free_dev(L.d_prow); free_dev(L.d_P); free_dev(L.d_rptr); free_dev(L.d_rcol);
     free_dev(L.d_rperm); free_dev(L.d_R); free_dev(L.d_apptr); free_dev(L.d_apcol); free_dev(L.d_aprow); free_dev(L.d_AP); free_dev(L.d_crow);
@@ -325,22 +326,24 @@ static int plan_level_below(tb_amg *amg, int l, bool *coarsened)
     const int64_t n = amg->lv[(size_t)l].n, nnz = amg->lv[(size_t)l].nnz;
     {
         AmgLevel &L = amg->lv[(size_t)l];
-        if (!L.d_strength) TB_HIP(hipMalloc((void **)&L.d_strength, (size_t)std::max<int64_t>(nnz, 1)));
-        hipLaunchKernelGGL(k_amg_rowmax, dim3(blocks_of(n, 256)), dim3(256), 0, dev->stream, n, L.rowptr, L.colidx, L.A, (const int8_t *)L.d_comp, L.w);
-        hipLaunchKernelGGL(k_amg_strength, dim3(blocks_of(n, 256)), dim3(256), 0, dev->stream, n, L.rowptr, L.colidx, L.A, (const int8_t *)L.d_comp, (const double *)L.w,
-                           amg->theta, L.d_strength);
-        L.h_strength.resize((size_t)nnz);
-        TB_HIP(hipMemcpyAsync(L.h_strength.data(), L.d_strength, (size_t)nnz, hipMemcpyDeviceToHost, dev->stream));
-        TB_SYNC_STREAM(dev);
-        free_dev(L.d_strength);
-        const int64_t *hp = l == 0 ? amg->pat->h_rowptr.data() : L.h_rowptr.data();
-        const int32_t *hc = l == 0 ? amg->pat->h_colidx.data() : L.h_colidx.data();
-        amgplan::plan_level(n, hp, hc, L.h_comp.empty() ? nullptr : L.h_comp.data(), L.h_strength.data(), L.plan);
+        if (amg->nns_k) TB_TRY(amg_block_plan(amg, l)); // node strength, node aggregates, k columns per aggregate
+        else {
+            if (!L.d_strength) TB_HIP(hipMalloc((void **)&L.d_strength, (size_t)std::max<int64_t>(nnz, 1)));
+            launch_amg_strength(dev, n, L.rowptr, L.colidx, L.A, (const int8_t *)L.d_comp, amg->theta, L.w, L.d_strength);
+            L.h_strength.resize((size_t)nnz);
+            TB_HIP(hipMemcpyAsync(L.h_strength.data(), L.d_strength, (size_t)nnz, hipMemcpyDeviceToHost, dev->stream));
+            TB_SYNC_STREAM(dev);
+            free_dev(L.d_strength);
+            const int64_t *hp = l == 0 ? amg->pat->h_rowptr.data() : L.h_rowptr.data();
+            const int32_t *hc = l == 0 ? amg->pat->h_colidx.data() : L.h_colidx.data();
+            amgplan::plan_level(n, hp, hc, L.h_comp.empty() ? nullptr : L.h_comp.data(), L.h_strength.data(), L.plan);
+        }
         ++amg->aggregations;
         if (L.plan.nc <= 0 || L.plan.nc >= n) { L.plan = amgplan::LevelPlan(); L.plan.n = n; return TB_OK; }
         amgplan::LevelPlan &p = L.plan;
-        std::vector<double> tval((size_t)p.nc);
-        for (int64_t J = 0; J < p.nc; ++J) tval[(size_t)J] = 1.0 / std::sqrt((double)p.agg_size[(size_t)J]);
+        std::vector<double> tval(amg->nns_k ? 0 : (size_t)p.nc);
+        for (size_t J = 0; J < tval.size(); ++J) tval[J] = 1.0 / std::sqrt((double)p.agg_size[J]);
+        if (amg->nns_k) TB_TRY(amg_block_tentative(amg, l)); // T, B_{l+1} and the dead flags instead of one constant per aggregate
         TB_TRY(upload_all(dev, p.agg, &L.d_agg, tval, &L.d_tval, p.p_ptr, &L.d_pptr, p.p_col, &L.d_pcol, p.p_row, &L.d_prow, p.r_ptr, &L.d_rptr, p.r_col, &L.d_rcol,
                           p.r_perm, &L.d_rperm, p.ap_ptr, &L.d_apptr, p.ap_col, &L.d_apcol, p.ap_row, &L.d_aprow, p.c_row, &L.d_crow));
         L.pnnz = (int64_t)p.p_col.size();
@@ -358,6 +361,13 @@ static int plan_level_below(tb_amg *amg, int l, bool *coarsened)
     N.h_rowptr.swap(p.c_ptr);
     N.h_colidx.swap(p.c_col);
     N.h_comp = L.h_comp.empty() ? std::vector<int8_t>() : p.ccomp;
+    if (amg->nns_k) { // node = aggregate of this level, dofs k·a … k·a + k − 1; the candidates are the R factors
+        N.n_nodes = p.nc / amg->nns_k;
+        N.h_node.resize((size_t)N.n);
+        for (int64_t i = 0; i < N.n; ++i) N.h_node[(size_t)i] = (int32_t)(i / amg->nns_k);
+        N.d_B = L.d_Bc;
+        L.d_Bc = nullptr;
+    }
     TB_TRY(upload_all(dev, N.h_rowptr, &N.d_rowptr, N.h_colidx, &N.d_colidx, N.h_comp, &N.d_comp, p.c_diag, &N.d_diag));
     TB_HIP(hipMalloc((void **)&N.d_A, sizeof(double) * (size_t)std::max<int64_t>(N.nnz, 1)));
     N.rowptr = N.d_rowptr; N.colidx = N.d_colidx; N.A = N.d_A;
@@ -368,6 +378,13 @@ static int plan_level_below(tb_amg *amg, int l, bool *coarsened)
     std::vector<int32_t>().swap(p.r_col); std::vector<int64_t>().swap(p.r_ptr); std::vector<int32_t>().swap(p.p_row);
     *coarsened = true;
     return TB_OK;
+}
+
+void launch_amg_strength(tb_device *dev, int64_t n, const int64_t *rowptr, const int32_t *colidx, const double *val, const int8_t *comp, double theta, double *m,
+                         uint8_t *flag)
+{
+    hipLaunchKernelGGL(k_amg_rowmax, dim3(blocks_of(n, 256)), dim3(256), 0, dev->stream, n, rowptr, colidx, val, comp, m);
+    hipLaunchKernelGGL(k_amg_strength, dim3(blocks_of(n, 256)), dim3(256), 0, dev->stream, n, rowptr, colidx, val, comp, (const double *)m, theta, flag);
 }
 
 void launch_amg_spgemm(tb_device *dev, int64_t cnnz, const int32_t *crow, const int32_t *ccol, const int64_t *aptr, const int32_t *acol, const double *aval, const int64_t *bptr,
@@ -382,12 +399,15 @@ static int launch_level_numeric(tb_amg *amg, int l)
     tb_device *dev = amg->dev;
     AmgLevel &L = amg->lv[(size_t)l], &N = amg->lv[(size_t)l + 1];
     const double omega = 4.0 / (3.0 * L.lmax);
-    hipLaunchKernelGGL(k_amg_smooth_p, dim3(blocks_of(L.pnnz, 256)), dim3(256), 0, dev->stream, L.pnnz, (const int32_t *)L.d_prow, (const int32_t *)L.d_pcol, L.rowptr,
-                       L.colidx, L.A, (const int32_t *)L.d_agg, (const double *)L.d_tval, (const double *)L.dinv, omega, L.d_P);
+    if (amg->nns_k) amg_block_smooth_p(amg, l, omega);
+    else
+        hipLaunchKernelGGL(k_amg_smooth_p, dim3(blocks_of(L.pnnz, 256)), dim3(256), 0, dev->stream, L.pnnz, (const int32_t *)L.d_prow, (const int32_t *)L.d_pcol, L.rowptr,
+                           L.colidx, L.A, (const int32_t *)L.d_agg, (const double *)L.d_tval, (const double *)L.dinv, omega, L.d_P);
     hipLaunchKernelGGL(k_amg_gather, dim3(blocks_of(L.pnnz, 256)), dim3(256), 0, dev->stream, L.pnnz, (const int64_t *)L.d_rperm, (const double *)L.d_P, L.d_R);
     if (amg->products) return amg->products(amg->products_ctx, l);
     launch_amg_spgemm(dev, L.apnnz, L.d_aprow, L.d_apcol, L.rowptr, L.colidx, L.A, L.d_pptr, L.d_pcol, L.d_P, L.d_AP);
     launch_amg_spgemm(dev, N.nnz, L.d_crow, N.colidx, L.d_rptr, L.d_rcol, L.d_R, L.d_apptr, L.d_apcol, L.d_AP, N.d_A);
+    if (amg->nns_k) amg_block_dead_diag(amg, l);
     return TB_OK;
 }
 
@@ -525,9 +545,14 @@ int tb_amg_setup(tb_amg *amg, const double *d_Anz, int degree, double interval_r
         F.n = pat->n_rows; F.nnz = pat->nnz;
         F.rowptr = pat->d_rowptr; F.colidx = pat->d_colidx;
         F.h_comp = amg->comp;
+        if (amg->nns_k) {
+            F.h_node = amg->nns_node;
+            F.n_nodes = amg->nns_nodes;
+        }
         std::vector<int64_t> diag;
         amgplan::diagonal_positions(F.n, pat->h_rowptr.data(), pat->h_colidx.data(), diag);
         int rc = upload_all(dev, F.h_comp, &F.d_comp, diag, &F.d_diag);
+        if (!rc && amg->nns_k) rc = upload(dev, amg->nns_B, &F.d_B);
         if (!rc) rc = F.alloc(F.n);
         if (rc) { free_plan(amg); return rc; }
     }

@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "tb_amg_block_planners.hpp"
 #include "tb_amg_planners.hpp"
 #include "tb_internal.h"
 #include "tb_mg_internal.hpp"
@@ -33,7 +34,29 @@ struct AmgLevel : MgVectors {
     int32_t *d_agg = nullptr, *d_pcol = nullptr, *d_prow = nullptr, *d_rcol = nullptr, *d_apcol = nullptr, *d_aprow = nullptr, *d_crow = nullptr;
     int64_t *d_pptr = nullptr, *d_rptr = nullptr, *d_rperm = nullptr, *d_apptr = nullptr;
     double *d_tval = nullptr, *d_P = nullptr, *d_R = nullptr, *d_AP = nullptr;
+    // with a near-null-space of k candidates (tb_amg_block.hip; all empty without one)
+    std::vector<int32_t> h_node;         // node of every dof (level 0: the caller's map; below: dof / k)
+    int64_t n_nodes = 0;
+    double *d_B = nullptr;               // candidates B_l, n × k row-major (rows of eliminated dofs zeroed when the level is planned)
+    double *d_T = nullptr;               // tentative prolongator, dense n × k: row i lies in the column block of its node's aggregate
+    double *d_Bc = nullptr;              // B_{l+1} on its way to the level below (which owns it from its creation on)
+    uint8_t *d_dead = nullptr;           // one byte per dof of level l + 1: a dead column of its aggregate's QR
+    int64_t *d_adofptr = nullptr;        // the dofs of every aggregate, ascending
+    int32_t *d_adof = nullptr;
+    amgplan::BlockPlan bplan;            // (its LevelPlan moves into `plan`)
 };
+
+// k_amg_rowmax and k_amg_strength on any CSR with one value per non-zero (the node graph and its block norms); m: n doubles of scratch; enqueues only
+void launch_amg_strength(tb_device *dev, int64_t n, const int64_t *rowptr, const int32_t *colidx, const double *val, const int8_t *comp, double theta, double *m,
+                         uint8_t *flag);
+// tb_amg_block.hip — the steps a near-null-space replaces.  amg_block_plan: candidates' zero rows, node strength (device), node graph, aggregates and
+// patterns (host) into lv[l].h_strength, .plan, .bplan; amg_block_tentative: uploads, the per-aggregate QR into d_T, d_Bc and d_dead;
+// amg_block_smooth_p and amg_block_dead_diag enqueue only.
+int amg_block_plan(tb_amg *amg, int l);
+int amg_block_tentative(tb_amg *amg, int l);
+void amg_block_smooth_p(tb_amg *amg, int l, double omega);
+void amg_block_dead_diag(tb_amg *amg, int l);
+void amg_block_free_level(AmgLevel &L);
 
 int amg_apply_cb(void *ctx, const double *r, double *z); // z = one V-cycle on r (ctx: the tb_amg); enqueues only
 // k_amg_spgemm, C = A·B on the planned pattern of C (crow, ccol: row and column of every non-zero of C); enqueues only
@@ -61,5 +84,10 @@ struct tb_amg {
     void *products_ctx = nullptr;
     int last_max = tb::MG_COARSEST_MAX;
     const char *who = "tb_amg_setup", *unit = "dofs";
+    // tb_amg_set_near_nullspace: k candidates on node blocks (k = 0: none — the scalar method, one constant per aggregate and component)
+    int nns_k = 0;
+    int64_t nns_nodes = 0;
+    std::vector<int32_t> nns_node;
+    std::vector<double> nns_B;
     int64_t aggregations = 0;            // host aggregation runs so far (one per level planned): what a numeric-only set-up leaves as it is
 };

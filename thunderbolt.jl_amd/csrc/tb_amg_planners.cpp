@@ -133,6 +133,13 @@ void plan_level(int64_t n, const int64_t *rowptr, const int32_t *colidx, const i
         if (L.agg[(size_t)i] >= 0) L.p_col.insert(L.p_col.end(), at_col.begin() + (std::ptrdiff_t)first, at_col.end());
         L.p_ptr[(size_t)i + 1] = (int64_t)L.p_col.size();
     }
+    complete_patterns(n, rowptr, colidx, L);
+}
+
+void complete_patterns(int64_t n, const int64_t *rowptr, const int32_t *colidx, LevelPlan &L)
+{
+    const int64_t nc = L.nc;
+    std::vector<int32_t> mark((size_t)std::max<int64_t>(nc, 1), -1);
     rows_of(L.p_ptr, L.p_row);
     // R = Pᵀ: a counting transpose keeps the fine dofs of a row ascending; r_perm remembers where each value sits in P
     L.r_ptr.assign((size_t)nc + 1, 0);
@@ -150,7 +157,6 @@ void plan_level(int64_t n, const int64_t *rowptr, const int32_t *colidx, const i
     }
     // A·P: the union of P's rows over the columns of A's row
     L.ap_ptr.assign((size_t)n + 1, 0);
-    std::fill(mark.begin(), mark.end(), -1);
     for (int64_t i = 0; i < n; ++i) {
         struct Cols { const int32_t *b, *e; const int32_t *begin() const { return b; } const int32_t *end() const { return e; } };
         union_rows(Cols{colidx + rowptr[i], colidx + rowptr[i + 1]}, L.p_ptr, L.p_col, mark, (int32_t)i, L.ap_col);

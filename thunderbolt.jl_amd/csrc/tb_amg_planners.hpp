@@ -32,6 +32,8 @@ void diagonal_positions(int64_t n, const int64_t *rowptr, const int32_t *colidx,
 void aggregate(int64_t n, const int64_t *rowptr, const int32_t *colidx, const uint8_t *strength, std::vector<int32_t> &agg, int64_t &n_agg);
 // aggregates and every pattern of one level (comp NULL: one component)
 void plan_level(int64_t n, const int64_t *rowptr, const int32_t *colidx, const int8_t *comp, const uint8_t *strength, LevelPlan &out);
+// from n, nc and P's pattern (p_ptr, p_col): p_row, R with its permutation, A·P, A_c and its diagonal positions
+void complete_patterns(int64_t n, const int64_t *rowptr, const int32_t *colidx, LevelPlan &L);
 
 } // namespace amgplan
 } // namespace tb

@@ -163,6 +163,10 @@ struct tb_mg {
     // tb_mg_set_coarse_amg: level 0 is solved by one cycle of a smoothed-aggregation hierarchy (tb_amg.hip) instead of the dense inverse
     bool coarse_amg = false;
     double amg_theta = 0.25;
+    int amg_nns_k = 0;                   // tb_mg_set_coarse_amg_near_nullspace: handed to that hierarchy when it is created (0: none)
+    int64_t amg_nns_nodes = 0;
+    std::vector<int32_t> amg_nns_node;
+    std::vector<double> amg_nns_B;
     int amg_max_coarse = tb::MG_COARSEST_MAX, amg_max_levels = 16;
     struct tb_amg *amg = nullptr;
 };

@@ -256,7 +256,13 @@ static int create_coarse_amg(tb_mg *mg)
         for (size_t q = 0; q < m->h_cell_dofs.size(); ++q) // local dof l of a cell carries component l mod ncomp, in any numbering
             comp[(size_t)m->h_cell_dofs[q]] = (int8_t)((q % (size_t)m->ndpc) % (size_t)m->ncomp);
     }
-    return tb_amg_create(pat, comp.empty() ? nullptr : comp.data(), mg->amg_theta, mg->amg_max_coarse, mg->amg_max_levels, &mg->amg);
+    TB_TRY(tb_amg_create(pat, comp.empty() ? nullptr : comp.data(), mg->amg_theta, mg->amg_max_coarse, mg->amg_max_levels, &mg->amg));
+    if (mg->amg_nns_k) {
+        TB_REQUIRE((int64_t)mg->amg_nns_node.size() == pat->n_rows, "tb_mg_set_coarse_amg_near_nullspace: the arrays were sized for %lld dofs, level 0 has %lld",
+                   (long long)mg->amg_nns_node.size(), (long long)pat->n_rows);
+        TB_TRY(tb_amg_set_near_nullspace(mg->amg, mg->amg_nns_nodes, mg->amg_nns_node.data(), mg->amg_nns_k, mg->amg_nns_B.data()));
+    }
+    return TB_OK;
 }
 
 static mgplan::LevelView view_of(const tb_pattern *p)
@@ -553,6 +559,23 @@ int tb_mg_set_coarse_amg(tb_mg *mg, double theta, int max_coarse, int max_levels
     mg->amg_theta = theta;
     mg->amg_max_coarse = max_coarse;
     mg->amg_max_levels = max_levels;
+    return TB_OK;
+}
+
+int tb_mg_set_coarse_amg_near_nullspace(tb_mg *mg, int64_t n_nodes, const int32_t *node_of_dof, int k, const double *B)
+{
+    TB_REQUIRE(mg && node_of_dof && B, "tb_mg_set_coarse_amg_near_nullspace: NULL argument");
+    TB_REQUIRE(mg->coarse_amg, "tb_mg_set_coarse_amg_near_nullspace: no AMG on level 0 (tb_mg_set_coarse_amg comes first)");
+    TB_REQUIRE(k >= 1 && k <= 6, "tb_mg_set_coarse_amg_near_nullspace: k = %d candidates; 1 to 6 are supported", k);
+    TB_REQUIRE(n_nodes >= 0, "tb_mg_set_coarse_amg_near_nullspace: negative node count");
+    TB_NO_CAPTURE(mg->dev);
+    TB_HIP(hipSetDevice(mg->dev->id));
+    free_plans(mg);
+    const int64_t n = 3 * n_nodes; // (3 dofs per node: tb_amg_set_near_nullspace checks the map against level 0 when the hierarchy is created)
+    mg->amg_nns_k = k;
+    mg->amg_nns_nodes = n_nodes;
+    mg->amg_nns_node.assign(node_of_dof, node_of_dof + n);
+    mg->amg_nns_B.assign(B, B + n * k);
     return TB_OK;
 }
 

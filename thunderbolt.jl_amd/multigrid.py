@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib as L
 from ._lib import check, lib
-from .amg import AlgebraicHierarchy, AMGPrecon
+from .amg import AlgebraicHierarchy, AMGPrecon, resolve_near_nullspace
 from .api import DofHandler, Hexahedron, LagrangeCollection, _ptr, allocate_matrix
 from .meshgen import GridHierarchy
 
@@ -161,6 +161,10 @@ class MultigridHierarchy:
         self.coarse = coarse
         if coarse is not None:
             check(lib().tb_mg_set_coarse_amg(self.h, coarse.theta, coarse.max_coarse, coarse.max_levels))
+            nns = resolve_near_nullspace(coarse.near_nullspace, self.dhs[0])     # the AMG sits on the first-order level 0, whose coordinates are its grid's
+            if nns is not None:
+                n_nodes, node, B = nns
+                check(lib().tb_mg_set_coarse_amg_near_nullspace(self.h, n_nodes, node.ctypes.data_as(L.c_i32p), B.shape[1], B.ctypes.data_as(L.c_dp)))
         self._A = None
 
     @property
@@ -186,6 +190,7 @@ class MultigridHierarchy:
         view = AlgebraicHierarchy.__new__(AlgebraicHierarchy)
         view.device, view.pattern, view.degree, view.interval_ratio, view.h, view._A, view.owner = self.device, self.patterns[0], self.degree, self.interval_ratio, h, None, self
         view.close = lambda: None
+        view.k = 0 if self.coarse is None or self.coarse.near_nullspace is None else 6 if isinstance(self.coarse.near_nullspace, str) else np.shape(self.coarse.near_nullspace)[1]
         return view
 
     def level_matrix(self, level):
