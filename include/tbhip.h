@@ -207,6 +207,8 @@ const char *tb_version(void);
  * Added under 10, purely additive: tb_bidomain_amg_* (smoothed-aggregation multigrid preconditioner of the bidomain block system: block V-cycle from the matrix alone).
  * Added under 10, purely additive: tb_amg_set_near_nullspace, tb_amg_level_nodes, tb_amg_level_near_nullspace, tb_amg_level_tentative, tb_amg_level_dead,
  * tb_mg_set_coarse_amg_near_nullspace (node-wise aggregation with rigid-body modes for elasticity); without them tb_amg_* behaves bit for bit as before.
+ * Added under 10, purely additive: tb_gmres_solve_mg, tb_gmres_solve_amg, tb_mg_set_general, tb_amg_set_general (multigrid-preconditioned GMRES for operators
+ * that are not symmetric; a pivoted last-level inverse); without them every entry behaves bit for bit as before.
  * A host binding compares tb_abi_revision() with the
  * TB_ABI_REVISION it was written against and refuses to run on a mismatch (julia/ThunderboltHIPBackend.jl does, in __init__) */
 #define TB_ABI_REVISION 10
@@ -910,7 +912,7 @@ int tb_cg_solve_f32(tb_pattern *pat, const float *d_Anz, const float *d_b, float
  * Chebyshev–Jacobi smoother of multigrid.jl:28-33 on [λmax/interval_ratio, λmax] of D⁻¹A, an explicit inverse on the coarsest level.  A symmetric
  * positive-definite operator, so plain PCG applies.  The finest level may carry a second-order (TB_HEX27) field: one p-level joins it to the first-order field on the
  * same cells (PMGPrecon; with h-levels below: ChainedMGPrecon).  Out of scope and refused: orders above 2, more than one p-level, tetrahedra, W- and
- * F-cycles, other smoothers, GMRES, several ranks.
+ * F-cycles, other smoothers, several ranks.  Operators that are not symmetric: tb_mg_set_general and tb_gmres_solve_mg, below the AMG entries.
  *   tb_mg_create        an empty hierarchy of n_levels ≥ 2 levels; level 0 is the coarsest, level n_levels − 1 the one the solve runs on
  *   tb_mg_set_level     the pattern of a level: the allocate_matrix pattern of a first-order field (1 or 3 components) on that level's grid — on the
  *                       finest level also of a TB_HEX27 field on TB_HEX8 geometry; the pattern (and its mesh) must outlive the hierarchy
@@ -1053,6 +1055,36 @@ int tb_amg_level_near_nullspace(tb_amg *amg, int level, int *k, double *B);
 int tb_amg_level_tentative(tb_amg *amg, int level, double *T);
 int tb_amg_level_dead(tb_amg *amg, int level, uint8_t *dead);
 int tb_mg_set_coarse_amg_near_nullspace(tb_mg *mg, int64_t n_nodes, const int32_t *node_of_dof, int k, const double *B);
+
+/* ------------------------------------------------------------------ multigrid-preconditioned GMRES for non-symmetric operators (tb_krylov.hip, tb_multigrid.hip, tb_amg.hip)
+ * KrylovMGSolver(mg) of the reference defaults to KrylovJL_GMRES(gmres_restart = 400) (src/solver/linear/multigrid.jl:114-115); its worked example
+ * pairs GMRES with GMGPrecon inside NewtonRaphsonSolver.  For the tangents that are not symmetric: pressure follower loads, the rate-coupled sarcomere
+ * tangent, the inner solves of the chamber Schur complement.
+ *   tb_mg_set_general / tb_amg_set_general   general = 1: the operator need not be symmetric.  The one place where the hierarchies use symmetry in numbers
+ *                       is the dense inverse of the last level: it is then computed by Gauss–Jordan elimination with partial (row) pivoting — ties to the
+ *                       lowest row, so two set-ups give the same bits — and is not symmetrised.  A zero or non-finite pivot makes the set-up return
+ *                       TB_ERR_BAD_ARG with a message that names the entry and the level.  Everything else is unchanged: restriction is Pᵀ, the Galerkin
+ *                       products, the smoothed prolongator, the strength measure, and λmax — of a non-symmetric D⁻¹A the same Lanczos / Gershgorin figure,
+ *                       i.e. an estimate of the spectral radius of the symmetrised iteration, not a bound.  A positive diagonal is still required, and the
+ *                       Chebyshev–Jacobi smoother is for MILDLY non-symmetric operators (a skew part of a tenth to a third of the diagonal scale; at a
+ *                       skew part as large as the symmetric one point-Jacobi Chebyshev smoothing breaks down).  general = 0 (the default) is the path and
+ *                       the bits of before.  A change clears the numeric phase: the next tb_mg_setup / tb_amg_setup redoes it (plans are kept), and the
+ *                       solve and apply entries refuse until then.  tb_mg_set_general reaches the AMG of tb_mg_set_coarse_amg as well.
+ *   tb_gmres_solve_mg / tb_gmres_solve_amg   tb_gmres_solve with the fixed RIGHT preconditioner M⁻¹ = one V cycle (tb_mg_apply / tb_amg_apply) in place of D⁻¹:
+ *                       per Arnoldi step z = M⁻¹ v_j, w = A z, twice-iterated classical Gram–Schmidt, host Givens; at the end of a restart cycle
+ *                       x += M⁻¹(V y), one more cycle (no second basis is stored: M must be a fixed operator; flexible GMRES is out of scope).  The
+ *                       contract of tb_gmres_solve in every respect: stopping test on the true residual at the top of each cycle, iters counts Arnoldi
+ *                       steps and the solve stops at the first whose estimate meets the threshold, tb_solver_last_tolerance, a non-finite ‖r₀‖ returns
+ *                       at once with a NaN threshold, breakdown is TB_ERR_BAD_ARG, not inside a graph capture.  The checks of tb_pcg_solve_mg /
+ *                       tb_pcg_solve_amg on the hierarchy (set up, this pattern, this matrix array), and restart in 1..1000.  The hierarchy may be in
+ *                       either mode; on a non-symmetric operator general = 1 is the one whose coarse solve is exact.  The bidomain block recipes
+ *                       (tb_bidomain_mg_*, tb_bidomain_amg_*) keep to CG. */
+int tb_mg_set_general(tb_mg *mg, int general);
+int tb_amg_set_general(tb_amg *amg, int general);
+int tb_gmres_solve_mg(tb_pattern *pat, const double *d_Anz, const double *d_b, double *d_x, double rtol, double atol, int maxiter, int restart, tb_mg *mg,
+                      int *iters, double *resnorm);
+int tb_gmres_solve_amg(tb_pattern *pat, const double *d_Anz, const double *d_b, double *d_x, double rtol, double atol, int maxiter, int restart, tb_amg *amg,
+                       int *iters, double *resnorm);
 
 /* ------------------------------------------------------------------ parabolic-elliptic bidomain block system (tb_bidomain.hip)
  * ParabolicEllipticBidomainModel (src/modeling/electrophysiology.jl:305-326, declared "Not implemented yet" there).  Backward Euler on the transformed

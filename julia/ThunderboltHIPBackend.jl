@@ -758,6 +758,19 @@ function pcg_mg!(x::HIPVector{Float64}, A::HIPSparseMatrixCSR{Float64}, b::HIPVe
         A.ddh.pattern, A.nzval.ptr, b.ptr, x.ptr, rtol, atol, maxiter, mg.handle, it, res))
     return Int(it[]), res[]
 end
+# general mode: the matrix need not be symmetric (pivoted, unsymmetrised coarsest inverse); a change makes the next setup! redo the numeric phase
+set_general!(mg::HIPGMGPrecon, general::Bool = true) = check(ccall((:tb_mg_set_general, libtbhip), Cint, (Ptr{Cvoid}, Cint), mg.handle, general ? 1 : 0))
+# KrylovMGSolver(KrylovJL_GMRES(gmres_restart = restart), mg) (multigrid.jl:114-115): general mode, the numeric phase from the matrix, then GMRES(restart)
+# with one cycle as the fixed right preconditioner; for mildly non-symmetric matrices with a positive diagonal
+function gmres_mg!(x::HIPVector{Float64}, A::HIPSparseMatrixCSR{Float64}, b::HIPVector{Float64}, mg::HIPGMGPrecon; rtol = 1e-8, atol = 1e-14, maxiter = 5000,
+                   restart = 50, setup = true, general = true)
+    set_general!(mg, general)
+    setup && setup!(mg, A)
+    it = Ref{Cint}(0); res = Ref{Cdouble}(0)
+    check(ccall((:tb_gmres_solve_mg, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Cint, Cint, Ptr{Cvoid}, Ref{Cint}, Ref{Cdouble}),
+        A.ddh.pattern, A.nzval.ptr, b.ptr, x.ptr, rtol, atol, maxiter, restart, mg.handle, it, res))
+    return Int(it[]), res[]
+end
 # Smoothed-aggregation algebraic multigrid (SmoothedAggregationCoarseSolver, the default pcoarse_solver of PMGPrecon: src/solver/linear/multigrid.jl:27).
 # `pattern`: the tb_pattern of the matrix; `components`: one Int8 label per dof (empty: one component).  Level 0 is the matrix, level l + 1 the Galerkin
 # operator of level l's aggregates.  The first `setup!` plans, every later one redoes the numeric phase on the same aggregates; `replan!` drops the plan.
@@ -859,6 +872,17 @@ function pcg_amg!(x::HIPVector{Float64}, A::HIPSparseMatrixCSR{Float64}, b::HIPV
     it = Ref{Cint}(0); res = Ref{Cdouble}(0)
     check(ccall((:tb_pcg_solve_amg, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Cint, Ptr{Cvoid}, Ref{Cint}, Ref{Cdouble}),
         A.ddh.pattern, A.nzval.ptr, b.ptr, x.ptr, rtol, atol, maxiter, amg.handle, it, res))
+    return Int(it[]), res[]
+end
+# general mode and GMRES(restart) with one AMG cycle as the fixed right preconditioner: as set_general! and gmres_mg! of the geometric hierarchy
+set_general!(amg::HIPAMGPrecon, general::Bool = true) = check(ccall((:tb_amg_set_general, libtbhip), Cint, (Ptr{Cvoid}, Cint), amg.handle, general ? 1 : 0))
+function gmres_amg!(x::HIPVector{Float64}, A::HIPSparseMatrixCSR{Float64}, b::HIPVector{Float64}, amg::HIPAMGPrecon; rtol = 1e-8, atol = 1e-14, maxiter = 5000,
+                    restart = 50, setup = true, general = true)
+    set_general!(amg, general)
+    setup && setup!(amg, A)
+    it = Ref{Cint}(0); res = Ref{Cdouble}(0)
+    check(ccall((:tb_gmres_solve_amg, libtbhip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Cint, Cint, Ptr{Cvoid}, Ref{Cint}, Ref{Cdouble}),
+        A.ddh.pattern, A.nzval.ptr, b.ptr, x.ptr, rtol, atol, maxiter, restart, amg.handle, it, res))
     return Int(it[]), res[]
 end
 # the coarsest level of a geometric or p-hierarchy is solved by one AMG cycle instead of the dense inverse (call before the first setup!); afterwards

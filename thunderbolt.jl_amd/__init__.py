@@ -16,7 +16,7 @@ from .meshgen import uniform_refinement_with_maps, GridHierarchy  # noqa: F401
 from . import amg  # noqa: F401
 from .amg import AMGPrecon, AlgebraicHierarchy  # noqa: F401
 from . import multigrid  # noqa: F401
-from .multigrid import GMGPrecon, PMGPrecon, ChainedMGPrecon, KrylovMGSolver, MultigridHierarchy  # noqa: F401
+from .multigrid import GMGPrecon, PMGPrecon, ChainedMGPrecon, KrylovGMRES, KrylovMGSolver, MultigridHierarchy  # noqa: F401
 from . import chamber  # noqa: F401
 from .chamber import (RSAFDQ2022SurrogateVolume, Hirschvogel2017SurrogateVolume, ConstantChamberVolume, ChamberVolumeCoupling,  # noqa: F401
                       LumpedFluidSolidCoupler, ChamberForm, ChamberTying, compute_chamber_volume, SchurComplementLinearSolver, BlockedChamberSystem,

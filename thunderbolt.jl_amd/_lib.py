@@ -247,6 +247,10 @@ SIGNATURES = {
     "tb_amg_level_tentative": (C.c_int, [vp, C.c_int, c_dp]),
     "tb_amg_level_dead": (C.c_int, [vp, C.c_int, vp]),
     "tb_mg_set_coarse_amg_near_nullspace": (C.c_int, [vp, C.c_int64, c_i32p, C.c_int, c_dp]),
+    "tb_mg_set_general": (C.c_int, [vp, C.c_int]),
+    "tb_amg_set_general": (C.c_int, [vp, C.c_int]),
+    "tb_gmres_solve_mg": (C.c_int, [vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "tb_gmres_solve_amg": (C.c_int, [vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "tb_bidomain_create": (C.c_int, [vp, C.POINTER(vp)]),
     "tb_bidomain_destroy": (C.c_int, [vp]),
     "tb_bidomain_set_matrices": (C.c_int, [vp, vp, vp, vp, vp, C.c_double, vp, C.c_double]),

@@ -6,11 +6,13 @@ AMGPrecon is the recipe; `materialize(pattern, ch)` gives the AlgebraicHierarchy
 and the ECG caches drive through the protocol of the geometric multigrid (materialize / tb_mg_solve).  Inside ChainedMGPrecon(PMGPrecon(), AMGPrecon())
 and GMGPrecon(gh, coarse=AMGPrecon()) it replaces the dense inverse of the coarsest level (multigrid.py → tb_mg_set_coarse_amg).
 
-Covered: one field of 1 or 3 components on the whole grid, CG, V-cycles with the Chebyshev–Jacobi smoother.  For elasticity,
+Covered: one field of 1 or 3 components on the whole grid, CG and — for mildly non-symmetric matrices with a positive diagonal, the hierarchy in
+general mode: a pivoted, unsymmetrised last-level inverse — restarted GMRES (gmres_solve(…, precond=AMGPrecon(…))), V-cycles with the Chebyshev–Jacobi
+smoother.  One hierarchy serves one kind of solve cheaply: CG after GMRES on it, or the other way round, flips the mode and sets up again.  For elasticity,
 AMGPrecon(near_nullspace="rigid_body") aggregates node by node and carries the six rigid-body modes through the hierarchy (Vaněk–Mandel–Brezina: a
 per-aggregate QR of the candidates gives the tentative prolongator and the candidates of the level below; the method as include/tbhip.h states it);
 without the keyword the prolongator has one constant per aggregate and component, which carries the translations only.  Refused with a message: the
-bidomain block system (BidomainAMGPrecon in bidomain.py is its recipe), GMRES, W- and F-cycles, other smoothers, subdomain dof handlers, "rigid_body" on
+bidomain block system (BidomainAMGPrecon in bidomain.py is its recipe), W- and F-cycles, other smoothers, subdomain dof handlers, "rigid_body" on
 a scalar or second-order field.  Out of scope: block-Jacobi smoothers, candidates in the current configuration, candidates on scalar fields,
 aggregation on the device, classical Ruge–Stüben coarsening, Float32, several ranks."""
 import ctypes as C
@@ -155,10 +157,23 @@ class AlgebraicHierarchy:
         self.k = B.shape[1]
         return self
 
+    general = False          # set_general: the matrix need not be symmetric (pivoted last-level inverse, nothing symmetrised)
+    n_setups = 0             # numeric set-ups so far
+
+    def set_general(self, general):
+        """general mode on or off (tb_amg_set_general); a change drops the numeric phase, so the next solve or `setup` redoes it"""
+        general = bool(general)
+        if general != self.general:
+            check(lib().tb_amg_set_general(self.h, int(general)))
+            self.general = general
+            self._A = None
+        return self
+
     def setup(self, A):
         """plan (first call) and numeric phase for the matrix values `A` (after apply_zero): smoothed P, Galerkin chain, D⁻¹, λmax per level, last inverse"""
         check(lib().tb_amg_setup(self.h, _ptr(A), self.degree, self.interval_ratio))
         self._A = A                                  # the cycle reads the array: keep it alive
+        self.n_setups += 1
         return self
 
     def replan(self):
@@ -256,10 +271,23 @@ class AlgebraicHierarchy:
 
     def solve(self, A, b, x, rtol=1e-5, atol=1e-6, maxiter=1000, setup=True):
         """CG on A x = b preconditioned by one cycle (tb_pcg_solve_amg) → (iterations, residual norm); setup=False reuses the numeric phase"""
+        self.set_general(False)
         if setup or self._A is None:
             self.setup(A)
         it, res = C.c_int(), C.c_double()
         check(lib().tb_pcg_solve_amg(self.pattern.h, _ptr(A), _ptr(b), _ptr(x), float(rtol), float(atol), int(maxiter), self.h, C.byref(it), C.byref(res)))
+        return it.value, res.value
+
+    def solve_gmres(self, A, b, x, rtol=1e-5, atol=1e-6, maxiter=1000, restart=50, setup=True, general=True):
+        """GMRES(restart) on A x = b with one cycle as the fixed right preconditioner (tb_gmres_solve_amg) → (Arnoldi steps, residual norm).  The
+        hierarchy goes to general mode first (general=False keeps the symmetrised last-level inverse: for measurements); setup=False reuses the
+        numeric phase unless the mode changed"""
+        self.set_general(general)
+        if setup or self._A is None:
+            self.setup(A)
+        it, res = C.c_int(), C.c_double()
+        check(lib().tb_gmres_solve_amg(self.pattern.h, _ptr(A), _ptr(b), _ptr(x), float(rtol), float(atol), int(maxiter), int(restart), self.h, C.byref(it),
+                                       C.byref(res)))
         return it.value, res.value
 
     reuse_setup = False      # set by the Newton loop under simplified_newton: the tangent, and with it the numeric phase, is the previous one
@@ -269,6 +297,12 @@ class AlgebraicHierarchy:
         if pattern is not self.pattern:
             raise ValueError("pcg_solve: the AMG hierarchy was materialised for another pattern")
         return self.solve(A, b, x, rtol, atol, maxiter, setup=not self.reuse_setup)
+
+    def tb_mg_gmres_solve(self, pattern, A, b, x, rtol, atol, maxiter, restart):
+        """what gmres_solve(…, precond=<this>) runs"""
+        if pattern is not self.pattern:
+            raise ValueError("gmres_solve: the AMG hierarchy was materialised for another pattern")
+        return self.solve_gmres(A, b, x, rtol, atol, maxiter, restart, setup=not self.reuse_setup)
 
     def close(self):
         if self.h:

@@ -1132,8 +1132,18 @@ def l1gs_apply(pattern, A, r, z, partsize=64, sweep="symmetric"):
     return z
 
 
-def gmres_solve(pattern, A, b, x, rtol=1e-8, atol=1e-14, maxiter=5000, restart=50, jacobi=True):
-    """LinearSolve.solve! with KrylovJL_GMRES (the Newton default, newton_raphson.jl:61): restarted GMRES on the device."""
+def gmres_solve(pattern, A, b, x, rtol=1e-8, atol=1e-14, maxiter=5000, restart=50, jacobi=True, precond=None):
+    """LinearSolve.solve! with KrylovJL_GMRES (the Newton default, newton_raphson.jl:61): restarted GMRES on the device.  precond = None: right
+    Jacobi (`jacobi`).  precond = GMGPrecon | PMGPrecon | ChainedMGPrecon | AMGPrecon (with or without near_nullspace, or as the `coarse` of a
+    GMGPrecon) or a materialised hierarchy: one V cycle as the fixed right preconditioner (multigrid.jl:114-115; tb_gmres_solve_mg / _amg) — the
+    hierarchy is switched to general mode (pivoted, unsymmetrised coarsest inverse) and its numeric phase rebuilt from `A` as pcg_solve does.  For
+    mildly non-symmetric matrices with a positive diagonal; Dirichlet dofs need the hierarchy materialised with their handler."""
+    if precond is not None:
+        if hasattr(precond, "materialize"):
+            precond = precond.materialize(pattern)
+        if not hasattr(precond, "tb_mg_gmres_solve"):
+            raise TypeError("gmres_solve: precond is None (right Jacobi), a multigrid recipe (GMGPrecon, PMGPrecon, ChainedMGPrecon, AMGPrecon) or a materialised hierarchy")
+        return precond.tb_mg_gmres_solve(pattern, A, b, x, rtol, atol, maxiter, restart)
     it, res = C.c_int(), C.c_double()
     check(lib().tb_gmres_solve(pattern.h, _ptr(A), _ptr(b), _ptr(x), float(rtol), float(atol), int(maxiter), int(restart), int(jacobi),
                                C.byref(it), C.byref(res)))

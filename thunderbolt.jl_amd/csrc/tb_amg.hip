@@ -465,7 +465,8 @@ static int setup_levels(tb_amg *amg)
             }
             if (amg->products) break; // the block hierarchy inverts its own last level
             if (!amg->d_cinv) TB_HIP(hipMalloc((void **)&amg->d_cinv, sizeof(double) * (size_t)L.n * (size_t)L.n));
-            launch_dense_inverse(dev, (int)L.n, L.rowptr, L.colidx, L.A, amg->d_cinv);
+            launch_dense_inverse(dev, (int)L.n, L.rowptr, L.colidx, L.A, amg->d_cinv, amg->general);
+            if (amg->general) TB_TRY(dense_inverse_status(dev, amg->who, l, (int)L.n));
             break;
         }
         hipLaunchKernelGGL(k_amg_dinv, dim3(blocks_of(L.n, 256)), dim3(256), 0, dev->stream, L.n, (const int64_t *)L.d_diag, L.A, L.dinv);
@@ -563,6 +564,15 @@ int tb_amg_setup(tb_amg *amg, const double *d_Anz, int degree, double interval_r
     return TB_OK;
 }
 
+int tb_amg_set_general(tb_amg *amg, int general)
+{
+    TB_REQUIRE(amg, "tb_amg_set_general: NULL argument");
+    if (amg->general == (general != 0)) return TB_OK;
+    amg->general = general != 0;
+    amg->ready = false; // the numeric phase is redone by the next tb_amg_setup (the plan stays)
+    return TB_OK;
+}
+
 int tb_amg_apply(tb_amg *amg, const double *d_r, double *d_z)
 {
     TB_REQUIRE(amg && d_r && d_z, "tb_amg_apply: NULL argument");
@@ -582,6 +592,19 @@ int tb_pcg_solve_amg(tb_pattern *pat, const double *d_Anz, const double *d_b, do
     TB_REQUIRE(amg->lv[0].A == d_Anz, "tb_pcg_solve_amg: the hierarchy was set up with another matrix array (tb_amg_setup follows every new matrix)");
     TB_HIP(hipSetDevice(pat->mesh->dev->id));
     return launch_pcg_apply(pat, d_Anz, d_b, d_x, rtol, atol, maxiter, amg_apply_cb, amg, "AMG preconditioner", iters, resnorm);
+}
+
+int tb_gmres_solve_amg(tb_pattern *pat, const double *d_Anz, const double *d_b, double *d_x, double rtol, double atol, int maxiter, int restart, tb_amg *amg,
+                       int *iters, double *resnorm)
+{
+    TB_REQUIRE(pat && d_Anz && d_b && d_x && amg, "tb_gmres_solve_amg: NULL argument");
+    TB_REQUIRE(rtol >= 0 && atol >= 0 && maxiter >= 0, "tb_gmres_solve_amg: negative tolerance or iteration limit");
+    TB_REQUIRE(restart >= 1 && restart <= 1000, "tb_gmres_solve_amg: restart must be in 1..1000 (got %d)", restart);
+    TB_REQUIRE(amg->ready, "tb_gmres_solve_amg: no numeric setup yet (tb_amg_setup; tb_amg_set_general asks for a new one)");
+    TB_REQUIRE(amg->pat == pat, "tb_gmres_solve_amg: the hierarchy was created for another pattern");
+    TB_REQUIRE(amg->lv[0].A == d_Anz, "tb_gmres_solve_amg: the hierarchy was set up with another matrix array (tb_amg_setup follows every new matrix)");
+    TB_HIP(hipSetDevice(pat->mesh->dev->id));
+    return launch_gmres_apply(pat, d_Anz, d_b, d_x, rtol, atol, maxiter, restart, amg_apply_cb, amg, "tb_gmres_solve_amg", iters, resnorm);
 }
 
 // ---- inspectors ----

@@ -73,6 +73,7 @@ struct tb_amg {
     std::vector<int8_t> comp;
     std::vector<tb::AmgLevel> lv;        // lv[0]: the caller's matrix
     bool planned = false, ready = false;
+    bool general = false;                // tb_amg_set_general: the operator need not be symmetric — the last level's inverse is pivoted and not symmetrised
     int degree = 2;
     double ratio = 4.0;
     double *d_cinv = nullptr;            // dense inverse of the last level's operator

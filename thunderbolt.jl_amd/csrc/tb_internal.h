@@ -462,6 +462,9 @@ int estimate_lambda_max(tb_pattern *pat, const double *A, const double *dinv, do
                         double *lmax_out); // Lanczos + Gershgorin estimate of λmax(D⁻¹A): five scratch vectors, two device scalars; reads back
 int launch_pcg_apply(tb_pattern *pat, const double *A, const double *b, double *x, double rtol, double atol, int maxiter,
                      int (*apply)(void *ctx, const double *r, double *z), void *ctx, const char *what, int *iters, double *resnorm);
+int launch_gmres_apply(tb_pattern *pat, const double *A, const double *b, double *x, double rtol, double atol, int maxiter, int restart,
+                       int (*apply)(void *ctx, const double *r, double *z), void *ctx, const char *what, int *iters, double *resnorm); // launch_gmres with
+                       // M⁻¹ by the caller's launches (a fixed right preconditioner); `what`: the entry's name in the breakdown message
 int launch_cgd_dot(tb_device *dev, int64_t n, const double *w, const double *a, const double *b, double *d_out);
 int launch_cgd_update(tb_device *dev, int64_t n, const double *w, const double *dinv, const double *p, const double *Ap, double *x, double *r,
                       const double *d_rz, const double *d_pAp, double *d_out3);

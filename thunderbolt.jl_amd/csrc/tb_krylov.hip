@@ -248,21 +248,19 @@ k_add_diag(int64_t n, const double *__restrict__ d, const double *__restrict__ t
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) x[i] += d ? d[i] * t[i] : t[i];
 }
 
-int launch_gmres(tb_pattern *pat, const double *A, const double *b, double *x, double rtol, double atol, int maxiter, int restart, int jacobi,
-                 int *iters, double *resnorm)
+// The restarted GMRES loop of every fixed right preconditioner M (A M⁻¹ y = b, x = M⁻¹ y: the monitored residual is the true one), as pcg_loop is the
+// loop of every CG preconditioner applied by launches.  V: restart + 1 basis vectors; w, z: n doubles each; sc: h1[(m+2)·GM_HS] | h2[(m+2)·GM_HS] | y[m+2].
+// precondition(v, z) enqueues z = M⁻¹ v; correct(t, x) enqueues x += M⁻¹ t, where t is z and w is free for it to use.  `who` names the entry in the
+// breakdown message.
+template <class Precondition, class Correct>
+static int gmres_loop(tb_pattern *pat, const double *A, const double *b, double *x, double rtol, double atol, int maxiter, int restart, double *V, double *w,
+                      double *z, double *sc, Precondition precondition, Correct correct, const char *who, int *iters, double *resnorm)
 {
     tb_device *dev = pat->mesh->dev;
-    TB_NO_CAPTURE(dev); // reads scalars back (convergence looks)
     const int64_t n = pat->n_rows;
     const int m = restart;
-    double *V = krylov_ws(pat, (size_t)(m + 4) * n + (2 * GM_HS + 1) * (size_t)(m + 2)); // (restart + 1) basis vectors, 3 vectors, scalars
-    if (!V) return TB_ERR_HIP;
-    pat->cg_dinv_of = nullptr; // the workspace no longer holds launch_cg's D⁻¹
-    double *w = V + (size_t)(m + 1) * n, *z = w + n, *dinv = z + n, *sc = dinv + n; // sc: h1[(m+2)·GM_HS] | h2[(m+2)·GM_HS] | y[m+2]
     double *h1 = sc, *h2 = sc + (size_t)(m + 2) * GM_HS, *yd = sc + 2 * (size_t)(m + 2) * GM_HS;
     const unsigned g = grid_for(dev, n, 256);
-    if (jacobi) { const int rcd = launch_extract_inverse_diagonal(pat, A, dinv); if (rcd) return rcd; }
-    const double *dp = jacobi ? dinv : nullptr;
     std::vector<double> H((size_t)(m + 1) * m), cs(m), sn(m), gvec(m + 1), yh(m), hh(2 * (size_t)(m + 2) * GM_HS);
     int it = 0;
     double rnorm = 0.0, tol = 0.0;
@@ -283,8 +281,9 @@ int launch_gmres(tb_pattern *pat, const double *A, const double *b, double *x, d
         int j = 0;
         double res_est = rnorm;
         for (; j < m && it < maxiter && res_est > tol; ++j, ++it) {
-            // w = A D⁻¹ v_j
-            hipLaunchKernelGGL(k_scale_diag, dim3(g), dim3(256), 0, dev->stream, n, 1.0, dp, V + (size_t)j * n, z);
+            // w = A M⁻¹ v_j
+            rc = precondition((const double *)(V + (size_t)j * n), z);
+            if (rc) return rc;
             rc = launch_spmv(pat, A, z, 1.0, 0.0, w);
             if (rc) return rc;
             TB_HIP(hipMemsetAsync(sc, 0, sizeof(double) * 2 * (m + 2) * GM_HS, dev->stream));
@@ -299,7 +298,7 @@ int launch_gmres(tb_pattern *pat, const double *A, const double *b, double *x, d
             for (int i = 0; i <= j; ++i) Hj[i] = hh[(size_t)i * GM_HS] + hh[((size_t)(m + 2) + i) * GM_HS];
             const double wn = std::sqrt(hh[((size_t)(m + 2) + (m + 1)) * GM_HS]);
             Hj[j + 1] = wn;
-            if (!std::isfinite(wn)) { set_error("tb_gmres_solve: breakdown (non-finite Arnoldi vector)"); return TB_ERR_BAD_ARG; }
+            if (!std::isfinite(wn)) { set_error("%s: breakdown (non-finite Arnoldi vector)", who); return TB_ERR_BAD_ARG; }
             for (int i = 0; i < j; ++i) { const double t = cs[i] * Hj[i] + sn[i] * Hj[i + 1]; Hj[i + 1] = -sn[i] * Hj[i] + cs[i] * Hj[i + 1]; Hj[i] = t; }
             const double den = std::hypot(Hj[j], Hj[j + 1]);
             cs[j] = den > 0 ? Hj[j] / den : 1.0; sn[j] = den > 0 ? Hj[j + 1] / den : 0.0;
@@ -309,7 +308,7 @@ int launch_gmres(tb_pattern *pat, const double *A, const double *b, double *x, d
             if (wn > 0.0 && j + 1 <= m) hipLaunchKernelGGL(k_scale_diag, dim3(g), dim3(256), 0, dev->stream, n, 1.0 / wn, (const double *)nullptr, w, V + (size_t)(j + 1) * n);
             if (wn == 0.0) { ++j; ++it; break; } // lucky breakdown: the Krylov space is invariant, the solution is exact in it
         }
-        // y = H⁻¹ g (upper triangular), x += D⁻¹ V y
+        // y = H⁻¹ g (upper triangular), x += M⁻¹ V y
         for (int i = j - 1; i >= 0; --i) {
             double sacc = gvec[i];
             for (int l = i + 1; l < j; ++l) sacc -= H[(size_t)l * (m + 1) + i] * yh[l];
@@ -318,13 +317,63 @@ int launch_gmres(tb_pattern *pat, const double *A, const double *b, double *x, d
         TB_HIP(hipMemcpyAsync(yd, yh.data(), sizeof(double) * j, hipMemcpyHostToDevice, dev->stream));
         TB_HIP(hipMemsetAsync(z, 0, sizeof(double) * n, dev->stream));
         hipLaunchKernelGGL(k_multi_axpy, dim3(grid_red(dev, n)), dim3(1024), 0, dev->stream, n, j, 1.0, yd, 1, V, z, (double *)nullptr);
-        hipLaunchKernelGGL(k_add_diag, dim3(g), dim3(256), 0, dev->stream, n, dp, z, x);
+        rc = correct((const double *)z, x);
+        if (rc) return rc;
         TB_SYNC_STREAM(dev); // yh is reused by the next cycle
     }
     TB_HIP(hipGetLastError());
     if (iters) *iters = it;
     if (resnorm) *resnorm = rnorm;
     return TB_OK;
+}
+
+int launch_gmres(tb_pattern *pat, const double *A, const double *b, double *x, double rtol, double atol, int maxiter, int restart, int jacobi,
+                 int *iters, double *resnorm)
+{
+    tb_device *dev = pat->mesh->dev;
+    TB_NO_CAPTURE(dev); // reads scalars back (convergence looks)
+    const int64_t n = pat->n_rows;
+    const int m = restart;
+    double *V = krylov_ws(pat, (size_t)(m + 4) * n + (2 * GM_HS + 1) * (size_t)(m + 2)); // (restart + 1) basis vectors, 3 vectors, scalars
+    if (!V) return TB_ERR_HIP;
+    pat->cg_dinv_of = nullptr; // the workspace no longer holds launch_cg's D⁻¹
+    double *w = V + (size_t)(m + 1) * n, *z = w + n, *dinv = z + n, *sc = dinv + n;
+    const unsigned g = grid_for(dev, n, 256);
+    if (jacobi) { const int rcd = launch_extract_inverse_diagonal(pat, A, dinv); if (rcd) return rcd; }
+    const double *dp = jacobi ? dinv : nullptr;
+    auto precondition = [&](const double *v, double *y) -> int { // y = D⁻¹ v
+        hipLaunchKernelGGL(k_scale_diag, dim3(g), dim3(256), 0, dev->stream, n, 1.0, dp, v, y);
+        return TB_OK;
+    };
+    auto correct = [&](const double *t, double *xx) -> int { // x += D⁻¹ t
+        hipLaunchKernelGGL(k_add_diag, dim3(g), dim3(256), 0, dev->stream, n, dp, t, xx);
+        return TB_OK;
+    };
+    return gmres_loop(pat, A, b, x, rtol, atol, maxiter, restart, V, w, z, sc, precondition, correct, "tb_gmres_solve", iters, resnorm);
+}
+
+// GMRES with the fixed right preconditioner supplied by the caller as enqueue-only launches (tb_gmres_solve_mg, tb_gmres_solve_amg: one multigrid
+// cycle per Arnoldi step and one more per restart cycle for x += M⁻¹(V y); no second basis is stored, so M must not change during the solve)
+int launch_gmres_apply(tb_pattern *pat, const double *A, const double *b, double *x, double rtol, double atol, int maxiter, int restart,
+                       int (*apply)(void *ctx, const double *r, double *z), void *ctx, const char *what, int *iters, double *resnorm)
+{
+    tb_device *dev = pat->mesh->dev;
+    TB_NO_CAPTURE(dev); // reads scalars back (convergence looks)
+    const int64_t n = pat->n_rows;
+    const int m = restart;
+    double *V = krylov_ws(pat, (size_t)(m + 3) * n + (2 * GM_HS + 1) * (size_t)(m + 2)); // (restart + 1) basis vectors, 2 vectors, scalars
+    if (!V) return TB_ERR_HIP;
+    pat->cg_dinv_of = nullptr; // the workspace no longer holds launch_cg's D⁻¹
+    double *w = V + (size_t)(m + 1) * n, *z = w + n, *sc = z + n;
+    const unsigned g = grid_for(dev, n, 256);
+    auto precondition = [&](const double *v, double *y) -> int { return apply(ctx, v, y); };
+    auto correct = [&](const double *t, double *xx) -> int { // x += M⁻¹ t: the cycle reads t throughout, so it lands in w (free between two cycles)
+        const int rc = apply(ctx, t, w);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_add_diag, dim3(g), dim3(256), 0, dev->stream, n, (const double *)nullptr, (const double *)w, xx);
+        return TB_OK;
+    };
+    return gmres_loop(pat, A, b, x, rtol, atol, maxiter, restart, V, w, z, sc, precondition, correct, what, iters, resnorm);
 }
 
 // ------------------------------------------------------------------------------------------------

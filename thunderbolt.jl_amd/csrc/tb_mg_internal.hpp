@@ -108,7 +108,11 @@ struct ChebSchedule {
 
 // tb_multigrid.hip: enqueue-only launchers of the kernels the family shares
 void launch_cheb_step(tb_device *dev, int mode, int64_t n, ChebSchedule::Step c, const double *dinv, const double *r, const double *w, double *d, double *x); // k_mg_cheb<mode>
-void launch_dense_inverse(tb_device *dev, int n, const int64_t *rowptr, const int32_t *colidx, const double *nz, double *C); // C = A⁻¹ of a CSR with n ≤ MG_COARSEST_MAX rows
+// C = A⁻¹ of a CSR with n ≤ MG_COARSEST_MAX rows.  general = false: no pivoting, symmetrised (a symmetric positive definite level).  general = true:
+// partial pivoting, nothing symmetrised (any non-singular level); the kernel leaves 0, or 1 + the elimination step whose pivot was zero or not
+// finite, in the device's read-back line, and dense_inverse_status reads it.
+void launch_dense_inverse(tb_device *dev, int n, const int64_t *rowptr, const int32_t *colidx, const double *nz, double *C, bool general = false);
+int dense_inverse_status(tb_device *dev, const char *who, int level, int n); // after a general launch_dense_inverse: TB_ERR_BAD_ARG and a message naming `who` and the level on a failed pivot; reads back
 void launch_fill_diag(tb_device *dev, int64_t n, const int64_t *diagpos, const uint8_t *flags, double *A); // flagged diagonals ← mean |diagonal| of the others
 void launch_fold_sum(tb_device *dev, int nb, const double *part, double *out);                              // *out = Σ part[0 … nb) in one fixed order
 void launch_fold_max(tb_device *dev, int nb, const double *part, double *out);                              // *out = max part[0 … nb), part ≥ 0
@@ -156,6 +160,7 @@ struct tb_mg {
     tb_device *dev = nullptr;
     std::vector<tb::MgLevel> lv;
     bool planned = false, ready = false;
+    bool general = false;     // tb_mg_set_general: the operator need not be symmetric — the coarsest inverse is pivoted and not symmetrised
     int degree = 2;
     double ratio = 4.0;
     double *d_cinv = nullptr; // dense inverse of the coarsest operator

@@ -196,6 +196,103 @@ k_mg_dense_inverse(int n, const int64_t *__restrict__ rowptr, const int32_t *__r
     mg_gauss_jordan(n, C);
 }
 
+// The same for an operator that need not be symmetric (tb_mg_set_general, tb_amg_set_general): Gauss–Jordan elimination in place with partial (row)
+// pivoting, nothing symmetrised.  Step k: every thread holds one row and offers |C[row][k]| for the rows k … n − 1 (a NaN counts as +∞, so that it is
+// chosen and reported); a butterfly picks the wave's largest, a fold over the 16 waves in LDS the workgroup's — ties go to the lowest row in both, so
+// two set-ups choose the same pivots and give the same bits.  Rows k and p are swapped, the step is mg_gauss_jordan's.  In-place elimination keeps
+// the identity columns implicit, so a row swap at step k is a column swap (k, p) of the result: the swaps are composed in reverse order into one
+// column map in LDS and every row is gathered through it at the end (a wave per row: the whole row is in registers before any of it is stored).
+// *status = 0, or 1 + the step whose pivot was zero or not finite (the workgroup leaves there; C is then of no use).
+__global__ void __launch_bounds__(1024)
+k_mg_dense_inverse_pivot(int n, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, const double *__restrict__ nz, double *__restrict__ C,
+                         double *__restrict__ status)
+{
+    __shared__ double s_val[16];
+    __shared__ int s_row[16];
+    __shared__ int s_piv[MG_COARSEST_MAX], s_map[MG_COARSEST_MAX]; // the row swapped with row k at step k; the column map of the end
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = blockDim.x >> 6; // (launched with MG_COARSEST_MAX threads: a row each)
+    for (int i = wv; i < n; i += nw)
+        for (int j = lane; j < n; j += 64) C[(size_t)i * n + j] = 0.0;
+    __syncthreads();
+    for (int i = wv; i < n; i += nw)
+        for (int64_t k = rowptr[i] + lane; k < rowptr[i + 1]; k += 64) C[(size_t)i * n + colidx[k]] = nz[k];
+    __syncthreads();
+    for (int k = 0; k < n; ++k) {
+        double a = -1.0;
+        int row = 0x7fffffff;
+        if (tid >= k && tid < n) {
+            a = fabs(C[(size_t)tid * n + k]);
+            if (a != a) a = __builtin_inf();
+            row = tid;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const double a2 = __shfl_xor(a, o, 64);
+            const int r2 = __shfl_xor(row, o, 64);
+            if (a2 > a || (a2 == a && r2 < row)) { a = a2; row = r2; }
+        }
+        if (lane == 0) { s_val[wv] = a; s_row[wv] = row; }
+        __syncthreads();
+        a = s_val[0]; row = s_row[0];
+        for (int q = 1; q < nw; ++q) {
+            const double a2 = s_val[q];
+            const int r2 = s_row[q];
+            if (a2 > a || (a2 == a && r2 < row)) { a = a2; row = r2; }
+        }
+        const int p = row; // (the same in every thread; k ≤ p < n because row k itself is offered)
+        if (!(a > 0.0) || a == __builtin_inf()) {
+            if (tid == 0) *status = (double)(k + 1);
+            return;
+        }
+        if (tid == 0) s_piv[k] = p;
+        if (p != k)
+            for (int j = tid; j < n; j += blockDim.x) {
+                const double t = C[(size_t)k * n + j];
+                C[(size_t)k * n + j] = C[(size_t)p * n + j];
+                C[(size_t)p * n + j] = t;
+            }
+        __syncthreads(); // (also: nobody overwrites s_val of this step before everyone has folded it)
+        const double piv = 1.0 / C[(size_t)k * n + k];
+        for (int i = wv; i < n; i += nw) {
+            if (i == k) continue;
+            const double f = C[(size_t)i * n + k] * piv;
+            for (int j = lane; j < n; j += 64)
+                if (j != k) C[(size_t)i * n + j] -= f * C[(size_t)k * n + j];
+        }
+        __syncthreads();
+        for (int j = tid; j < n; j += blockDim.x)
+            if (j != k) { C[(size_t)k * n + j] *= piv; C[(size_t)j * n + k] *= -piv; }
+        if (tid == 0) C[(size_t)k * n + k] = piv;
+        __syncthreads();
+    }
+    if (tid == 0) { // result[:, j] = C[:, map[j]]: the column swaps (k, p_k) for k = n − 1 … 0, composed
+        for (int j = 0; j < n; ++j) s_map[j] = j;
+        for (int k = n - 1; k >= 0; --k) {
+            const int p = s_piv[k];
+            const int t = s_map[k]; s_map[k] = s_map[p]; s_map[p] = t;
+        }
+        *status = 0.0;
+    }
+    __syncthreads();
+    for (int i0 = 0; i0 < n; i0 += nw) { // (uniform trip count: the barrier below is reached by every wave)
+        const int i = i0 + wv;
+        double v[MG_COARSEST_MAX / 64];
+#pragma unroll
+        for (int t = 0; t < MG_COARSEST_MAX / 64; ++t) {
+            const int j = lane + 64 * t;
+            v[t] = i < n && j < n ? C[(size_t)i * n + s_map[j]] : 0.0;
+        }
+        // A lane stores to column j what another lane of the same wave loaded from column s_map[j], and a lane's store depends on its own loads only:
+        // the barrier brings the wait for every lane's loads (vmcnt 0) in front of the first store.  Nothing is ordered between waves: a row is one wave's.
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < MG_COARSEST_MAX / 64; ++t) {
+            const int j = lane + 64 * t;
+            if (i < n && j < n) C[(size_t)i * n + j] = v[t];
+        }
+    }
+}
+
 // x = C r, dense: one wavefront per row
 __global__ void __launch_bounds__(256)
 k_mg_dense_apply(int n, const double *__restrict__ C, const double *__restrict__ r, double *__restrict__ x)
@@ -257,6 +354,7 @@ static int create_coarse_amg(tb_mg *mg)
             comp[(size_t)m->h_cell_dofs[q]] = (int8_t)((q % (size_t)m->ndpc) % (size_t)m->ncomp);
     }
     TB_TRY(tb_amg_create(pat, comp.empty() ? nullptr : comp.data(), mg->amg_theta, mg->amg_max_coarse, mg->amg_max_levels, &mg->amg));
+    TB_TRY(tb_amg_set_general(mg->amg, mg->general ? 1 : 0)); // the mode the hierarchy has when its plans are built; tb_mg_set_general forwards every later change
     if (mg->amg_nns_k) {
         TB_REQUIRE((int64_t)mg->amg_nns_node.size() == pat->n_rows, "tb_mg_set_coarse_amg_near_nullspace: the arrays were sized for %lld dofs, level 0 has %lld",
                    (long long)mg->amg_nns_node.size(), (long long)pat->n_rows);
@@ -373,9 +471,21 @@ void launch_cheb_step(tb_device *dev, int mode, int64_t n, ChebSchedule::Step c,
     auto *k = mode == 0 ? k_mg_cheb<0> : mode == 1 ? k_mg_cheb<1> : k_mg_cheb<2>;
     hipLaunchKernelGGL(k, dim3(grid_for(dev, n, 256)), dim3(256), 0, dev->stream, n, c.c1, c.c2, dinv, r, w, d, x);
 }
-void launch_dense_inverse(tb_device *dev, int n, const int64_t *rowptr, const int32_t *colidx, const double *nz, double *C)
+void launch_dense_inverse(tb_device *dev, int n, const int64_t *rowptr, const int32_t *colidx, const double *nz, double *C, bool general)
 {
-    hipLaunchKernelGGL(k_mg_dense_inverse, dim3(1), dim3(1024), 0, dev->stream, n, rowptr, colidx, nz, C);
+    if (general) hipLaunchKernelGGL(k_mg_dense_inverse_pivot, dim3(1), dim3(MG_COARSEST_MAX), 0, dev->stream, n, rowptr, colidx, nz, C, dev->d_readback);
+    else hipLaunchKernelGGL(k_mg_dense_inverse, dim3(1), dim3(1024), 0, dev->stream, n, rowptr, colidx, nz, C);
+}
+int dense_inverse_status(tb_device *dev, const char *who, int level, int n)
+{
+    double step = 0.0;
+    TB_TRY(read_back(dev, &step, dev->d_readback, 1));
+    if (step != 0.0) {
+        set_error("%s: the operator of level %d (%d dofs, inverted densely) is singular or not finite: no usable pivot at elimination step %d of the pivoted "
+                  "Gauss-Jordan inverse (general mode)", who, level, n, (int)step - 1);
+        return TB_ERR_BAD_ARG;
+    }
+    return TB_OK;
 }
 void launch_fill_diag(tb_device *dev, int64_t n, const int64_t *diagpos, const uint8_t *flags, double *A)
 {
@@ -579,6 +689,16 @@ int tb_mg_set_coarse_amg_near_nullspace(tb_mg *mg, int64_t n_nodes, const int32_
     return TB_OK;
 }
 
+int tb_mg_set_general(tb_mg *mg, int general)
+{
+    TB_REQUIRE(mg, "tb_mg_set_general: NULL argument");
+    if (mg->general == (general != 0)) return TB_OK;
+    mg->general = general != 0;
+    mg->ready = false; // the numeric phase is redone by the next tb_mg_setup (the plans stay); the AMG below level 0 takes the flag there
+    if (mg->amg) TB_TRY(tb_amg_set_general(mg->amg, general));
+    return TB_OK;
+}
+
 int tb_mg_coarse_amg(tb_mg *mg, tb_amg **out)
 {
     TB_REQUIRE(mg && out, "tb_mg_coarse_amg: NULL argument");
@@ -621,8 +741,10 @@ int tb_mg_setup(tb_mg *mg, const double *d_Anz_fine, int degree, double interval
     if (mg->amg) { // the AMG below level 0: planned at its first setup, numeric phase only afterwards
         const int rc = tb_amg_setup(mg->amg, C0.A, degree, interval_ratio);
         if (rc) { free_plans(mg); return rc; }
-    } else
-        launch_dense_inverse(dev, (int)C0.n, C0.pat->d_rowptr, C0.pat->d_colidx, C0.A, mg->d_cinv);
+    } else {
+        launch_dense_inverse(dev, (int)C0.n, C0.pat->d_rowptr, C0.pat->d_colidx, C0.A, mg->d_cinv, mg->general);
+        if (mg->general) TB_TRY(dense_inverse_status(dev, "tb_mg_setup", 0, (int)C0.n));
+    }
     TB_HIP(hipGetLastError());
     mg->ready = true;
     return TB_OK;
@@ -700,4 +822,17 @@ int tb_pcg_solve_mg(tb_pattern *pat, const double *d_Anz, const double *d_b, dou
     TB_REQUIRE(mg->lv.back().A == d_Anz, "tb_pcg_solve_mg: the hierarchy was set up with another matrix array (tb_mg_setup follows every new matrix)");
     TB_HIP(hipSetDevice(pat->mesh->dev->id));
     return launch_pcg_apply(pat, d_Anz, d_b, d_x, rtol, atol, maxiter, mg_apply_cb, mg, "multigrid preconditioner", iters, resnorm);
+}
+
+int tb_gmres_solve_mg(tb_pattern *pat, const double *d_Anz, const double *d_b, double *d_x, double rtol, double atol, int maxiter, int restart, tb_mg *mg,
+                      int *iters, double *resnorm)
+{
+    TB_REQUIRE(pat && d_Anz && d_b && d_x && mg, "tb_gmres_solve_mg: NULL argument");
+    TB_REQUIRE(rtol >= 0 && atol >= 0 && maxiter >= 0, "tb_gmres_solve_mg: negative tolerance or iteration limit");
+    TB_REQUIRE(restart >= 1 && restart <= 1000, "tb_gmres_solve_mg: restart must be in 1..1000 (got %d)", restart);
+    TB_REQUIRE(mg->ready, "tb_gmres_solve_mg: no numeric setup yet (tb_mg_setup; tb_mg_set_general asks for a new one)");
+    TB_REQUIRE(mg->lv.back().pat == pat, "tb_gmres_solve_mg: the pattern is not the finest level of the hierarchy");
+    TB_REQUIRE(mg->lv.back().A == d_Anz, "tb_gmres_solve_mg: the hierarchy was set up with another matrix array (tb_mg_setup follows every new matrix)");
+    TB_HIP(hipSetDevice(pat->mesh->dev->id));
+    return launch_gmres_apply(pat, d_Anz, d_b, d_x, rtol, atol, maxiter, restart, mg_apply_cb, mg, "tb_gmres_solve_mg", iters, resnorm);
 }

@@ -3,8 +3,12 @@
 coarse operators rebuilt from every new matrix, one V(degree, degree) cycle with a Chebyshev–Jacobi smoother, an explicit coarsest inverse.
 
 Covered: h-levels of first-order hexahedra on the nested grids of a GridHierarchy (GMGPrecon); one p-level from a second-order field to the first-order
-field on the same grid (PMGPrecon), alone or on top of the h-levels (ChainedMGPrecon); one field of 1 or 3 components on the whole grid, CG.  Refused
-with a message: orders above 2, tetrahedra, GMRES, W- and F-cycles, other smoothers, hierarchies over several ranks, subdomain dof handlers."""
+field on the same grid (PMGPrecon), alone or on top of the h-levels (ChainedMGPrecon); one field of 1 or 3 components on the whole grid; CG, and restarted GMRES with the
+cycle as a fixed right preconditioner (gmres_solve(…, precond=…), KrylovMGSolver(KrylovGMRES(restart), mg), NewtonRaphsonSolver(inner_solver="gmres",
+inner_precond=…)) for MILDLY non-symmetric matrices with a positive diagonal: the hierarchy then runs in general mode, whose coarsest inverse is
+pivoted and not symmetrised (the point-Jacobi Chebyshev smoother breaks down when the skew part is as large as the symmetric one).  One hierarchy
+serves one kind of solve cheaply: CG after GMRES on it, or the other way round, flips the mode and sets up again.  Refused with a message: orders
+above 2, tetrahedra, W- and F-cycles, other smoothers, hierarchies over several ranks, subdomain dof handlers."""
 import ctypes as C
 
 import numpy as np
@@ -171,10 +175,24 @@ class MultigridHierarchy:
     def n_levels(self):
         return len(self.patterns)
 
+    general = False          # set_general: the matrix need not be symmetric (pivoted coarsest inverse, nothing symmetrised)
+    n_setups = 0             # numeric set-ups so far
+
+    def set_general(self, general):
+        """general mode on or off (tb_mg_set_general; it reaches the AMG of coarse=AMGPrecon(…) too); a change drops the numeric phase, so the next
+        solve or `setup` redoes it"""
+        general = bool(general)
+        if general != self.general:
+            check(lib().tb_mg_set_general(self.h, int(general)))
+            self.general = general
+            self._A = None
+        return self
+
     def setup(self, A):
         """the numeric phase for the matrix values `A` (after apply_zero): Galerkin chain, D⁻¹, λmax per level, coarsest inverse"""
         check(lib().tb_mg_setup(self.h, _ptr(A), self.degree, self.interval_ratio))
         self._A = A                                  # the cycle reads the array: keep it alive
+        self.n_setups += 1
         return self
 
     def apply(self, r, z):
@@ -182,7 +200,9 @@ class MultigridHierarchy:
         return z
 
     def coarse_hierarchy(self):
-        """the AMG hierarchy below level 0 (coarse=AMGPrecon(…), after one setup) as an AlgebraicHierarchy to inspect; this object keeps owning it"""
+        """the AMG hierarchy below level 0 (coarse=AMGPrecon(…), after one setup) as an AlgebraicHierarchy to inspect; this object keeps owning it.  The
+        view is taken afresh at every call: its `general` is this hierarchy's mode and its `n_setups` this hierarchy's count at that moment (every set-up
+        of this hierarchy sets the AMG up too), and the mode is changed through this hierarchy's set_general only — the view's refuses"""
         h = C.c_void_p()
         check(lib().tb_mg_coarse_amg(self.h, C.byref(h)))
         if not h:
@@ -190,6 +210,11 @@ class MultigridHierarchy:
         view = AlgebraicHierarchy.__new__(AlgebraicHierarchy)
         view.device, view.pattern, view.degree, view.interval_ratio, view.h, view._A, view.owner = self.device, self.patterns[0], self.degree, self.interval_ratio, h, None, self
         view.close = lambda: None
+        view.general, view.n_setups = self.general, self.n_setups
+
+        def refuse(general):
+            raise RuntimeError("the AMG below level 0 takes its mode from the hierarchy that owns it: call set_general on the MultigridHierarchy")
+        view.set_general = refuse
         view.k = 0 if self.coarse is None or self.coarse.near_nullspace is None else 6 if isinstance(self.coarse.near_nullspace, str) else np.shape(self.coarse.near_nullspace)[1]
         return view
 
@@ -234,10 +259,23 @@ class MultigridHierarchy:
 
     def solve(self, A, b, x, rtol=1e-5, atol=1e-6, maxiter=1000, setup=True):
         """CG on A x = b preconditioned by one cycle (tb_pcg_solve_mg) → (iterations, residual norm); setup=False reuses the numeric phase"""
+        self.set_general(False)
         if setup or self._A is None:
             self.setup(A)
         it, res = C.c_int(), C.c_double()
         check(lib().tb_pcg_solve_mg(self.pattern.h, _ptr(A), _ptr(b), _ptr(x), float(rtol), float(atol), int(maxiter), self.h, C.byref(it), C.byref(res)))
+        return it.value, res.value
+
+    def solve_gmres(self, A, b, x, rtol=1e-5, atol=1e-6, maxiter=1000, restart=50, setup=True, general=True):
+        """GMRES(restart) on A x = b with one cycle as the fixed right preconditioner (tb_gmres_solve_mg) → (Arnoldi steps, residual norm).  The
+        hierarchy goes to general mode first (general=False keeps the symmetrised coarsest inverse: for measurements); setup=False reuses the
+        numeric phase unless the mode changed"""
+        self.set_general(general)
+        if setup or self._A is None:
+            self.setup(A)
+        it, res = C.c_int(), C.c_double()
+        check(lib().tb_gmres_solve_mg(self.pattern.h, _ptr(A), _ptr(b), _ptr(x), float(rtol), float(atol), int(maxiter), int(restart), self.h, C.byref(it),
+                                      C.byref(res)))
         return it.value, res.value
 
     reuse_setup = False      # set by the Newton loop under simplified_newton: the tangent, and with it the numeric phase, is the previous one
@@ -247,6 +285,12 @@ class MultigridHierarchy:
         if pattern is not self.pattern:
             raise ValueError("pcg_solve: the multigrid hierarchy was materialised for another pattern")
         return self.solve(A, b, x, rtol, atol, maxiter, setup=not self.reuse_setup)
+
+    def tb_mg_gmres_solve(self, pattern, A, b, x, rtol, atol, maxiter, restart):
+        """what gmres_solve(…, precond=<this>) runs"""
+        if pattern is not self.pattern:
+            raise ValueError("gmres_solve: the multigrid hierarchy was materialised for another pattern")
+        return self.solve_gmres(A, b, x, rtol, atol, maxiter, restart, setup=not self.reuse_setup)
 
     def close(self):
         if self.h:
@@ -260,20 +304,38 @@ class MultigridHierarchy:
             pass
 
 
+class KrylovGMRES:
+    """KrylovGMRES(restart=50): restarted GMRES as the Krylov method of a KrylovMGSolver — the reference's KrylovJL_GMRES(gmres_restart = …), the
+    default of its KrylovMGSolver (multigrid.jl:114-115, there with a restart of 400)."""
+
+    def __init__(self, restart=50):
+        if int(restart) < 1:
+            raise ValueError("KrylovGMRES: restart must be at least 1 (got %r)" % (restart,))
+        self.restart = int(restart)
+
+    def __repr__(self):
+        return "KrylovGMRES(restart=%d)" % self.restart
+
+
 class KrylovMGSolver:
-    """KrylovMGSolver(krylov, mg, maxiters): a Krylov method preconditioned by a multigrid (multigrid.jl) — CG; usable as the callable inner_solver of
-    NewtonRaphsonSolver ((pattern, J, residual, Δu) → iterations) or through `solve`."""
+    """KrylovMGSolver(krylov, mg, maxiters): a Krylov method preconditioned by a multigrid (multigrid.jl) — "cg", or KrylovGMRES(restart) for matrices
+    that are not symmetric (the hierarchy then runs in general mode); usable as the callable inner_solver of NewtonRaphsonSolver ((pattern, J,
+    residual, Δu) → iterations) or through `solve`."""
 
     def __init__(self, krylov="cg", mg=None, maxiters=None, rtol=1e-8, atol=1e-14):
-        if krylov != "cg":
-            raise NotImplementedError("KrylovMGSolver(%r): the multigrid preconditions CG only (GMRES is out of scope)" % (krylov,))
+        if not isinstance(krylov, KrylovGMRES) and krylov != "cg":
+            raise NotImplementedError("KrylovMGSolver(%r): the Krylov method is \"cg\" or a tb.KrylovGMRES(restart=...) object (GMRES takes its restart "
+                                      "length from there; the bare string is not accepted)" % (krylov,))
         if not isinstance(mg, (GMGPrecon, PMGPrecon, MultigridHierarchy, AMGPrecon, AlgebraicHierarchy)):
             raise TypeError("KrylovMGSolver: mg must be a GMGPrecon, a PMGPrecon, a ChainedMGPrecon, an AMGPrecon or a materialised hierarchy")
-        self.mg, self.maxiters, self.rtol, self.atol = mg, maxiters, rtol, atol
+        self.krylov, self.mg, self.maxiters, self.rtol, self.atol = krylov, mg, maxiters, rtol, atol
 
     def solve(self, pattern, A, b, x, ch=None):
         mg = self.mg.materialize(pattern, ch) if hasattr(self.mg, "materialize") else self.mg
-        return mg.solve(A, b, x, self.rtol, self.atol, self.maxiters if self.maxiters is not None else 1000)
+        maxiter = self.maxiters if self.maxiters is not None else 1000
+        if isinstance(self.krylov, KrylovGMRES):
+            return mg.solve_gmres(A, b, x, self.rtol, self.atol, maxiter, self.krylov.restart)
+        return mg.solve(A, b, x, self.rtol, self.atol, maxiter)
 
     def __call__(self, pattern, J, b, x):
         return self.solve(pattern, J, b, x)[0]

@@ -824,7 +824,8 @@ class NewtonRaphsonSolver:
     follows :215-320 — update_linearization!, eliminate constraints, residual norm over the free dofs, linear solve,
     eliminate the increment, u .-= Δu, Θₖ contraction monitor, early exits.  inner_solver: "cg" (Jacobi-PCG; symmetric positive
     definite tangents) or "gmres" (restarted, right-Jacobi; the reference's default KrylovJL_GMRES — for indefinite or
-    non-symmetric tangents), or — LinearSolve.jl's pluggability — any callable (pattern, J, residual, Δu) → iterations that leaves the
+    non-symmetric tangents; with inner_precond = a multigrid recipe — GMGPrecon, ChainedMGPrecon, AMGPrecon … — one V cycle in general mode is its
+    right preconditioner instead, for mildly non-symmetric tangents with a positive diagonal: the reference's GMRES + GMGPrecon pairing), or — LinearSolve.jl's pluggability — any callable (pattern, J, residual, Δu) → iterations that leaves the
     solution of J Δu = residual in Δu (device vectors; the CSR structure is `pattern.sp.rowptr/colidx` on the host, J its values on the device),
     or a BlockedLinearSolver for a blocked system (nlsolve(…, system=…))."""
 
@@ -833,7 +834,7 @@ class NewtonRaphsonSolver:
         if not isinstance(inner_solver, BlockedLinearSolver) and inner_solver not in ("cg", "gmres") and not callable(inner_solver):
             raise ValueError("inner_solver: 'cg', 'gmres', a callable (pattern, J, residual, Δu) -> linear iterations or a BlockedLinearSolver")
         self.inner_solver, self.gmres_restart = inner_solver, gmres_restart
-        self.inner_precond = inner_precond          # None (Jacobi, device-scalar CG), L1GSPrecBuilder(partsize) or ChebyshevPrecBuilder(degree)
+        self.inner_precond = inner_precond          # None (Jacobi, device-scalar CG), L1GSPrecBuilder(partsize), ChebyshevPrecBuilder(degree) or a multigrid recipe
         # simplified_newton: the tangent of the first iteration is reused, later iterations assemble the residual only (residual!);
         # forcing: EisenstatWalkerForcing() adapts the inner Krylov tolerance (ignored by callable inner solvers, as by direct ones)
         self.simplified_newton, self.forcing = bool(simplified_newton), forcing
@@ -891,7 +892,10 @@ class DisplacementSystem:
             # extension rebuilds the coarse operators per solve) and stays while simplified_newton keeps the tangent
             mg = solver.inner_precond.materialize(self.op.pattern, self.ch)
             mg.reuse_setup = not getattr(solver, "jacobian_is_fresh", True)
-            its, lres = pcg_solve(self.op.pattern, self.op.J, res, du, inner_rtol, solver.inner_atol, solver.inner_maxiter, mg)
+            if solver.inner_solver == "gmres":               # a non-symmetric tangent (follower loads): the cycle as the right preconditioner of GMRES
+                its, lres = gmres_solve(self.op.pattern, self.op.J, res, du, inner_rtol, solver.inner_atol, solver.inner_maxiter, solver.gmres_restart, precond=mg)
+            else:
+                its, lres = pcg_solve(self.op.pattern, self.op.J, res, du, inner_rtol, solver.inner_atol, solver.inner_maxiter, mg)
             return its, lres, solve_converged(self.op.pattern, lres)
         its, lres = inner_linear_solve(solver, self.op.pattern, self.op.J, res, du, inner_rtol)
         return its, lres, lres is None or solve_converged(self.op.pattern, lres)
